@@ -16,16 +16,27 @@ fused STREAM launch over the next int(I·ln I / 256)·256 shuffled triples (samp
 ML-20M-shaped user shard; the item table is replicated and reconciled by an asynchronous
 all-reduce of item deltas every --sync-every steps (revisit_bpr/distributed.py).
 
-Prints ONE JSON line (rank 0).  `value` (r6) = the TRAINED state: after the driver's K-step region (`timed_region`)
-and three whole epochs from random init (`early_state` / `sustained`: what r1-r5 called `value`) the job trains on,
-untimed, to 30 epochs, and epochs 31..130 are timed by wall clock between barriers, every `bpr_plan_epoch` in place,
-nothing modelled (`steady_state`; its `first_epoch` is epoch 31 alone) — once the adaptive sampler has a model to
-adapt to its negatives concentrate on popular rows and a launch costs more than on tables fresh from their random
-init: a long job lives in that state.  `steps` = the steps behind `value`.  `roofline`: dominant kernel = the fused
-stream kernel on that state, HBM bound, algorithmic bytes 24·d+8 per triple, duration from hipEvents recorded by
-the library on the launch stream; `traffic` REPLAYED from committed rocprofv3 --pmc passes of the same state
-(profiles/traffic_r06.json), never measured in-run.  `cpu_baseline`: the reference's op sequence restated on CPU
-tensors, `cpu_baseline_c_port`: the C oracle with OpenMP — both on this host's cores over a bounded sample.
+Prints ONE JSON line (rank 0).  `value` = the TRAINED state: the job trains, untimed, for --trained-epochs (80) whole
+epochs from random init, and the next K = --steps steps (the last --warmup before them untimed too) are timed by wall
+clock between barriers (`trained_region`).  The region starts one step past an epoch boundary, so that floor(K / steps
+per epoch) `bpr_plan_epoch` calls fall inside; the share of the plan K steps hold beyond those is added from the plan
+timed on its own, never subtracted.  Once the adaptive sampler has a model to adapt to, its negatives concentrate on
+popular rows and a launch costs more than on tables fresh from their random init: a long job lives in that state.
+`steps` = K, `ms_per_step` = the K steps' time / K.
+--dump-outputs DIR writes, after the timed steps, what the step function computes from the seeded inputs: the tables
+after steps 0 and 1 of the job as DIR/<name>.npy (step 1 is the first on the timed schedule: lagged snapshot committed,
+next one cut, hot block folded, LDS tier), so that two builds compare output for output.  The tables after the K timed
+steps differ from run to run: the STREAM kernel applies a launch's triples concurrently and the adaptive sampler turns
+the last bits that leaves into other negatives.
+
+--full adds, in the same job and before the headline's steps: the K-step region from random init after --warmup + 1
+steps (`timed_region`), whole epochs from random init (`early_state` / `sustained`: what r1-r5 called `value`),
+epochs 31..130 (--steady-epochs, --steady-timed-epochs) of the trained state (`steady_state`: r6's headline); the
+headline's K steps then run after them, at least --trained-epochs deep; and the epoch plan timed alone, `roofline`: dominant kernel = the fused stream kernel on the trained state, HBM bound, algorithmic bytes 24·d+8
+per triple, duration from hipEvents recorded by the library on the launch stream; `traffic` REPLAYED from committed
+rocprofv3 --pmc passes of the same state (profiles/traffic_r06.json), never measured in-run.  `cpu_baseline`: the
+reference's op sequence restated on CPU tensors, `cpu_baseline_c_port`: the C oracle with OpenMP — both on this
+host's cores over a bounded sample.
 The schedule (snapshot one launch older on 32 masked CUs, asynchronous cut, LDS tier of the hot block) is what
 `fast.StreamTrainer` picks by itself at the workload's learning rate (`fast.lag_within_budget`).
 """
@@ -147,8 +158,20 @@ TRAFFIC_FILES = {
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=96)
-    ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=96,
+                    help="timed steps of the headline: consecutive steps of the job on the trained state")
+    ap.add_argument("--warmup", type=int, default=8,
+                    help="untimed steps of the job right before the timed ones (at least this many)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run and report everything beside the headline: the K-step region and whole epochs from "
+                         "random init (`timed_region`, `sustained` / `early_state`), --steady-timed-epochs whole epochs "
+                         "of the trained state (`steady_state`), the epoch plan alone, the rooflines (hipEvent kernel "
+                         "timing), the item reconciliation's timing and the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the step function computed from the seeded inputs — the "
+                         "item table, a fixed seeded sample of the user rows, the item bias and the loss / triple "
+                         "counters after steps 0 and 1 of the job, step 1 being the first on the timed schedule — as "
+                         "DIR/<name>.npy")
     ap.add_argument("--workload", default="ml-20m", choices=sorted(WORKLOADS))
     ap.add_argument("--dim", type=int, default=None, help="default: the workload's (WORKLOADS)")
     ap.add_argument("--sampler", choices=["adaptive", "uniform", "given"], default=None)
@@ -194,7 +217,7 @@ def parse_args():
     ap.add_argument("--scale", type=float, default=1.0, help="shrink users/actions (debug)")
     ap.add_argument("--max-inflight", type=int, default=0)
     ap.add_argument("--time-every", type=int, default=8,
-                    help="hipEvent timing of the dominant kernel on every N-th launch of the timed region")
+                    help="--full: hipEvent timing of the dominant kernel on every N-th launch of the timed regions")
     ap.add_argument("--run-len", type=int, default=0, help="0: chosen by the library from the launch size")
     ap.add_argument("--refresh-lag", type=float, default=None,
                     help="adaptive snapshot schedule (DESIGN.md §4.3): 0 = sorted between launches "
@@ -236,19 +259,24 @@ def parse_args():
                          "its RQ configs switch it on).  Single GPU only here (a measurement aid: "
                          "profiles/shapes_r04.txt); the default 0 is the model every earlier round timed")
     ap.add_argument("--sustained-epochs", type=int, default=3,
-                    help="after the K-step region: this many WHOLE epochs (every plan and every step in place) timed "
-                         "by wall clock between barriers — the headline `value`, on tables a few epochs from their "
-                         "random init as every round's line was (-1: as many as make ~0.6 s of work; 0 = skip: "
-                         "`value` is then the K-step region's).  See --steady-epochs for the trained state")
+                    help="--full, after the K-step region: this many WHOLE epochs (every plan and every step in place) "
+                         "timed by wall clock between barriers — `early_state` / `sustained`, on tables a few epochs from "
+                         "their random init as every round's line up to r5 was (-1: as many as make ~0.6 s of work; 0 = "
+                         "skip).  See --steady-epochs for the trained state")
+    ap.add_argument("--trained-epochs", type=int, default=80,
+                    help="the headline's trained state: the job trains on, untimed, until this many epochs are done before "
+                         "the --steps timed steps start (0 = from random init).  The adaptive sampler's negatives "
+                         "concentrate on popular rows and its walks get deeper once the model has moved (DESIGN.md §4.1 r5; "
+                         "tools/trained_state_probe.py): a long job sees this state, the first epochs from random init see "
+                         "`early_state`.  80 = the middle of epochs 31..130, whose whole-epoch rate r6's headline was (the "
+                         "rate still rises along them: 808 M triples/s on epoch 32, 831 M over the 100)")
     ap.add_argument("--steady-epochs", type=int, default=30,
-                    help="after the sustained region the job trains on, untimed, until this many epochs are done, and "
-                         "ONE more epoch is timed by wall clock: `steady_state` (0 = skip).  The adaptive sampler's "
-                         "negatives concentrate on popular rows and its walks get deeper once the model has moved "
-                         "(DESIGN.md §4.1 r5; tools/trained_state_probe.py): a long job sees this number, the first "
-                         "epochs from random init see `value`")
+                    help="--full, after the sustained region: the job trains on, untimed, until this many epochs are "
+                         "done, and --steady-timed-epochs whole epochs are timed by wall clock: `steady_state` (0 = "
+                         "skip); the headline's steps come after them")
     ap.add_argument("--steady-timed-epochs", type=int, default=100,
-                    help="whole epochs timed for the steady state — the headline `value` (r6): epochs steady-epochs + 1 .. "
-                         "steady-epochs + this many of the same job, by wall clock between barriers")
+                    help="--full: whole epochs timed for `steady_state` (r6's headline), by wall clock between barriers: "
+                         "epochs steady-epochs + 1 .. steady-epochs + this many of the same job")
     ap.add_argument("--launch-split", type=int, default=0,
                     help="launches per refresh period that read the same snapshot (fast.StreamTrainer launch_split); 0 = "
                          "auto: 2 outside the one-rank budget lr x 2 x period <= 2,000, else 1")
@@ -265,8 +293,8 @@ def parse_args():
                          "first node run; tests/test_gpu_bench.py)")
     ap.add_argument("--split-cold-mb", type=float, default=0.0,
                     help="N>1: all-reduces of at least this many MB run as reduce-scatter + all-gather (0 = off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baselines out")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: timed seconds of the C port's baseline")
     ap.add_argument("--seed", type=int, default=13)
     args = ap.parse_args()
     w = WORKLOADS[args.workload]
@@ -577,6 +605,7 @@ def main():
     fused_sync = (lag >= 1.0 and sync is not None and sync.hot_tier and sync.can_fuse and args.sync_every == 1
                   and bool(args.fuse_sync))
     synced = [False]
+    ran = [0]  # steps run so far: each adds `chunk` triples to scalars[3]
     # --async-cut: the snapshot cut leaves the launch stream (bpr_train_stream_acut: a read-only pass on the
     # side stream beside the next launch); the hot rows are folded before the tables are read
     from revisit_bpr.fast import auto_async_cut
@@ -630,7 +659,40 @@ def main():
                 elif sync is not None and sync.hot_tier:
                     sync.hot_step()
 
+    # --dump-outputs: what the step function computes from the benchmark's seeded inputs — the tables after steps 0 and
+    # 1 of the job.  Step 1 is the first on the timed steps' schedule: it commits the snapshot sorted beside step 0's
+    # launch and samples from it (lag 1), its launch cuts the next snapshot (fused or asynchronous), the hot block is
+    # folded and the LDS tier runs.  Later tables are not comparable run to run: the STREAM kernel applies a launch's
+    # triples concurrently and the adaptive sampler turns those last-bit differences into other
+    # negatives within a few steps (two runs of 200 steps from the same inputs: 3e-2 relative; after the 80 untimed
+    # epochs of the headline: 0.6).  Reading the tables there folds the hot block and flushes the lazy optimizer state
+    # one step early and synchronizes the device: a run with --dump-outputs runs that much of a different job, untimed.
+    DUMP_STEP = 1
+    first_step = {}
+
+    def keep_first_step():
+        first_step["lds_rows"] = e.stream_lds_rows()
+        if acut:
+            e.hot_fold()  # the item table whole for a reader
+        if batched:
+            e.flush_lazy()  # the lazily applied optimizer state of the batched kernel, as a reader would see it
+        torch.cuda.synchronize()
+
+        def rows(t, budget, seed_rows):  # all rows where they fit, else a fixed seeded sample of them
+            n = t.shape[0]
+            fit = max(1, budget // (t[0].numel() * t.element_size()))
+            if n <= fit:
+                return t.cpu().numpy()
+            idx = np.sort(np.random.default_rng(seed_rows).choice(n, size=fit, replace=False))
+            return t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+
+        first_step.update(item_emb=rows(Q, 32 << 20, 1), user_emb_sample=rows(P, 24 << 20, 2),
+                          scalars=scalars.double().cpu().numpy())  # steps 0..DUMP_STEP: loss sum, triple count
+        if item_bias is not None:
+            first_step["item_bias"] = item_bias.cpu().numpy()
+
     def step(k: int):
+        ran[0] += 1
         c = k % n_chunks
         lo = c * chunk
         if jit:
@@ -686,6 +748,8 @@ def main():
                 e.flush_items()
             sync.step()
         synced[0] = False
+        if k == DUMP_STEP and args.dump_outputs and rank == 0:
+            keep_first_step()
 
     def barrier():
         torch.cuda.synchronize()
@@ -697,24 +761,31 @@ def main():
     on_main = torch.cuda.stream(main_stream.torch) if main_stream is not None else contextlib.nullcontext()
     q_before = Q.double().sum().item(), Q.abs().double().sum().item()
     torch.cuda.synchronize()
-    # The timed region is K consecutive steps in their natural order (step k = chunk k mod n_chunks;
-    # an epoch = n_chunks steps and starts with a bpr_plan_epoch).  With the driver's short regions
-    # no epoch boundary may fall inside: the plan is then timed separately (after the region) and
-    # its amortised share — K / n_chunks plans — is ADDED to the measured time, never subtracted.
-    k0 = 0
-    with on_main:
-        for k in range(k0, k0 + args.warmup + 1):
+
+    def dump_outputs():
+        """--dump-outputs DIR: the tables after step DUMP_STEP (`first_step`) as float32 / float64 DIR/<name>.npy, 64 MB
+        at most — the item table, a fixed seeded sample of the user rows, the item bias, the loss and triple counters."""
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        arrays = {k: v for k, v in first_step.items() if k != "lds_rows"}
+        for name, a in arrays.items():
+            np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64
+                                                                   else np.float32))
+        return sorted(arrays)
+
+    def trained_region(k_from: int):
+        """The headline: `--steps` consecutive steps of the job on the trained state, by wall clock between barriers,
+        every bpr_plan_epoch in place where it falls, nothing modelled.  Steps k_from.. run untimed until at least
+        `--trained-epochs` epochs are done and `--warmup` steps have run; the region then starts one step past an epoch
+        boundary, so that the plans inside are floor(K / steps per epoch); the share of the plan K steps hold beyond
+        those is added from the plan timed on its own (time_plan), never subtracted."""
+        lo = max(args.trained_epochs * n_chunks + 1, k_from + args.warmup)
+        k_t = -(-(lo - 1) // n_chunks) * n_chunks + 1
+        for k in range(k_from, k_t):
             step(k)
         barrier()
-        # hipEvents around every `--time-every`-th launch of the dominant kernel (each timed launch
-        # idles the stream for ~12 us; the rocprofv3 summary under profiles/ times all of them)
-        e.timing_enable(max(1, args.time_every))
-        if sync is not None:
-            sync.timing = True
-        scalars.zero_()
         t0 = time.perf_counter()
-        first = k0 + args.warmup + 1
-        for k in range(first, first + args.steps):
+        for k in range(k_t, k_t + args.steps):
             step(k)
         if sync is not None:
             sync.hot_finish()
@@ -722,51 +793,41 @@ def main():
         if acut:
             e.hot_fold()
         torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
+        h_dt = time.perf_counter() - t0
         barrier()
-        # SUSTAINED: whole epochs in place — every epoch's bpr_plan_epoch where it belongs, nothing
-        # modelled — wall clock over `sus_epochs` x n_chunks steps (the driver's 20-step
-        # region is 5 ms and holds no plan)
-        sus_epochs = args.sustained_epochs
-        if sus_epochs < 0:  # ~0.6 s of work (the K-step region of the driver's --steps 20 is a few ms), >= 3 epochs
-            sus_epochs = int(min(max(math.ceil(0.6 / max(dt / args.steps * n_chunks, 1e-9)), 3), 400))
-            if world > 1:  # the same count on every rank
-                te = torch.tensor([sus_epochs], device=dev)
-                dist.all_reduce(te, op=dist.ReduceOp.MAX)
-                sus_epochs = int(te.item())
-        sus_dt = 0.0
-        if sus_epochs > 0:
-            k_s = ((first + args.steps) // n_chunks + 1) * n_chunks  # the next epoch boundary
-            ts = time.perf_counter()
-            for k in range(k_s, k_s + sus_epochs * n_chunks):
-                step(k)
-            if sync is not None:
-                sync.hot_finish()
-                sync.finish()
-            if acut:
-                e.hot_fold()
-            torch.cuda.synchronize()
-            sus_dt = time.perf_counter() - ts
-            barrier()
-        kernel_ms, launches = e.timing_read()
-        e.timing_enable(False)
-        # STEADY STATE: train on (untimed) to --steady-epochs epochs, then one whole epoch by wall clock
-        steady = None
-        steady_steps = 0
-        if args.steady_epochs > 0:
-            k_now = (k_s + sus_epochs * n_chunks) if sus_epochs > 0 else ((first + args.steps) // n_chunks + 1) * n_chunks
-            k_end = max(args.steady_epochs * n_chunks, k_now)
-            for k in range(k_now, k_end):
+        if world > 1:
+            tt = torch.tensor([h_dt], device=dev, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            h_dt = float(tt.item())
+        region = {"first_step": k_t, "epochs_trained_before": (k_t - 1) // n_chunks, "steps": args.steps,
+                  "warmup": args.warmup, "untimed_steps_before": k_t - k_from,
+                  "plans_inside": sum(1 for k in range(k_t, k_t + args.steps) if k % n_chunks == 0)}
+        return region, h_dt
+
+    steady = None
+    sus_epochs = 0
+    with on_main:
+        if not args.full:
+            region, h_dt = trained_region(0)
+        else:
+            # The K-step region from random init: K consecutive steps in their natural order (step k = chunk k mod
+            # n_chunks; an epoch = n_chunks steps and starts with a bpr_plan_epoch).  With the driver's short regions
+            # no epoch boundary may fall inside: the plan is then timed separately (after the region) and its
+            # amortised share — K / n_chunks plans — is ADDED to the measured time, never subtracted.
+            k0 = 0
+            for k in range(k0, k0 + args.warmup + 1):
                 step(k)
             barrier()
+            # hipEvents around every `--time-every`-th launch of the dominant kernel (each timed launch
+            # idles the stream for ~12 us; the rocprofv3 summary under profiles/ times all of them)
             e.timing_enable(max(1, args.time_every))
-            st_epochs = max(1, args.steady_timed_epochs)
-            tq = time.perf_counter()
-            for k in range(k_end, k_end + n_chunks):  # the first timed epoch on its own: r5's `steady_state` was this epoch
-                step(k)
-            torch.cuda.synchronize()
-            st_first = time.perf_counter() - tq
-            for k in range(k_end + n_chunks, k_end + st_epochs * n_chunks):
+            if sync is not None:
+                sync.timing = True
+            scalars.zero_()
+            ran[0] = 0
+            t0 = time.perf_counter()
+            first = k0 + args.warmup + 1
+            for k in range(first, first + args.steps):
                 step(k)
             if sync is not None:
                 sync.hot_finish()
@@ -774,25 +835,77 @@ def main():
             if acut:
                 e.hot_fold()
             torch.cuda.synchronize()
-            st_dt = time.perf_counter() - tq
+            dt = time.perf_counter() - t0
             barrier()
-            st_kernel_ms, st_launches = e.timing_read()
+            # SUSTAINED: whole epochs in place — every epoch's bpr_plan_epoch where it belongs, nothing
+            # modelled — wall clock over `sus_epochs` x n_chunks steps (the driver's 20-step
+            # region is 5 ms and holds no plan)
+            sus_epochs = args.sustained_epochs
+            if sus_epochs < 0:  # ~0.6 s of work (the K-step region of the driver's --steps 20 is a few ms), >= 3 epochs
+                sus_epochs = int(min(max(math.ceil(0.6 / max(dt / args.steps * n_chunks, 1e-9)), 3), 400))
+                if world > 1:  # the same count on every rank
+                    te = torch.tensor([sus_epochs], device=dev)
+                    dist.all_reduce(te, op=dist.ReduceOp.MAX)
+                    sus_epochs = int(te.item())
+            sus_dt = 0.0
+            if sus_epochs > 0:
+                k_s = ((first + args.steps) // n_chunks + 1) * n_chunks  # the next epoch boundary
+                ts = time.perf_counter()
+                for k in range(k_s, k_s + sus_epochs * n_chunks):
+                    step(k)
+                if sync is not None:
+                    sync.hot_finish()
+                    sync.finish()
+                if acut:
+                    e.hot_fold()
+                torch.cuda.synchronize()
+                sus_dt = time.perf_counter() - ts
+                barrier()
+            kernel_ms, launches = e.timing_read()
             e.timing_enable(False)
-            steady_steps = k_end + st_epochs * n_chunks - k_now
-            if world > 1:
-                tt = torch.tensor([st_dt], device=dev, dtype=torch.float64)
-                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-                st_dt = float(tt.item())
-            steady = {"epochs_trained_before": k_end // n_chunks, "epochs": st_epochs, "steps": st_epochs * n_chunks,
-                      "ms_per_step": st_dt * 1e3 / (st_epochs * n_chunks),
-                      "value": st_epochs * n_chunks * chunk * world / st_dt, "kernel_ms_avg": st_kernel_ms,
-                      "kernel_launches_timed": st_launches,
-                      "first_epoch": {"epoch": k_end // n_chunks + 1, "ms_per_step": st_first * 1e3 / n_chunks,
-                                      "value": n_chunks * chunk * world / st_first,
-                                      "note": "the first of the timed epochs alone (what r5 reported as steady_state); rank 0's clock"},
-                      "note": "whole epochs by wall clock (every bpr_plan_epoch in place, nothing modelled) after that many "
-                              "epochs of the same job (lr as configured): the state a long training run is in"}
-        # the epoch plan, timed on its own (3 calls; it does not touch the model)
+            # STEADY STATE: train on (untimed) to --steady-epochs epochs, then --steady-timed-epochs whole epochs by wall clock
+            k_now = (k_s + sus_epochs * n_chunks) if sus_epochs > 0 else ((first + args.steps) // n_chunks + 1) * n_chunks
+            if args.steady_epochs > 0:
+                k_end = max(args.steady_epochs * n_chunks, k_now)
+                for k in range(k_now, k_end):
+                    step(k)
+                barrier()
+                e.timing_enable(max(1, args.time_every))
+                st_epochs = max(1, args.steady_timed_epochs)
+                tq = time.perf_counter()
+                for k in range(k_end, k_end + n_chunks):  # the first timed epoch on its own: r5's `steady_state` was this epoch
+                    step(k)
+                torch.cuda.synchronize()
+                st_first = time.perf_counter() - tq
+                for k in range(k_end + n_chunks, k_end + st_epochs * n_chunks):
+                    step(k)
+                if sync is not None:
+                    sync.hot_finish()
+                    sync.finish()
+                if acut:
+                    e.hot_fold()
+                torch.cuda.synchronize()
+                st_dt = time.perf_counter() - tq
+                barrier()
+                st_kernel_ms, st_launches = e.timing_read()
+                e.timing_enable(False)
+                if world > 1:
+                    tt = torch.tensor([st_dt], device=dev, dtype=torch.float64)
+                    dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                    st_dt = float(tt.item())
+                steady = {"epochs_trained_before": k_end // n_chunks, "epochs": st_epochs, "steps": st_epochs * n_chunks,
+                          "ms_per_step": st_dt * 1e3 / (st_epochs * n_chunks),
+                          "value": st_epochs * n_chunks * chunk * world / st_dt, "kernel_ms_avg": st_kernel_ms,
+                          "kernel_launches_timed": st_launches,
+                          "first_epoch": {"epoch": k_end // n_chunks + 1, "ms_per_step": st_first * 1e3 / n_chunks,
+                                          "value": n_chunks * chunk * world / st_first,
+                                          "note": "the first of the timed epochs alone (what r5 reported as steady_state); rank 0's clock"},
+                          "note": "whole epochs by wall clock (every bpr_plan_epoch in place, nothing modelled) after that many "
+                                  "epochs of the same job (lr as configured): the state a long training run is in"}
+                k_now = k_end + st_epochs * n_chunks
+            # the headline region, as a plain run times it: on to --trained-epochs epochs, then the K steps
+            region, h_dt = trained_region(k_now)
+        # the epoch plan, timed on its own after the job's last step (3 calls; it does not touch the model)
         tp = time.perf_counter()
         for r in range(3):
             if batched:
@@ -801,94 +914,54 @@ def main():
                 e.plan_epoch(src_users, src_items, chunk, seed + 1000 + r, out=(users_e, items_e), sorted_input=users_sorted)
         torch.cuda.synchronize()
         plan_ms = (time.perf_counter() - tp) * 1e3 / 3
-    plans_timed = sum(1 for k in range(first, first + args.steps) if k % n_chunks == 0)
-    dt_measured = dt
-    if jit:  # every chunk's plan ran inside the region (on the side stream): nothing to add
-        plans_timed = args.steps / n_chunks
-    dt += max(0.0, args.steps / n_chunks - plans_timed) * plan_ms * 1e-3
-    if world > 1:
-        t = torch.tensor([dt, sus_dt], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, sus_dt = float(t[0].item()), float(t[1].item())
+    # the headline's amortised plan share: the plans K steps of the job hold beyond those inside the region
+    # (none to add when every chunk is planned inside its step: --jit-plan)
+    h_plans_added = 0.0 if jit else max(0.0, args.steps / n_chunks - region["plans_inside"])
+    h_dt_measured = h_dt
+    h_dt += h_plans_added * plan_ms * 1e-3
+    if args.full:
+        plans_timed = sum(1 for k in range(first, first + args.steps) if k % n_chunks == 0)
+        dt_measured = dt
+        if jit:  # every chunk's plan ran inside the region (on the side stream): nothing to add
+            plans_timed = args.steps / n_chunks
+        dt += max(0.0, args.steps / n_chunks - plans_timed) * plan_ms * 1e-3
+        if world > 1:
+            t = torch.tensor([dt, sus_dt], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt, sus_dt = float(t[0].item()), float(t[1].item())
+    dumped = dump_outputs() if (args.dump_outputs and rank == 0) else None
     sc = scalars.cpu().numpy()
     if batched:
         e.flush_lazy()
     q_after = Q.double().sum().item(), Q.abs().double().sum().item()
-    # a kernel that did nothing cannot produce a number: every triple of the timed region was
-    # counted by the kernel itself, the loss it accumulated is a real -log sigma, the tables moved
-    counted = (args.steps + sus_epochs * n_chunks + steady_steps) * chunk
+    # a kernel that did nothing cannot produce a number: every triple the job ran was counted by the kernel
+    # itself, the loss it accumulated is a real -log sigma, the tables moved
+    counted = ran[0] * chunk
     assert int(round(float(sc[3]))) == counted, (sc[3], counted)
     assert 0.0 < float(sc[0] / sc[3]) < 5.0 and q_after != q_before and torch.isfinite(Q).all()
-    # line-atomics per triple of the chunk planned last (what the L2 atomic units see): 2 item rows
-    # of d*4/128 lines each + one row per piece of every user a run boundary cuts (k_stream's rule)
-    lines_per_row = max(1, (d * 4) // 128)
-    user_atomic_rows = 0.0
-    if not batched:
-        L = e.stream_run_len()  # what the library's last launch used (it picks it from the occupancy)
-        planned_users = cbuf[(first + args.steps - 1) & 1][0] if jit else users_e[:chunk]
-        user_atomic_rows = cut_user_pieces(planned_users, L, not args.ungrouped) / chunk
 
     opt_desc = {"sgd": f"SGD lr={args.lr}", "momentum": f"SGD(momentum 0.9) lr={args.lr}",
                 "adam": f"Adam lr={args.lr} betas={tuple(args.betas)}",
                 "rmsprop": f"RMSprop lr={args.lr} alpha=0.99"}[args.optimizer]
     if rank == 0:
-        triples = args.steps * chunk * world
-        region_value = args.steps * chunk * world / dt_measured  # the K-step region as measured (no plan inside unless an epoch began there)
-        region_value_with_plan = triples / dt
-        # headline (r6): the TRAINED state — whole epochs by wall clock after `--steady-epochs` epochs
-        # of the same job (every plan in place, nothing modelled) — when that leg ran; else the early whole epochs
-        # (`sustained`); else the K-step region.  The early number rides along as `early_state`.
-        early_value = (sus_epochs * n_chunks * chunk * world / sus_dt) if sus_epochs > 0 else region_value_with_plan
-        early_ms = (sus_dt * 1e3 / (sus_epochs * n_chunks)) if sus_epochs > 0 else dt * 1e3 / args.steps
-        early_kernel_ms = kernel_ms
-        if steady is not None:
-            value, ms_per_step, steps_behind = steady["value"], steady["ms_per_step"], steady["steps"]
-            kernel_ms, launches = steady["kernel_ms_avg"], steady["kernel_launches_timed"]
-            value_source = ("steady state: epochs %d..%d of the job (%d whole epochs = %d steps) by wall clock between "
-                            "barriers, every bpr_plan_epoch in place, nothing modelled" %
-                            (steady["epochs_trained_before"] + 1, steady["epochs_trained_before"] + steady["epochs"],
-                             steady["epochs"], steady["steps"]))
-        elif sus_epochs > 0:
-            value, ms_per_step, steps_behind = early_value, early_ms, sus_epochs * n_chunks
-            value_source = ("sustained: %d whole epochs = %d steps from random init by wall clock between barriers, every "
-                            "bpr_plan_epoch in place, nothing modelled" % (sus_epochs, sus_epochs * n_chunks))
-        else:
-            value, ms_per_step, steps_behind = region_value_with_plan, dt * 1e3 / args.steps, args.steps
-            value_source = "the K-step region (+ the plan's amortised share when no epoch began inside it)"
-        # SGD reads and writes 3 rows (+ 2 int32 ids); Adam reads and writes w, m, v of 3
-        # rows (+ ids + 24 B of per-row step marks); momentum / RMSprop carry one state table
-        bytes_per_triple = {"sgd": 24 * d + 8, "adam": 72 * d + 32, "momentum": 48 * d + 32,
-                            "rmsprop": 48 * d + 32}[args.optimizer]
-        # HBM-side bytes per k_stream launch: NOT measured by this run — replayed from the committed
-        # summary of separate rocprofv3 --pmc passes of this same command (profiles/*_pmc_traffic.md:
-        # FETCH_SIZE x2 correction + WRITE_SIZE); null when the run is not the profiled configuration
-        traffic = None
-        tname = TRAFFIC_FILES.get((args.workload, d, args.sampler, args.optimizer))
-        tfile = ROOT / "profiles" / (tname or "none")
-        if tfile.exists() and args.scale == 1.0 and not batched and not args.item_bias:
-            tj = json.loads(tfile.read_text())
-            if tj.get("triples_per_launch") == chunk:
-                traffic = tj["traffic_bytes_per_launch"]
-                if tname == "traffic_r06.json" and (e.lds_launches == 0 or steady is None):
-                    traffic = None  # (that file is the LDS-tier kernel on the trained state: not this run)
-        achieved = (bytes_per_triple * chunk) / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
+        # headline: the TRAINED state — `--steps` steps of the job after `--trained-epochs` epochs of it, by wall clock
+        # between barriers, every plan that falls inside in place, plus the share of the plan K steps hold beyond those
+        value, ms_per_step = args.steps * chunk * world / h_dt, h_dt * 1e3 / args.steps
+        value_source = ("trained state: steps %d..%d of the job (%d steps after %d whole epochs) by wall clock between "
+                        "barriers, %d bpr_plan_epoch inside + %.3f plans' amortised share (the plan timed on its own)" %
+                        (region["first_step"], region["first_step"] + args.steps - 1, args.steps,
+                         region["epochs_trained_before"], region["plans_inside"], h_plans_added))
+        region = dict(region, plans_added=h_plans_added, plan_ms=plan_ms, ms_per_step_measured=h_dt_measured * 1e3 / args.steps)
         out = {
             "metric": "BPR triples/sec at d=128 (1/2/4/8 GPU) + nDCG@100 parity vs reference",
             "value": value,
             "unit": "triples/s",
             "n_gpus": world,
-            "steps": steps_behind,  # the steps behind `value` (the driver's K: timed_region.steps)
+            "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_per_step,
             "value_source": value_source,
-            "early_state": {"value": early_value, "ms_per_step": early_ms, "kernel_ms_avg": early_kernel_ms,
-                            "roofline_frac": ((bytes_per_triple * chunk) / (early_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-                                              if early_kernel_ms > 0 else None),
-                            "note": "the same job on tables a few epochs from their random init (what r1-r5 reported as "
-                                    "`value`): the adaptive sampler's negatives are still uniform over the items there"},
-            "timed_region": {"steps": args.steps, "warmup": args.warmup, "ms_per_step_measured": dt_measured * 1e3 / args.steps,
-                             "value_measured": region_value, "plans_inside": plans_timed,
-                             "value_with_amortised_plan": region_value_with_plan},
+            "trained_region": region,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -919,14 +992,6 @@ def main():
                             f"{sync._hb.shape[0] if sync.hot_tier else 0} rows exchanged after every launch"
                             ) if (world > 1 or emu) else "single GPU",
                 "steps_per_epoch": n_chunks,
-                "plan_epoch": {"mode": ("per chunk, one step ahead, on the side stream behind the sort "
-                                        "(bpr_plan_chunk): inside every step") if jit else
-                                       ("bpr_plan_epoch per epoch, the next epoch's beside this epoch's launches on a "
-                                        "third stream masked to the sorter's CUs") if plan_ahead else "bpr_plan_epoch per epoch",
-                               "ms": plan_ms, "inside_timed_region": plans_timed,
-                               "amortised_share_added_ms_per_step":
-                                   max(0.0, args.steps / n_chunks - plans_timed) * plan_ms / args.steps,
-                               "ms_per_step_measured": dt_measured * 1e3 / args.steps},
                 "parallelism": f"user-sharded x{world}, item table replicated, async delta "
                                f"all-reduce every {args.sync_every} step(s)" if world > 1 else "single GPU",
                 "parity": PARITY_OF_TIMED_SCHEDULE if (world == 1 and lag >= 1.0 and not batched) else None,
@@ -934,7 +999,60 @@ def main():
                 "triples_counted_by_kernel": int(round(float(sc[3]))),
                 "item_table_abs_sum_before_after": [q_before[1], q_after[1]],
             },
-            "roofline": {
+        }
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": str(args.dump_outputs), "arrays": dumped, "after_step": DUMP_STEP,
+                                     "lds_rows_of_that_launch": first_step["lds_rows"]}
+        if rccl_ranks_seen is not None:
+            out["rccl_ranks_seen"] = rccl_ranks_seen
+            out["dist_backend"] = dist.get_backend()
+            out["forced_distributed"] = forced
+        if args.full:
+            triples = args.steps * chunk * world
+            region_value = triples / dt_measured  # the K-step region as measured (no plan inside unless an epoch began there)
+            region_value_with_plan = triples / dt
+            # the early whole epochs (`sustained`: what r1-r5 called `value`), else the K-step region
+            early_value = (sus_epochs * n_chunks * chunk * world / sus_dt) if sus_epochs > 0 else region_value_with_plan
+            early_ms = (sus_dt * 1e3 / (sus_epochs * n_chunks)) if sus_epochs > 0 else dt * 1e3 / args.steps
+            early_kernel_ms = kernel_ms
+            if steady is not None:  # the roofline is the trained state's whole epochs
+                kernel_ms, launches = steady["kernel_ms_avg"], steady["kernel_launches_timed"]
+            # SGD reads and writes 3 rows (+ 2 int32 ids); Adam reads and writes w, m, v of 3
+            # rows (+ ids + 24 B of per-row step marks); momentum / RMSprop carry one state table
+            bytes_per_triple = {"sgd": 24 * d + 8, "adam": 72 * d + 32, "momentum": 48 * d + 32,
+                                "rmsprop": 48 * d + 32}[args.optimizer]
+            # HBM-side bytes per k_stream launch: NOT measured by this run — replayed from the committed
+            # summary of separate rocprofv3 --pmc passes of this same command (profiles/*_pmc_traffic.md:
+            # FETCH_SIZE x2 correction + WRITE_SIZE); null when the run is not the profiled configuration
+            traffic = None
+            tname = TRAFFIC_FILES.get((args.workload, d, args.sampler, args.optimizer))
+            tfile = ROOT / "profiles" / (tname or "none")
+            if tfile.exists() and args.scale == 1.0 and not batched and not args.item_bias:
+                tj = json.loads(tfile.read_text())
+                if tj.get("triples_per_launch") == chunk:
+                    traffic = tj["traffic_bytes_per_launch"]
+                    if tname == "traffic_r06.json" and (e.lds_launches == 0 or steady is None):
+                        traffic = None  # (that file is the LDS-tier kernel on the trained state: not this run)
+            achieved = (bytes_per_triple * chunk) / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
+            out["early_state"] = {"value": early_value, "ms_per_step": early_ms, "kernel_ms_avg": early_kernel_ms,
+                                  "roofline_frac": ((bytes_per_triple * chunk) / (early_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                                                    if early_kernel_ms > 0 else None),
+                                  "note": "the same job on tables a few epochs from their random init (what r1-r5 reported as "
+                                          "`value`): the adaptive sampler's negatives are still uniform over the items there"}
+            out["timed_region"] = {"steps": args.steps, "warmup": args.warmup,
+                                   "ms_per_step_measured": dt_measured * 1e3 / args.steps,
+                                   "value_measured": region_value, "plans_inside": plans_timed,
+                                   "value_with_amortised_plan": region_value_with_plan,
+                                   "note": "K steps from random init, after --warmup + 1 steps"}
+            out["config"]["plan_epoch"] = {
+                "mode": ("per chunk, one step ahead, on the side stream behind the sort "
+                         "(bpr_plan_chunk): inside every step") if jit else
+                        ("bpr_plan_epoch per epoch, the next epoch's beside this epoch's launches on a "
+                         "third stream masked to the sorter's CUs") if plan_ahead else "bpr_plan_epoch per epoch",
+                "ms": plan_ms, "inside_timed_region": plans_timed,
+                "amortised_share_added_ms_per_step": max(0.0, args.steps / n_chunks - plans_timed) * plan_ms / args.steps,
+                "ms_per_step_measured": dt_measured * 1e3 / args.steps}
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": ("k_vstream" if batched else "k_stream") + "<G=%d,E=%d,%s>" % (32 if d <= 128 else 64, max(1, -(-d // (32 if d <= 128 else 64))), args.sampler.upper()),
                 "achieved": achieved,
@@ -953,53 +1071,53 @@ def main():
                 "bytes_per_triple": bytes_per_triple,
                 "kernel_ms_avg": kernel_ms,
                 "launches": launches,
-            },
-        }
-        if steady is not None:
-            out["steady_state"] = steady
-        if sus_epochs > 0:
-            out["sustained"] = {
-                "epochs": sus_epochs, "steps": sus_epochs * n_chunks,
-                "ms_per_step": sus_dt * 1e3 / (sus_epochs * n_chunks),
-                "value": sus_epochs * n_chunks * chunk * world / sus_dt,
-                "note": "whole epochs by wall clock, every bpr_plan_epoch in place (nothing modelled)"}
-        if not batched and kernel_ms > 0:
-            # what bounds k_stream is the L2 atomic units, not HBM: full-line fp32 atomic requests
-            lpt = 2 * lines_per_row + user_atomic_rows * lines_per_row
-            rate = lpt * chunk / (kernel_ms * 1e-3)
-            out["roofline_atomic"] = {
-                "bound": "l2-atomic-units", "unit": "line-atomics/s", "achieved": rate,
-                "peak": ATOMIC_LINES_PEAK, "frac": rate / ATOMIC_LINES_PEAK,
-                "line_atomics_per_triple": lpt,
-                "user_rows_cut_per_triple": user_atomic_rows,
-                "peak_source": "profiles/ubench_atomic_r02.txt (tools/ubench/atomic_bench.hip, uniform items)",
             }
-        if sync is not None:
-            # how the item reconciliation sits next to the step: the all-reduce runs on a side
-            # stream under the next step's kernels; it is hidden as long as it is shorter than a step
-            st = sync.timing_read()
-            st["sync_every_steps"] = args.sync_every
-            st["hidden_if_below_ms"] = dt * 1e3 / args.steps * args.sync_every
-            out["item_sync"] = st
-        if rccl_ranks_seen is not None:
-            out["rccl_ranks_seen"] = rccl_ranks_seen
-            out["dist_backend"] = dist.get_backend()
-            out["forced_distributed"] = forced
-        if not args.no_cpu_baseline:
-            smp = "uniform" if args.sampler == "given" else args.sampler
-            out["cpu_baseline"] = cpu_reference_op_sequence(data, d, reg, args.lr, args.adaptive_p,
-                                                            smp, args.seed, optimizer=args.optimizer,
-                                                            betas=tuple(args.betas), B=args.batch_size)
-            # the C restatement of the same path with OpenMP over triples beside it: sparse
-            # apply, no [B, I] weights — kinder to the CPU than the reference's own op sequence (plain SGD
-            # step whatever --optimizer: the C port has no sparse form of the stateful optimizers)
-            out["cpu_baseline_c_port"] = cpu_baseline(data, d, reg, args.lr, args.adaptive_p,
-                                                      args.cpu_seconds, args.seed, smp, B=args.batch_size)
+            if steady is not None:
+                out["steady_state"] = steady
+            if sus_epochs > 0:
+                out["sustained"] = {
+                    "epochs": sus_epochs, "steps": sus_epochs * n_chunks,
+                    "ms_per_step": sus_dt * 1e3 / (sus_epochs * n_chunks),
+                    "value": sus_epochs * n_chunks * chunk * world / sus_dt,
+                    "note": "whole epochs by wall clock, every bpr_plan_epoch in place (nothing modelled)"}
+            if not batched and kernel_ms > 0:
+                # what bounds k_stream is the L2 atomic units, not HBM: full-line fp32 atomic requests per triple of
+                # the chunk planned last — 2 item rows of d*4/128 lines each + one row per piece of every user a run
+                # boundary cuts (k_stream's rule)
+                lines_per_row = max(1, (d * 4) // 128)
+                L = e.stream_run_len()  # what the library's last launch used (it picks it from the occupancy)
+                planned_users = cbuf[(first + args.steps - 1) & 1][0] if jit else users_e[:chunk]
+                user_atomic_rows = cut_user_pieces(planned_users, L, not args.ungrouped) / chunk
+                lpt = 2 * lines_per_row + user_atomic_rows * lines_per_row
+                rate = lpt * chunk / (kernel_ms * 1e-3)
+                out["roofline_atomic"] = {
+                    "bound": "l2-atomic-units", "unit": "line-atomics/s", "achieved": rate,
+                    "peak": ATOMIC_LINES_PEAK, "frac": rate / ATOMIC_LINES_PEAK,
+                    "line_atomics_per_triple": lpt,
+                    "user_rows_cut_per_triple": user_atomic_rows,
+                    "peak_source": "profiles/ubench_atomic_r02.txt (tools/ubench/atomic_bench.hip, uniform items)",
+                }
+            if sync is not None:
+                # how the item reconciliation sits next to the step: the all-reduce runs on a side
+                # stream under the next step's kernels; it is hidden as long as it is shorter than a step
+                st = sync.timing_read()
+                st["sync_every_steps"] = args.sync_every
+                st["hidden_if_below_ms"] = dt * 1e3 / args.steps * args.sync_every
+                out["item_sync"] = st
+            if not args.no_cpu_baseline:
+                smp = "uniform" if args.sampler == "given" else args.sampler
+                out["cpu_baseline"] = cpu_reference_op_sequence(data, d, reg, args.lr, args.adaptive_p,
+                                                                smp, args.seed, optimizer=args.optimizer,
+                                                                betas=tuple(args.betas), B=args.batch_size)
+                # the C restatement of the same path with OpenMP over triples beside it: sparse
+                # apply, no [B, I] weights — kinder to the CPU than the reference's own op sequence (plain SGD
+                # step whatever --optimizer: the C port has no sparse form of the stateful optimizers)
+                out["cpu_baseline_c_port"] = cpu_baseline(data, d, reg, args.lr, args.adaptive_p,
+                                                          args.cpu_seconds, args.seed, smp, B=args.batch_size)
         print(json.dumps(out), flush=True)
     if world > 1 or forced:
         dist.barrier()
         dist.destroy_process_group()
-
 
 if __name__ == "__main__":
     main()

@@ -22,7 +22,7 @@ def _line(res):
 
 
 def test_bench_single_gpu_line():
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--scale", "0.05", "--steps", "6",
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--scale", "0.05", "--steps", "6",
                           "--warmup", "2", "--cpu-seconds", "1", "--steady-timed-epochs", "3"],
                          capture_output=True, text=True, timeout=900)
     j = _line(res)
@@ -41,13 +41,21 @@ def test_bench_single_gpu_line():
     assert st["epochs_trained_before"] >= 30 and st["steps"] == st["epochs"] * spe and st["value"] > 1e6
     assert st["first_epoch"]["epoch"] == st["epochs_trained_before"] + 1 and st["first_epoch"]["value"] > 1e6
     trained = (st["epochs_trained_before"] + st["epochs"]) * spe - ((6 + 2 + 1) // spe + 1 + sus["epochs"]) * spe
-    assert j["config"]["triples_counted_by_kernel"] == (6 + sus["steps"] + trained) * j["config"]["triples_per_step_per_gpu"]
+    tr = j["trained_region"]  # the headline's steps run after the steady epochs: its untimed lead-in and its K steps
+    assert j["config"]["triples_counted_by_kernel"] == (6 + sus["steps"] + trained + tr["untimed_steps_before"] + 6) * \
+        j["config"]["triples_per_step_per_gpu"]
     assert sus["epochs"] >= 3 and sus["value"] > 1e6 and 0 < r["read_only_frac"] < r["frac"]
-    # r6: the headline is the TRAINED state's whole-epoch wall-clock number, `steps` the steps behind it; the early
-    # state and the driver's K-step region ride along, nothing modelled in either
-    assert j["value"] == st["value"] and j["value_source"].startswith("steady state") and j["steps"] == st["steps"]
+    # the headline is the TRAINED state: the K = --steps steps of the job after --trained-epochs epochs, by wall clock,
+    # `steps` the steps behind it; the early state, the driver's K-step region from random init and the trained
+    # state's whole epochs (epochs 31.. as before) ride along under --full
+    assert st["epochs_trained_before"] == 30
+    assert j["value_source"].startswith("trained state") and j["steps"] == tr["steps"] == 6 and j["warmup"] == 2
+    assert tr["epochs_trained_before"] >= 80 and tr["first_step"] == tr["epochs_trained_before"] * spe + 1
+    assert tr["first_step"] >= (st["epochs_trained_before"] + st["epochs"]) * spe
+    assert abs(j["value"] - 6 * j["config"]["triples_per_step_per_gpu"] / (6 * j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    assert tr["plans_added"] == 6 / spe - 6 // spe and tr["ms_per_step_measured"] <= j["ms_per_step"]
     assert j["early_state"]["value"] == sus["value"] and 0 < j["early_state"]["roofline_frac"] < 1
-    assert r["kernel_ms_avg"] == st["kernel_ms_avg"] and j["ms_per_step"] == st["ms_per_step"]
+    assert r["kernel_ms_avg"] == st["kernel_ms_avg"] and st["ms_per_step"] > 0
     assert j["timed_region"]["steps"] == 6 and j["timed_region"]["value_measured"] > 1e6
     lds = j["config"]["hot_lds"]  # lr 0.001: inside the staleness budget -> asked for; a 5 % shard's launches may not fill the chip
     assert lds["rows_asked"] > 0 and lds["rows_in_lds_last_launch"] >= 0
@@ -60,7 +68,7 @@ def test_bench_single_gpu_line():
 def test_bench_workload_brings_its_own_hyperparameters():
     """--workload yelp = BASELINE configs[4]: Adam(0.1, 0.999), reg .0025/.0025/.00025, and a CPU baseline
     with the SAME optimizer (the committed cfg5 line carried an SGD baseline)."""
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "yelp", "--scale", "0.1",
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--workload", "yelp", "--scale", "0.1",
                           "--steps", "4", "--warmup", "2", "--cpu-seconds", "1", "--sustained-epochs", "1",
                           "--steady-epochs", "0"],
                          capture_output=True, text=True, timeout=900)
@@ -79,7 +87,7 @@ def test_bench_forced_distributed_one_rank_through_rccl(cadence):
     env = dict(os.environ)
     env.pop("BPR_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-           "--master-addr", "127.0.0.1", "--master-port", "29673", str(ROOT / "bench.py"), "--gpus", "1",
+           "--master-addr", "127.0.0.1", "--master-port", "29673", str(ROOT / "bench.py"), "--full", "--gpus", "1",
            "--force-dist", "--scale", "0.05", "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
            "--cadence", cadence, "--sustained-epochs", "1", "--steady-epochs", "0", "--split-cold-mb", "1"]
     j = _line(subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900))
@@ -89,7 +97,8 @@ def test_bench_forced_distributed_one_rank_through_rccl(cadence):
         assert j["config"]["refresh_schedule"]["sharded_over_ranks"] is True
     else:
         assert j["item_sync"]["hot"]["all_reduces"] >= 6 and j["config"]["refresh_schedule"]["lag"] == 1.0
-    steps = 6 + j["sustained"]["steps"]
+    tr = j["trained_region"]
+    steps = 6 + j["sustained"]["steps"] + tr["untimed_steps_before"] + tr["steps"]
     assert j["config"]["triples_counted_by_kernel"] == steps * j["config"]["triples_per_step_per_gpu"]
 
 
@@ -97,7 +106,7 @@ def test_bench_forced_distributed_one_rank_through_rccl(cadence):
 def test_bench_two_ranks_over_gloo(cadence):
     env = dict(os.environ, BPR_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", "29671", str(ROOT / "bench.py"), "--gpus", "2",
+           "--master-addr", "127.0.0.1", "--master-port", "29671", str(ROOT / "bench.py"), "--full", "--gpus", "2",
            "--scale", "0.05", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--cadence", cadence,
            "--sustained-epochs", "1", "--steady-epochs", "0"]
     j = _line(subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900))
@@ -109,5 +118,48 @@ def test_bench_two_ranks_over_gloo(cadence):
     else:  # lr 0.001: a full period per rank, hot tier exchanged after every launch
         assert "1 chunk(s)" in j["config"]["cadence"] and j["item_sync"]["hot"]["all_reduces"] >= 6
         assert j["config"]["refresh_schedule"]["lag"] == 1.0
-    steps = 6 + j["sustained"]["steps"]
+    tr = j["trained_region"]
+    steps = 6 + j["sustained"]["steps"] + tr["untimed_steps_before"] + tr["steps"]
     assert j["config"]["triples_counted_by_kernel"] == steps * j["config"]["triples_per_step_per_gpu"]
+
+
+def test_bench_plain_line_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run: set up, the job on to the trained state (--trained-epochs, the last --warmup steps just before),
+    exactly --steps timed steps, the line — none of --full's legs; --dump-outputs writes what the step function
+    computed from the seeded inputs (the tables after steps 0 and 1, step 1 on the timed schedule) as float .npy files
+    within 64 MB, and a second run with the same arguments writes them again within the spread measured below."""
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--scale", "0.05", "--steps", "5", "--warmup", "3",
+           "--trained-epochs", "4", "--dump-outputs", str(out)]
+    j = _line(subprocess.run(cmd, capture_output=True, text=True, timeout=600))
+    assert j["n_gpus"] == 1 and j["unit"] == "triples/s" and j["value"] > 1e6 and j["dtype"] == "f32"
+    assert j["higher_is_better"] is True and j["steps"] == 5 and j["warmup"] == 3 and j["ms_per_step"] > 0
+    spe, tps = j["config"]["steps_per_epoch"], j["config"]["triples_per_step_per_gpu"]
+    tr = j["trained_region"]
+    assert tr["epochs_trained_before"] == 4 and tr["first_step"] == tr["untimed_steps_before"]
+    assert tr["first_step"] == tr["epochs_trained_before"] * spe + 1 and tr["plans_inside"] == 5 // spe
+    assert tr["plans_added"] == 5 / spe - 5 // spe and tr["plan_ms"] > 0
+    assert abs(j["value"] - 5 * tps / (5 * j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    assert j["config"]["triples_counted_by_kernel"] == (tr["first_step"] + 5) * tps
+    assert not {"timed_region", "early_state", "sustained", "steady_state", "roofline", "roofline_atomic",
+                "cpu_baseline", "cpu_baseline_c_port", "item_sync"} & set(j)
+    assert "plan_epoch" not in j["config"]
+    import numpy as np
+
+    arrays = {p.stem: np.load(p) for p in out.iterdir()}
+    assert sorted(arrays) == j["outputs_dumped"]["arrays"] == ["item_emb", "scalars", "user_emb_sample"]
+    assert j["outputs_dumped"]["after_step"] == 1
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["item_emb"].shape[1] == 128 and np.isfinite(arrays["item_emb"]).all()
+    assert np.isfinite(arrays["user_emb_sample"]).all() and arrays["user_emb_sample"].shape[1] == 128
+    assert arrays["scalars"][3] == 2 * tps and 0 < arrays["scalars"][0] / arrays["scalars"][3] < 5
+    again = tmp_path / "again"
+    _line(subprocess.run(cmd[:-1] + [str(again)], capture_output=True, text=True, timeout=600))
+    # the kernel applies a launch's triples concurrently: a user row two workgroups share can be read before or after
+    # the other adds to it, and a few triples of the launch then draw another negative — about one SGD update on a few
+    # rows, 1e-5 .. 7e-5 of the table measured; the counters agree to float rounding
+    for name, a in arrays.items():
+        b = np.load(again / f"{name}.npy")
+        tol = 1e-6 if name == "scalars" else 5e-4
+        assert a.shape == b.shape and np.linalg.norm(a - b) <= tol * np.linalg.norm(a), name

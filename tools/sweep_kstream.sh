@@ -1,7 +1,7 @@
 #!/bin/bash
 # k_stream levers on one MI355X: heavy-user bitmaps, hot-block size / assignment, CU count.
 cd "$(dirname "$0")/.."
-run() { python bench.py --no-cpu-baseline --steps 94 --warmup 10 "$@" 2>&1 | python -c "
+run() { python bench.py --full --no-cpu-baseline --steps 94 --warmup 10 "$@" 2>&1 | python -c "
 import sys, json, os
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,8 +1,8 @@
 #!/bin/bash
-# Overlapped-refresh sweep on one MI355X: bench.py with every snapshot schedule / CU split.
+# Overlapped-refresh sweep on one MI355X: bench.py --full with every snapshot schedule / CU split.
 #   tools/sweep_overlap.sh > gpurun_out/sweep_overlap.txt
 cd "$(dirname "$0")/.."
-run() { python bench.py --no-cpu-baseline --steps 94 --warmup 10 "$@" 2>&1 | python -c "
+run() { python bench.py --full --no-cpu-baseline --steps 94 --warmup 10 "$@" 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

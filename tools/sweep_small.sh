@@ -2,7 +2,7 @@
 # Small STREAM launches (Netflix-sized periods, a rank's share of an ML-20M period at 8 ranks):
 # run length x the library's own choice (--run-len 0).  Output: profiles/r03_sweep_small.txt
 cd "$(dirname "$0")/.."
-run() { python bench.py --no-cpu-baseline --steps 94 --warmup 10 "$@" 2>&1 | python -c "
+run() { python bench.py --full --no-cpu-baseline --steps 94 --warmup 10 "$@" 2>&1 | python -c "
 import sys, json, os
 for l in sys.stdin:
     if l.startswith('{'):
