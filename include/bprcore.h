@@ -406,7 +406,9 @@ int bpr_set_hot_rows(bpr_ctx* ctx, int32_t hot_rows, int32_t replicas);
  * launches that do not fill the chip (tests).  Needs a hot block (bpr_plan_epoch / bpr_set_hot_items), d in
  * {32, 64, 128, 256, 512, 1024}, a snapshot sorted whole (the groups' seen structure is the LDS bitmap, or the staged
  * sorted list when the bitmaps would not leave 32 KB for rows: item tables past ~60 k items); otherwise the plain
- * kernel runs.  bpr_stream_lds_rows: LDS rows of the last STREAM launch (0 = the plain kernel ran). */
+ * kernel runs.  Under the hot tier (bpr_hot_tier_begin) only the first launch after a bpr_hot_exchange with cut = 1
+ * (or a bpr_sync_cut) takes it: a later one, whose block still holds the earlier launches' deltas, runs the plain kernel.
+ * bpr_stream_lds_rows: LDS rows of the last STREAM launch (0 = the plain kernel ran). */
 int bpr_set_hot_lds(bpr_ctx* ctx, int32_t rows, int32_t always);
 int bpr_stream_lds_rows(bpr_ctx* ctx);
 /* Test and measurement aids, per ctx (nothing in the library reads the environment per launch):

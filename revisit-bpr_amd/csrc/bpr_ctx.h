@@ -139,6 +139,10 @@ struct bpr_ctx {
   // launch and folds nothing — the hot deltas stay in the block until somebody needs the table
   // whole (hot_fold_impl: every other entry point, bpr_hot_fold)
   bool hot_unfolded = false;
+  // under the hot tier: the global block holds deltas of a launch since the last bpr_hot_exchange with cut = 1 /
+  // bpr_sync_cut.  The LDS-tier kernel reads a hot row of its LDS rows as Q + its own LDS delta, leaving those out:
+  // while this is set the plain kernel runs
+  bool hot_uncut = false;
   bool acut_call = false;
   int acut_parity = 0;
   hipEvent_t ev_launch = nullptr;

@@ -1558,6 +1558,7 @@ void hot_free(bpr_ctx* c) {
   c->hot_canon = c->hot_code = c->hot_by_rank = nullptr;
   c->hot_explicit = false;
   c->hot_tier = false;
+  c->hot_uncut = false;
   c->hot_delta_alloc = nullptr;
   c->hot_slot = c->hot_items = nullptr;
   c->hot_delta = nullptr;

@@ -399,10 +399,12 @@ static int launch_stream(bpr_ctx* c, StreamArgs a, int sampler, int64_t cap_grou
     if (c->tune_lds_block > 0) block_l = std::min<unsigned>(block_l, (unsigned)c->tune_lds_block);
     c->last_lds_rows = 0;
     // (not in the asynchronous-cut pipeline: there the deltas stay in the global block from launch to launch and a
-    // hot row's value is Q + that block — which the LDS-tier kernel, reading Q + its own LDS delta, leaves out)
+    // hot row's value is Q + that block — which the LDS-tier kernel, reading Q + its own LDS delta, leaves out;
+    // nor, for the same reason, under the hot tier while the block still holds an earlier launch's deltas that no
+    // bpr_hot_exchange with cut = 1 / bpr_sync_cut has taken out yet: c->hot_uncut)
     const bool acut_fold = acut && c->tune_acut_fold != 0;  // r6: the asynchronous cut with the fold kept on this stream
     if (c->tune_hot_lds > 0 && hot && c->hot_code != nullptr && c->d == G * E && a.snap_meta == nullptr &&
-        (!acut || acut_fold) && !c->hot_unfolded && (sampler == NEG_GIVEN || force != "csr")) {
+        (!acut || acut_fold) && !c->hot_unfolded && !c->hot_uncut && (sampler == NEG_GIVEN || force != "csr")) {
       if (cap_groups > 0 && cap_groups * G < block_l) block_l = (unsigned)(((cap_groups * G + 63) / 64) * 64);
       // the groups' seen structure beside the rows: the I-bit bitmaps while they leave 32 KB for rows, else (or
       // forced) the staged sorted lists (LIST_CAP entries per group: item tables past ~60 k items)
@@ -513,6 +515,7 @@ static int launch_stream(bpr_ctx* c, StreamArgs a, int sampler, int64_t cap_grou
       };
       if (!use_lds) pick(go);
     }
+    if (hot && c->hot_tier) c->hot_uncut = true;  // this launch's deltas stay in the block for bpr_hot_exchange
     if (a.bias != nullptr && !bias_in_epilogue)
       hipLaunchKernelGGL(k_bias_narrow, dim3((unsigned)((c->I + 255) / 256)), dim3(256), 0, c->stream,
                          c->bias_w, c->bias, (int32_t)c->I);
@@ -1419,6 +1422,7 @@ int bpr_hot_exchange(bpr_ctx* c, float* hot_base, float* tot, int32_t fold_prev,
   hipLaunchKernelGGL(k_hot_step, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0,
                      c->stream, a);
   BPR_HIP_CHECK(hipGetLastError());
+  if (cut) c->hot_uncut = false;  // the block is zero again: the next launch may take the LDS tier
   return BPR_OK;
 }
 
@@ -1461,6 +1465,7 @@ int bpr_sync_cut(bpr_ctx* c, float* hot_base, float* hot_tot, int32_t hot_fold_p
   hipExtLaunchKernelGGL(k_sync_cut, eg, dim3(256), 0, c->stream, nullptr, c->ev_keys, 0, a);
   BPR_HIP_CHECK(hipGetLastError());
   c->defer_pending = false;
+  c->hot_uncut = false;  // (the hot-tier step cut the block)
   c->keys_cut = true;   // the next bpr_adaptive_refresh_begin only queues the sort
   c->keys_event = true;
   return BPR_OK;

@@ -90,3 +90,50 @@ def run_launch(q0: np.ndarray, rows: np.ndarray, grads, grid: int, gpw: int, L: 
             alive.remove(b)
     q += delta.sum(0)  # the flush + the epilogue's fold
     return q, reads
+
+
+def two_half_stream(n: int, L: int, tail_percent: int, K: int, users_half: int, seed: int, own_seen: int = 8,
+                    neg_only: int = 2):
+    """A launch's triples for ONE wave of two groups (G = 32, `gpw_active` = 2, grid 1) whose groups never share a
+    row: wave-load k deals run 2k to group 0 and run 2k + 1 to group 1 (`deal` with grid 1, gpw 2), so the even runs
+    take only half A — users 1..users_half, items 1..K — and the odd runs only half B — users users_half + 1 ..
+    2 users_half, items K + 1 .. 2K.  Every user has seen ALL of the other half (and `own_seen` or fewer items of
+    its own), so a sampler can only pick a negative from the user's own half; the given negatives are drawn there
+    too.  Each half is a sequence of users with 1..12 consecutive triples (positives Zipf-skewed inside the half),
+    laid into its runs in order: users are cut by run boundaries.  The last `neg_only` items of each half are never
+    a positive (rows that only the negative's path reads and updates).  Run lengths and zones are those of `zones` /
+    `runs_of` with gpw = 2.  Returns dict(users, pos, neg, indptr, indices, half_of_user, half_of_item, runs, I, U)."""
+    rng = np.random.default_rng(seed)
+    U, I = 2 * users_half + 1, 2 * K + 1
+    half_u = np.full(U, -1)
+    half_u[1:users_half + 1], half_u[users_half + 1:] = 0, 1
+    half_i = np.full(I, -1)
+    half_i[1:K + 1], half_i[K + 1:] = 0, 1
+    items_of = [np.arange(1, K + 1, dtype=np.int32), np.arange(K + 1, 2 * K + 1, dtype=np.int32)]
+    rows = [np.zeros(0, np.int32)]
+    for u in range(1, U):
+        h = half_u[u]
+        own = rng.choice(items_of[h], size=int(rng.integers(0, own_seen + 1)), replace=False)
+        rows.append(np.sort(np.concatenate([own, items_of[1 - h]])).astype(np.int32))
+    indptr = np.zeros(U + 1, np.int64)
+    indptr[1:] = np.cumsum([len(r) for r in rows])
+    t1, t2 = zones(n, L, 2, tail_percent)
+    runs, _, _ = runs_of(n, L, t1, t2)
+    need = [sum(b - a for r, (a, b) in enumerate(runs) if r % 2 == h) for h in (0, 1)]
+    seqs = []
+    for h in (0, 1):
+        us = []
+        while len(us) < need[h]:
+            us += [int(rng.integers(1, users_half + 1)) + h * users_half] * int(rng.integers(1, 13))
+        us = np.asarray(us[:need[h]], np.int32)
+        pos = (items_of[h][0] + (rng.zipf(1.4, need[h]) - 1) % (K - neg_only)).astype(np.int32)
+        neg = rng.choice(items_of[h], size=need[h]).astype(np.int32)
+        seqs.append((us, pos, neg))
+    users, pos, neg = (np.zeros(n, np.int32) for _ in range(3))
+    at = [0, 0]
+    for r, (a, b) in enumerate(runs):
+        h, k = r % 2, at[r % 2]
+        users[a:b], pos[a:b], neg[a:b] = (s[k:k + b - a] for s in seqs[h])
+        at[h] += b - a
+    return dict(users=users, pos=pos, neg=neg, indptr=indptr, indices=np.concatenate(rows), half_of_user=half_u,
+                half_of_item=half_i, runs=runs, I=I, U=U)

@@ -31,13 +31,20 @@ def _problem(U, I, d, n, seed):
     return P, Q, indptr, np.concatenate(rows), users, pos
 
 
+DENSE_PROTOCOL = [(2, 1, 16, 64, 0), (3, 2, 40, 128, 0), (4, 3, 8, 256, 0), (2, 1, 16, 64, 9), (3, 2, 40, 128, 24),
+                  (4, 3, 12, 256, 12)]
+
+
 @pytest.mark.parametrize("fused", [False, True])
-@pytest.mark.parametrize("world,hot_split,H,d,lds", [(2, 1, 16, 64, 0), (3, 2, 40, 128, 0), (4, 3, 8, 256, 0),
-                                                     (2, 1, 16, 64, 9), (3, 2, 40, 128, 24), (4, 3, 12, 256, 12)])
-def test_two_tier_equals_the_dense_protocol(world, hot_split, H, d, fused, lds):
+@pytest.mark.parametrize("world,hot_split,H,d,lds,launches", [c + (m,) for m in (1, 2) for c in DENSE_PROTOCOL],
+                         ids=["-".join(map(str, c)) + ("" if m == 1 else "-x2") for m in (1, 2) for c in DENSE_PROTOCOL])
+def test_two_tier_equals_the_dense_protocol(world, hot_split, H, d, fused, lds, launches):
     """lds > 0 (r6): the launches run the LDS-tier kernel (`bpr_set_hot_lds`, forced for these small launches) — the
     `lds` hottest rows of the tier's H take a workgroup's updates in LDS and are flushed into the block the hot tier
     exchanges, the rest of the H go through the global block as before: the same protocol, the same tables.
+    launches = 2: every piece is two back-to-back launches with no exchange between them; the second reads the hot
+    rows as Q + a block that still holds the first one's deltas, so it must not run the LDS-tier kernel (which reads
+    its LDS rows as Q + its own LDS delta) — but the first launch after every exchange still does.
     fused: the last launch of a round leaves its epilogue to ONE pass — hot-tier step + cold step +
     the cut of the next snapshot's keys (bpr_sync_cut, ItemSync.step_cut) — instead of three kernels;
     same tables, and the snapshot sorted from that cut is the oracle's order of the table."""
@@ -66,10 +73,12 @@ def test_two_tier_equals_the_dense_protocol(world, hot_split, H, d, fused, lds):
         a, b = lo + n_round * p // hot_split, lo + n_round * (p + 1) // hot_split
         return a, b
 
-    def launch(e, r, k, p, cut=False):
+    def launch(e, r, k, p, cut=False):  # the piece as `launches` back-to-back launches (the last one cuts)
         a, b = piece(r, k, p)
-        e.train_stream(u_d[a:b], p_d[a:b], sampler=eng.NEG_UNIFORM, seed=7, offset=(r << 40) + a,
-                       max_inflight=1, cut=cut)
+        for m in range(launches):
+            x, y = a + (b - a) * m // launches, a + (b - a) * (m + 1) // launches
+            e.train_stream(u_d[x:y], p_d[x:y], sampler=eng.NEG_UNIFORM, seed=7, offset=(r << 40) + x,
+                           max_inflight=1, cut=cut and m == launches - 1)
 
     # ---- the product: ItemSync with the hot tier over LocalWorld
     lw = LocalWorld(world)
@@ -102,7 +111,8 @@ def test_two_tier_equals_the_dense_protocol(world, hot_split, H, d, fused, lds):
         syncs[r].hot_finish()
         syncs[r].finish()
     torch.cuda.synchronize()
-    assert all((e.lds_launches > 0) == (lds > 0) for e in es) and (lds == 0 or es[0].stream_lds_rows() == min(lds, H))
+    assert all((e.lds_launches > 0) == (lds > 0) for e in es)
+    assert lds == 0 or launches > 1 or es[0].stream_lds_rows() == min(lds, H)
 
     # ---- the protocol restated densely: plain engines, deltas as table differences
     ps = [engine() for _ in range(world)]
@@ -140,6 +150,9 @@ def test_two_tier_equals_the_dense_protocol(world, hot_split, H, d, fused, lds):
         err = np.abs(got - want).max()
         assert err <= 5e-6, (r, err)
         assert np.abs(es[r].P.cpu().numpy() - ps[r].P.cpu().numpy()).max() <= 5e-6
+    # every rank ran the LDS tier on the first launch after each exchange (and only there)
+    assert lds == 0 or all(e.lds_launches >= rounds * hot_split for e in es), [e.lds_launches for e in es]
+    assert lds == 0 or all(e.lds_launches == rounds * hot_split for e in es), [e.lds_launches for e in es]
     # the reconciled state: every replica is the same table, and the hot base is bit-identical
     for r in range(1, world):
         assert (es[r].Q - es[0].Q).abs().max().item() <= 2e-6

@@ -12,7 +12,8 @@ The HIP kernel is held to the oracle in tests/test_gpu_hotlds.py."""
 import numpy as np
 import pytest
 
-from hotlds_model import deal, run_launch, runs_of, zones
+import oracle
+from hotlds_model import deal, run_launch, runs_of, two_half_stream, zones
 
 
 @pytest.mark.parametrize("L", [1, 2, 3, 4, 5, 8, 12, 30])
@@ -83,3 +84,44 @@ def test_private_deltas_lose_nothing_and_one_workgroup_is_sequential():
     hot3[5] = True
     _, reads = run_launch(np.zeros(I), rows3, const, 16, gpw, L, 12, hot3, order="random", seed=2)
     assert reads.min() == 0.0 and reads.max() <= n / 16 + 2 * L * gpw  # each workgroup counts only its own ~n / 16
+
+
+@pytest.mark.parametrize("n,L,K", [(2000, 8, 40), (1100, 3, 40), (600, 1, 24)])
+def test_two_half_stream_keeps_the_two_groups_of_a_wave_apart(n, L, K):
+    """The stream tests/test_gpu_hotlds.py holds the two groups of one G = 32 wave to the sequential oracle with:
+    the runs a wave-load deals to its two groups share no user and no item row (positive or negative), every zone of
+    the launch is there, users are cut by run boundaries, and the samplers — uniform, and adaptive on a model that
+    moves — can only pick from the user's own half."""
+    s = two_half_stream(n, L, 12, K, 30, seed=n + L)
+    users, pos, neg, hu, hi, runs = s["users"], s["pos"], s["neg"], s["half_of_user"], s["half_of_item"], s["runs"]
+    t1, t2 = zones(n, L, 2, 12)
+    assert 0 < t1 < t2 < n and runs == runs_of(n, L, t1, t2)[0]
+    assert deal(len(runs), 1, 2) == [list(range(len(runs)))]  # one workgroup: wave-load k = runs 2k, 2k + 1
+    for k in range(0, len(runs), 2):
+        a = slice(*runs[k])
+        assert np.all(hu[users[a]] == 0) and np.all(hi[pos[a]] == 0) and np.all(hi[neg[a]] == 0)
+        if k + 1 < len(runs):
+            b = slice(*runs[k + 1])
+            assert np.all(hu[users[b]] == 1) and np.all(hi[pos[b]] == 1) and np.all(hi[neg[b]] == 1)
+            assert not set(users[a]) & set(users[b])
+            assert not (set(pos[a]) | set(neg[a])) & (set(pos[b]) | set(neg[b]))
+    assert users.min() >= 1 and pos.min() >= 1 and neg.min() >= 1
+    # users cut by run boundaries: a group's run starts with the user its previous run ended with
+    assert any(users[runs[r - 2][1] - 1] == users[runs[r][0]] for r in range(2, len(runs)))
+    indptr, indices, I = s["indptr"], s["indices"], s["I"]
+    for u in range(1, s["U"]):
+        seen = indices[indptr[u]:indptr[u + 1]]
+        assert np.array_equal(np.sort(seen[hi[seen] != hu[u]]), np.flatnonzero(hi == 1 - hu[u]))
+    uni = oracle.sample_uniform(indptr, indices, I, users, seed=11, offset=5)
+    assert np.array_equal(hi[uni], hu[users])
+    rng = np.random.default_rng(0)
+    d = 32
+    P = rng.normal(0, 0.1, (s["U"], d)).astype(np.float32)
+    Q = rng.normal(0, 0.1, (I, d)).astype(np.float32)
+    P[0], Q[0] = 0, 0
+    QT, sigma = oracle.adaptive_stats(Q)
+    picks = np.zeros(n, np.int32)
+    oracle.train_stream_seq(P, Q, None, users, pos, picks, oracle.NEG_ADAPTIVE, 0.05, (0.01, 0.02, 0.03),
+                            adaptive_p=0.05, sigma=sigma, order=oracle.adaptive_order(QT), indptr=indptr,
+                            indices=indices, seed=11)
+    assert picks.min() >= 1 and np.array_equal(hi[picks], hu[users])
