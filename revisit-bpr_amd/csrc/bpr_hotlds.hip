@@ -9,6 +9,7 @@
 
 #include "bpr_host.h"
 #include "bpr_stream.h"
+#include "bpr_stream_plan.h"
 
 namespace bpr {
 
@@ -28,19 +29,18 @@ static int allow_lds(K kernel, size_t shmem, size_t room) {
 // d == G * E (the FULL instantiations: every BASELINE shape)
 // (r6 also measured every user's seen bitmap in HBM instead of the per-group LDS bitmaps — twice the LDS rows, and
 // 612 against 832 M triples/s: the walk's lookups are LDS reads for a reason.  profiles/r06_hotlds.md.  Removed.)
-int launch_stream_lds(bpr_ctx* c, const StreamArgs& a, int sampler, int seen, unsigned grid, unsigned block, size_t shmem,
-                      hipEvent_t stop) {
+int launch_stream_lds(bpr_ctx* c, const StreamArgs& a, int sampler, const StreamPlan& p, hipEvent_t stop) {
   return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
     using T = decltype(tag);
     constexpr int G = T::G, E = T::E;
     auto go = [&](auto kernel) -> int {
-      if (int rc = allow_lds(kernel, shmem, lds_tier_room(G * E))) return rc;
-      hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), shmem, c->stream, nullptr, stop, 0, a);
+      if (int rc = allow_lds(kernel, p.shmem, lds_tier_room(G * E))) return rc;
+      hipExtLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.shmem, c->stream, nullptr, stop, 0, a);
       BPR_HIP_CHECK(hipGetLastError());
       return BPR_OK;
     };
     if (sampler == NEG_GIVEN) return go(k_stream<G, E, NEG_GIVEN, SEEN_CSR, true, false, true>);
-    if (seen == SEEN_LIST) {
+    if (p.seen == SEEN_LIST) {
       if (sampler == NEG_UNIFORM) return go(k_stream<G, E, NEG_UNIFORM, SEEN_LIST, true, false, true>);
       return go(k_stream<G, E, NEG_ADAPTIVE, SEEN_LIST, true, false, true>);
     }

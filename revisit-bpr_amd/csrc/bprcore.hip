@@ -10,9 +10,13 @@
 #include "bpr_ctx.h"
 #include "bpr_kernels.h"
 #include "bpr_host.h"
+#include "bpr_stream_plan.h"
 
 namespace bpr {
 static_assert(ORDER_PAD == BPR_ORDER_PAD, "walk vector width vs snapshot padding");
+static_assert(SEEN_CSR == STREAM_SEEN_CSR && SEEN_BITMAP == STREAM_SEEN_BITMAP && SEEN_LIST == STREAM_SEEN_LIST &&
+                  NEG_GIVEN == BPR_NEG_GIVEN,
+              "the launch plan names the kernels' template arguments");
 
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
@@ -30,10 +34,7 @@ static int max_blocks() {
   }();
   return v;
 }
-// STREAM grids: ~1.5 runs per group and the hardware dispatcher balances the rest (measured:
-// ML-20M 2,075 blocks 0.233 ms vs 0.24-0.25 for 1 or >= 2 runs per group; Yelp 10,922 blocks
-// 1.22 ms vs 1.31 ms with a persistent 2,048-block grid).  BPR_MAX_BLOCKS caps it (experiments).
-constexpr int64_t STREAM_MAX_GRID = 65536;  // also the size of the per-block partials scratch
+// STREAM grids (bpr_stream_plan.h): BPR_MAX_BLOCKS caps them (experiments).
 static int64_t stream_grid_cap() {
   static const bool forced = getenv("BPR_MAX_BLOCKS") != nullptr;
   return forced ? (int64_t)max_blocks() : STREAM_MAX_GRID;
@@ -59,6 +60,29 @@ int check_bound(const bpr_ctx* c, const char* who, bool whole_table) {
   return BPR_OK;
 }
 
+// k_stream_epilogue: the sum of a launch's loss partials (out != NULL), the fold of the hot block into Q and the
+// write-back of the wide item_bias, each if asked for.  `stop`: an event that rides on the kernel's own completion.
+static int stream_epilogue(bpr_ctx* c, const float* partials, int n_blocks, float* out, bool fold, bool with_bias,
+                           hipEvent_t stop) {
+  EpilogueArgs ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.partials = partials; ea.n_blocks = n_blocks; ea.out = out;
+  ea.Q = c->Q; ea.delta = c->hot_delta; ea.hot_items = c->hot_items;
+  ea.H = fold ? c->hot_H : 0; ea.R = c->hot_R; ea.d = c->d;
+  ea.fold_blocks = fold ? (int)std::min<int64_t>(((int64_t)c->hot_H * c->d + 255) / 256, 64) : 0;
+  if (with_bias) {
+    ea.bias_w = c->bias_w; ea.bias = c->bias; ea.I = (int32_t)c->I;
+    ea.bias_blocks = (int)std::min<int64_t>((c->I + 255) / 256, 256);
+  }
+  const dim3 grid(1 + ea.fold_blocks + ea.bias_blocks);
+  if (stop != nullptr)
+    hipExtLaunchKernelGGL(k_stream_epilogue, grid, dim3(256), 0, c->stream, nullptr, stop, 0, ea);
+  else
+    hipLaunchKernelGGL(k_stream_epilogue, grid, dim3(256), 0, c->stream, ea);
+  BPR_HIP_CHECK(hipGetLastError());
+  return BPR_OK;
+}
+
 // Fold the hot deltas an asynchronous cut left in the block (after that cut has read them).
 int hot_fold_impl(bpr_ctx* c) {
   if (!c->hot_unfolded) return BPR_OK;
@@ -67,13 +91,7 @@ int hot_fold_impl(bpr_ctx* c) {
   BPR_HIP_CHECK(hipSetDevice(c->device));
   if (c->ev_keys != nullptr) BPR_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_keys, 0));
   c->acut_pending = false;
-  EpilogueArgs ea;
-  memset(&ea, 0, sizeof(ea));
-  ea.Q = c->Q; ea.delta = c->hot_delta; ea.hot_items = c->hot_items;
-  ea.H = c->hot_H; ea.R = c->hot_R; ea.d = c->d;
-  ea.fold_blocks = (int)std::min<int64_t>(((int64_t)c->hot_H * c->d + 255) / 256, 64);
-  hipLaunchKernelGGL(k_stream_epilogue, dim3(1 + ea.fold_blocks), dim3(256), 0, c->stream, ea);
-  BPR_HIP_CHECK(hipGetLastError());
+  if (int rc = stream_epilogue(c, nullptr, 0, nullptr, true, false, nullptr)) return rc;
   return BPR_OK;  // (Q + delta is what it was: keys cut from it stay valid)
 }
 
@@ -273,9 +291,90 @@ static int stream_cus(bpr_ctx* c) {
   return c->stream_cus;
 }
 
-// STREAM: one group per run of a.run_len triples; max_inflight caps the number of groups (= triples
-// in flight).  A cap below one 256-thread block shrinks the block (whole waves), so
-// max_inflight = 1 at G = 64 really is ONE wave walking the stream sequentially.
+// ---- STREAM ------------------------------------------------------------------------------------
+using StreamKernelFn = void (*)(const StreamArgs);
+
+template <int G, int E, int SMP, int SN>
+static StreamKernelFn stream_kernel_of(bool full, bool part) {
+  if constexpr (SMP == NEG_ADAPTIVE)  // a partial snapshot: the instantiations whose walk can finish inside a bin
+    if (part) return full ? &k_stream<G, E, SMP, SN, true, true> : &k_stream<G, E, SMP, SN, false, true>;
+  return full ? &k_stream<G, E, SMP, SN, true> : &k_stream<G, E, SMP, SN, false>;
+}
+template <int G, int E, int SMP>
+static StreamKernelFn stream_kernel_seen(int seen, bool full, bool part) {
+  if (seen == SEEN_BITMAP) return stream_kernel_of<G, E, SMP, SEEN_BITMAP>(full, part);
+  if (seen == SEEN_LIST) return stream_kernel_of<G, E, SMP, SEEN_LIST>(full, part);
+  return stream_kernel_of<G, E, SMP, SEEN_CSR>(full, part);
+}
+// the plain k_stream instantiation for the ctx's shape (the LDSHOT ones: bpr_hotlds.hip)
+static int stream_kernel(const bpr_ctx* c, int sampler, int seen, bool part, StreamKernelFn* out) {
+  return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
+    using T = decltype(tag);
+    constexpr int G = T::G, E = T::E;
+    const bool full = c->d == G * E;
+    *out = sampler == NEG_GIVEN     ? stream_kernel_of<G, E, NEG_GIVEN, SEEN_CSR>(full, false)
+           : sampler == NEG_UNIFORM ? stream_kernel_seen<G, E, NEG_UNIFORM>(seen, full, false)
+                                    : stream_kernel_seen<G, E, NEG_ADAPTIVE>(seen, full, part);
+    return BPR_OK;
+  });
+}
+
+// blocks of the plan's plain kernel a CU holds at once (asked of the instantiation for a snapshot sorted whole),
+// cached per (d, sampler, seen, block, shmem) until the next bpr_set_tuning
+static int stream_occupancy(bpr_ctx* c, int sampler, const StreamPlan& p, int* occ) {
+  const auto key = std::make_tuple(c->d, sampler, p.seen, (int)p.block, (int64_t)p.shmem);
+  const auto it = c->stream_occ.find(key);
+  if (it != c->stream_occ.end()) {
+    *occ = it->second;
+    return BPR_OK;
+  }
+  StreamKernelFn k = nullptr;
+  if (int rc = stream_kernel(c, sampler, p.seen, false, &k)) return rc;
+  *occ = 0;
+  hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, k, (int)p.block, p.shmem);
+  if (*occ < 1) {
+    (void)hipGetLastError();
+    *occ = 1;
+  }
+  c->stream_occ[key] = *occ;
+  return BPR_OK;
+}
+
+// k_stream_epilogue_cut / k_sync_cut: the cut of the next snapshot's keys (Q + the hot block, transposed into
+// c->keysT) with the sum of the loss partials; fold: the hot block is folded into Q on the way; hot = false: the
+// keys are Q alone
+static EpilogueCutArgs cut_args(const bpr_ctx* c, const float* partials, int n_blocks, float* out, bool hot, bool fold,
+                                bool with_bias) {
+  EpilogueCutArgs ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.partials = partials; ea.n_blocks = n_blocks; ea.out = out;
+  ea.Q = c->Q; ea.T = c->keysT; ea.sig_acc = c->sig_acc; ea.d = c->d; ea.I = (int32_t)c->I;
+  if (hot) { ea.delta = c->hot_delta; ea.hot_slot = c->hot_slot; ea.H = c->hot_H; ea.R = c->hot_R; }
+  ea.fold = fold ? 1 : 0;
+  if (with_bias) { ea.bias_w = c->bias_w; ea.bias = c->bias; }
+  return ea;
+}
+static dim3 cut_grid(const bpr_ctx* c) { return dim3((unsigned)((c->I + 31) / 32), (unsigned)((c->d + 31) / 32) + 1u); }
+
+static int ensure_cut_events(bpr_ctx* c) {
+  if (c->ev_keys != nullptr) return BPR_OK;
+  BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_keys, hipEventDisableTiming));
+  BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_sorted, hipEventDisableTiming));
+  return BPR_OK;
+}
+
+// c->keysT holds the next snapshot's keys: the next bpr_adaptive_refresh_begin only queues the sort.  by_event:
+// ev_keys rides on the cut kernel; on_side: the cut runs on c->side — whoever sorts these keys on the launch stream
+// waits for ev_keys, and so does a launch outside the acut pipeline (the cut reads Q and that launch's partials)
+static void mark_keys_cut(bpr_ctx* c, bool by_event, bool on_side) {
+  c->keys_cut = true;
+  if (c->meta_front != nullptr && c->keysT == c->keys_front) c->keys_front_stale = true;
+  c->keys_event = by_event;
+  if (on_side) c->keys_on_side = c->acut_pending = true;
+}
+
+// One STREAM launch: one group per run of run_len triples; max_inflight (cap_groups) caps the number of groups
+// (= triples in flight).  The layout of the launch is decided in bpr_stream_plan.h.
 static int launch_stream(bpr_ctx* c, StreamArgs a, int sampler, int64_t cap_groups,
                          float* out_scalars, bool cut, bool acut = false) {
   if (a.n <= 0) return BPR_OK;
@@ -289,340 +388,141 @@ static int launch_stream(bpr_ctx* c, StreamArgs a, int sampler, int64_t cap_grou
     BPR_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_keys, 0));
     c->acut_pending = false;
   }
-  return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
-    using T = decltype(tag);
-    constexpr int G = T::G, E = T::E;
-    unsigned block = 256;
-    a.gpw_active = 64 / G;
-    if (cap_groups > 0 && cap_groups * G < 256) {
-      block = (unsigned)(((cap_groups * G + 63) / 64) * 64);
-      if (cap_groups < 64 / G) a.gpw_active = (int)cap_groups;  // one wave, one group at work
+  const bool hot = a.hot_slot != nullptr;
+  const bool part = a.snap_meta != nullptr;               // a partial snapshot in front
+  const bool acut_fold = acut && c->tune_acut_fold != 0;  // r6: the asynchronous cut with the fold kept on this stream
+
+  // ---- plan
+  StreamShape s = {};
+  s.n = a.n; s.I = c->I; s.d = c->d; s.G = c->G; s.E = c->E;
+  s.sampler = sampler; s.cap_groups = cap_groups; s.run_len = a.run_len; s.force_seen = c->tune_seen;
+  s.cus = stream_cus(c); s.grid_cap = stream_grid_cap();
+  s.hot = hot; s.hot_H = c->hot_H;
+  s.tune_hot_lds = c->tune_hot_lds; s.tune_hot_lds_force = c->tune_hot_lds_force != 0;
+  s.tune_lds_block = c->tune_lds_block; s.tune_lds_tail = c->tune_lds_tail;
+  // The LDS-tier kernel has FULL instantiations only, reads a snapshot sorted whole, and reads a hot row as Q + its
+  // own LDS delta — which leaves out what the global block holds.  So: not in r4's asynchronous-cut pipeline (the
+  // deltas stay in the block from launch to launch), nor under the hot tier while the block still holds an earlier
+  // launch's deltas that no bpr_hot_exchange with cut = 1 / bpr_sync_cut has taken out yet (c->hot_uncut).
+  s.lds_allowed = c->hot_code != nullptr && c->d == c->G * c->E && !part && (!acut || acut_fold) &&
+                  !c->hot_unfolded && !c->hot_uncut;
+  StreamPlan p = plan_stream_block(s);
+  int occ = 0;
+  if (int rc = stream_occupancy(c, sampler, p, &occ)) return rc;
+  p = plan_stream(s, p, occ);
+  const bool lds = p.kernel == STREAM_LDS;
+  a.run_len = p.run_len; a.bm_words = p.bm_words; a.gpw_active = p.gpw_active;
+  if (lds) {
+    a.lds_L = p.L; a.tail1 = p.tail1; a.tail2 = p.tail2;
+    a.hot_slot = c->hot_code;
+    a.hot_by_rank = c->hot_by_rank;
+    a.lds_only = c->hot_tier ? 0 : 1;
+  }
+  c->last_run_len = p.run_len;
+  c->last_lds_rows = p.L;
+  StreamKernelFn kernel = nullptr;
+  if (!lds)
+    if (int rc = stream_kernel(c, sampler, p.seen, part, &kernel)) return rc;
+
+  // ---- events, the partials' parity, the wide bias
+  if (cut || acut)
+    if (int rc = ensure_cut_events(c)) return rc;
+  if (acut) {
+    if (c->ev_launch == nullptr) BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_launch, hipEventDisableTiming));
+    if (c->side == nullptr) {
+      BPR_HIP_CHECK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+      c->side_owned = true;
     }
-    // "seen?" answers (bpr_device.h): the LDS bitmap (I bits per group) while a full 256-thread
-    // block's bitmaps fit 64 KiB (>= 2 blocks per CU at full width: I <= 65,536 for d <= 128,
-    // 131,072 above); larger item tables stage the user's sorted seen list in LDS instead
-    // (LIST_CAP entries per group, heavier users search the CSR in HBM).  bpr_set_tuning("seen", ...)
-    // forces a structure (tests, measurements); a forced bitmap shrinks the block to fit.
-    const int words = (int)(((c->I + 31) / 32 + 3) / 4 * 4);  // multiple of 4: 16-byte LDS wipes
-    static const char* const seen_names[] = {"", "csr", "bitmap", "list"};
-    const std::string force = seen_names[c->tune_seen];  // bpr_set_tuning (tests, measurements)
-    constexpr int LIST_CAP = 512;
-    int seen = SEEN_CSR;
-    int lds_words = 0;
-    if (sampler != NEG_GIVEN && force != "csr") {
-      const bool bm_fits = (size_t)(block / G) * words * sizeof(uint32_t) <= 64 * 1024;
-      if (force == "list" || (force != "bitmap" && !bm_fits)) {
-        seen = SEEN_LIST;
-        lds_words = LIST_CAP;
-      } else {
-        while (block > 64 && (size_t)(block / G) * words * sizeof(uint32_t) > 64 * 1024) block /= 2;
-        if ((size_t)(block / G) * words * sizeof(uint32_t) <= 64 * 1024) {
-          seen = SEEN_BITMAP;
-          lds_words = words;
-        } else {
-          block = 256;
-          seen = SEEN_LIST;
-          lds_words = LIST_CAP;
-        }
-      }
+    if (!acut_fold) {
+      // the launch after next reuses this launch's partials: two sets, used alternately
+      if (a.partials != nullptr) a.partials = c->dev_scalars + (size_t)c->acut_parity * 4 * (STREAM_MAX_GRID + 1);
+      c->acut_parity ^= 1;
     }
-    const size_t shmem = (size_t)(block / G) * (size_t)lds_words * sizeof(uint32_t);
-    const int64_t per_block = (int64_t)(block / 64) * a.gpw_active;
-    // groups the launch stream's CUs hold at once (occupancy of THIS instantiation x its CUs)
-    auto pick = [&](auto fn) {
-      using std::integral_constant;
-      auto with_seen = [&](auto smp) {
-        if (seen == SEEN_BITMAP) fn(smp, integral_constant<int, SEEN_BITMAP>{});
-        else if (seen == SEEN_LIST) fn(smp, integral_constant<int, SEEN_LIST>{});
-        else fn(smp, integral_constant<int, SEEN_CSR>{});
-      };
-      if (sampler == NEG_GIVEN)
-        fn(integral_constant<int, NEG_GIVEN>{}, integral_constant<int, SEEN_CSR>{});
-      else if (sampler == NEG_UNIFORM) with_seen(integral_constant<int, NEG_UNIFORM>{});
-      else with_seen(integral_constant<int, NEG_ADAPTIVE>{});
-    };
-    const auto occ_key = std::make_tuple(c->d, sampler, seen, (int)block, (int64_t)shmem);
-    auto occ_it = c->stream_occ.find(occ_key);
-    int occ = occ_it != c->stream_occ.end() ? occ_it->second : 0;
-    if (occ < 1) pick([&](auto smp, auto sn) {
-      constexpr int SMP = decltype(smp)::value, SN = decltype(sn)::value;
-      if (c->d == G * E)
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_stream<G, E, SMP, SN, true>, (int)block,
-                                                     shmem);
-      else
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_stream<G, E, SMP, SN, false>,
-                                                     (int)block, shmem);
-    });
-    if (occ < 1) {
-      (void)hipGetLastError();
-      occ = 1;
+  }
+  if (a.bias != nullptr) {  // the launch works on the bias with one item per line (bpr_kernels.h)
+    if (c->bias_w_rows != c->I) {
+      hipFree(c->bias_w);
+      c->bias_w = nullptr;
+      c->bias_w_rows = 0;
+      BPR_HIP_CHECK(hipMalloc(&c->bias_w, sizeof(float) * (size_t)c->I * BIAS_LINE));
+      c->bias_w_rows = c->I;
     }
-    c->stream_occ[occ_key] = occ;
-    const int64_t resident = (int64_t)occ * stream_cus(c) * per_block;
-    // run_len 0 = by launch size.  A launch whose runs of 8 overfill the chip takes runs of 8 and a
-    // grid of ~1.5 runs per group (the dispatcher balances the rest: r1 sweep).  A smaller launch
-    // (Netflix-sized periods, a rank's share of a period at 8 ranks) is over when its slowest group
-    // is: the shortest runs of >= 4 triples that still fit the chip in ONE residency, one run per
-    // group (profiles/r03_sweep_small.txt: 40,704 triples d=64 0.0433 -> 0.0393 ms, 24,896 triples
-    // d=128 0.0550 -> 0.0413 ms; runs shorter than 4 re-load the user row too often).
-    if (a.run_len <= 0) {
-      a.run_len = 8;
-      // (max_inflight > 0 — what StreamTrainer passes — only changes this when the cap binds: the
-      // residency bound is min(chip, cap))
-      const int64_t room = cap_groups > 0 ? std::min<int64_t>(resident, cap_groups) : resident;
-      if ((a.n + 7) / 8 < room) {
-        a.run_len = 4;
-        while (a.run_len < 8 && (a.n + a.run_len - 1) / a.run_len > room) ++a.run_len;
-      }
+    // (re)fill the wide table — unless it is known to equal the dense vector still: the epilogue of
+    // the previous launch wrote it back, and nobody has touched the vector since (every entry point
+    // of the library that writes it says so; writes of the caller's own: bpr_bias_written)
+    if (!(c->bias_track && c->bias_w_valid && c->bias_w_of == c->bias))
+      hipLaunchKernelGGL(k_bias_widen, dim3((unsigned)((c->I + 255) / 256)), dim3(256), 0, c->stream, c->bias,
+                         c->bias_w, (int32_t)c->I);
+    c->bias_w_valid = false;
+    c->bias_w_of = c->bias;
+    a.bias = c->bias_w;
+  }
+  // hot tier + cut: fold, reconciliation passes and snapshot cut are ONE pass, bpr_sync_cut, which the
+  // caller issues next; the launch leaves it its loss partials too
+  const bool defer = cut && hot && c->hot_tier;
+  // the write-back rides on the launch's own epilogue where there is one on this stream
+  const bool bias_in_epilogue = a.bias != nullptr && (!acut || acut_fold) && !defer;
+
+  // ---- launch
+  {
+    Timer tm(c, true);
+    (void)tm;
+    hipEvent_t stop = (acut && !acut_fold) ? c->ev_launch : nullptr;
+    if (lds) {
+      if (int rc = launch_stream_lds(c, a, sampler, p, stop)) return rc;
+    } else {
+      hipExtLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.shmem, c->stream, nullptr, stop, 0, a);
     }
-    c->last_run_len = a.run_len;
-    const int64_t n_runs = (a.n + a.run_len - 1) / a.run_len;
-    int64_t want = n_runs;
-    if (cap_groups > 0 && want > cap_groups) want = cap_groups;
-    int64_t nblk = (want + per_block - 1) / per_block;
-    if ((cap_groups <= 0 || n_runs <= cap_groups) && n_runs > resident)
-      nblk = (2 * nblk + 2) / 3;  // 1.5 runs per group
-    const int64_t max_blk = std::min<int64_t>(stream_grid_cap() * (256 / block), STREAM_MAX_GRID);
-    if (nblk > max_blk) nblk = max_blk;
-    unsigned grid = (unsigned)(nblk < 1 ? 1 : nblk);
-    a.bm_words = lds_words;
-    const bool hot = a.hot_slot != nullptr;
-    // ---- the LDS tier of the hot block (k_stream LDSHOT, bpr_hotlds.hip; bpr_set_tuning "hot_lds" = rows asked
-    // for): ONE workgroup per CU — up to 1,024 threads, its groups' seen bitmaps and an [L, d] fp32 delta block in
-    // LDS — persistent over its share of the runs.  Taken when the launch fills the chip at least twice (a smaller
-    // one is over when its slowest group is: the plain kernel's short runs win there), the shape has a FULL
-    // instantiation, the snapshot is sorted whole and the per-group bitmaps leave room for >= 8 rows.
-    bool use_lds = false;
-    int seen_l = SEEN_BITMAP;
-    size_t shmem_l = 0;
-    unsigned block_l = E <= 4 ? 1024 : 512;  // (E >= 8: 64+ registers of rows per lane — two waves per SIMD)
-    if (c->tune_lds_block > 0) block_l = std::min<unsigned>(block_l, (unsigned)c->tune_lds_block);
-    c->last_lds_rows = 0;
-    // (not in the asynchronous-cut pipeline: there the deltas stay in the global block from launch to launch and a
-    // hot row's value is Q + that block — which the LDS-tier kernel, reading Q + its own LDS delta, leaves out;
-    // nor, for the same reason, under the hot tier while the block still holds an earlier launch's deltas that no
-    // bpr_hot_exchange with cut = 1 / bpr_sync_cut has taken out yet: c->hot_uncut)
-    const bool acut_fold = acut && c->tune_acut_fold != 0;  // r6: the asynchronous cut with the fold kept on this stream
-    if (c->tune_hot_lds > 0 && hot && c->hot_code != nullptr && c->d == G * E && a.snap_meta == nullptr &&
-        (!acut || acut_fold) && !c->hot_unfolded && !c->hot_uncut && (sampler == NEG_GIVEN || force != "csr")) {
-      if (cap_groups > 0 && cap_groups * G < block_l) block_l = (unsigned)(((cap_groups * G + 63) / 64) * 64);
-      // the groups' seen structure beside the rows: the I-bit bitmaps while they leave 32 KB for rows, else (or
-      // forced) the staged sorted lists (LIST_CAP entries per group: item tables past ~60 k items)
-      size_t bm_bytes = sampler == NEG_GIVEN ? 0 : (size_t)(block_l / G) * words * sizeof(uint32_t);
-      if (sampler != NEG_GIVEN && (force == "list" || (force != "bitmap" && bm_bytes + 32 * 1024 > lds_tier_room(c->d)))) {
-        seen_l = SEEN_LIST;
-        bm_bytes = (size_t)(block_l / G) * LIST_CAP * sizeof(uint32_t);
-      }
-      const size_t row_bytes = sizeof(float) * (size_t)c->d + sizeof(uint32_t);
-      const size_t room = lds_tier_room(c->d);
-      int64_t L = bm_bytes < room ? (int64_t)((room - bm_bytes) / row_bytes) : 0;
-      L = std::min<int64_t>(L, std::min<int64_t>(c->tune_hot_lds, c->hot_H));
-      const int64_t per_block_l = (int64_t)(block_l / 64) * a.gpw_active;
-      const int64_t runs8 = (a.n + 7) / 8;
-      const bool fills = runs8 >= 2 * (int64_t)stream_cus(c) * per_block_l;
-      if (L >= 8 && (fills || c->tune_hot_lds_force)) {
-        use_lds = true;
-        if (c->run_len <= 0) a.run_len = 8;
-        c->last_run_len = a.run_len;
-        // the last tickets of a persistent workgroup are short runs (k_stream: tail1 / tail2), whole wave-loads each
-        // (zones hold whole wave-loads of runs: what is left of the chunk past the last whole wave-load of full
-        // runs always goes in the shortest runs)
-        const int64_t len2 = std::max(1, a.run_len / 2), len3 = std::max(1, a.run_len / 4);
-        const int64_t wl = (int64_t)a.run_len * a.gpw_active;  // triples of a wave-load of full runs
-        int64_t t1 = (int64_t)((double)a.n * (1.0 - c->tune_lds_tail / 100.0)) / wl * wl;
-        int64_t t2 = t1 + (int64_t)((double)(a.n - t1) * 0.6) / (len2 * a.gpw_active) * (len2 * a.gpw_active);
-        if (c->tune_lds_tail <= 0) t1 = t2 = a.n / wl * wl;
-        a.tail1 = (int32_t)t1;
-        a.tail2 = (int32_t)t2;
-        const int64_t n_runs_l = t1 / a.run_len + (t2 - t1) / len2 + (a.n - t2 + len3 - 1) / len3;
-        int64_t want_l = n_runs_l;
-        if (cap_groups > 0 && want_l > cap_groups) want_l = cap_groups;
-        grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(stream_cus(c), (want_l + per_block_l - 1) / per_block_l));
-        a.bm_words = sampler == NEG_GIVEN ? 0 : (seen_l == SEEN_LIST ? LIST_CAP : words);
-        a.lds_L = (int32_t)L;
-        a.hot_by_rank = c->hot_by_rank;
-        a.lds_only = c->hot_tier ? 0 : 1;
-        a.hot_slot = c->hot_code;
-        shmem_l = bm_bytes + (size_t)L * row_bytes;
-        c->last_lds_rows = (int)L;
-      }
-    }
-    // hot tier + cut: fold, reconciliation passes and snapshot cut are ONE pass, bpr_sync_cut, which the
-    // caller issues next; the launch leaves it its loss partials too
-    const bool defer = cut && hot && c->hot_tier;
-    if ((cut || acut) && c->ev_keys == nullptr) {
-      BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_keys, hipEventDisableTiming));
-      BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_sorted, hipEventDisableTiming));
-    }
-    if (acut) {
-      if (c->ev_launch == nullptr) BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_launch, hipEventDisableTiming));
-      if (c->side == nullptr) {
-        BPR_HIP_CHECK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-        c->side_owned = true;
-      }
-      if (!acut_fold) {
-        // the launch after next reuses this launch's partials: two sets, used alternately
-        if (a.partials != nullptr) a.partials = c->dev_scalars + (size_t)c->acut_parity * 4 * (STREAM_MAX_GRID + 1);
-        c->acut_parity ^= 1;
-      }
-    }
-    if (a.bias != nullptr) {  // the launch works on the bias with one item per line (bpr_kernels.h)
-      if (c->bias_w_rows != c->I) {
-        hipFree(c->bias_w);
-        c->bias_w = nullptr;
-        c->bias_w_rows = 0;
-        BPR_HIP_CHECK(hipMalloc(&c->bias_w, sizeof(float) * (size_t)c->I * BIAS_LINE));
-        c->bias_w_rows = c->I;
-      }
-      // (re)fill the wide table — unless it is known to equal the dense vector still: the epilogue of
-      // the previous launch wrote it back, and nobody has touched the vector since (every entry point
-      // of the library that writes it says so; writes of the caller's own: bpr_bias_written)
-      if (!(c->bias_track && c->bias_w_valid && c->bias_w_of == c->bias))
-        hipLaunchKernelGGL(k_bias_widen, dim3((unsigned)((c->I + 255) / 256)), dim3(256), 0, c->stream, c->bias,
-                           c->bias_w, (int32_t)c->I);
-      c->bias_w_valid = false;
-      c->bias_w_of = c->bias;
-      a.bias = c->bias_w;
-    }
-    // the write-back rides on the launch's own epilogue where there is one on this stream
-    const bool bias_in_epilogue = a.bias != nullptr && (!acut || acut_fold) && !(cut && hot && c->hot_tier);
-    {
-      Timer tm(c, true);
-      (void)tm;
-      hipEvent_t stop = (acut && !acut_fold) ? c->ev_launch : nullptr;
-      if (use_lds) {
-        if (int rc = launch_stream_lds(c, a, sampler, seen_l, grid, block_l, shmem_l, stop)) return rc;
-      }
-      auto go = [&](auto smp, auto sn) {
-        constexpr int SMP = decltype(smp)::value, SN = decltype(sn)::value;
-        if constexpr (SMP == NEG_ADAPTIVE) {
-          if (a.snap_meta != nullptr) {  // a partial snapshot: the instantiations whose walk can finish inside a bin
-            if (c->d == G * E)
-              hipExtLaunchKernelGGL((k_stream<G, E, SMP, SN, true, true>), dim3(grid), dim3(block), shmem,
-                                    c->stream, nullptr, stop, 0, a);
-            else
-              hipExtLaunchKernelGGL((k_stream<G, E, SMP, SN, false, true>), dim3(grid), dim3(block), shmem,
-                                    c->stream, nullptr, stop, 0, a);
-            return;
-          }
-        }
-        if (c->d == G * E)
-          hipExtLaunchKernelGGL((k_stream<G, E, SMP, SN, true>), dim3(grid), dim3(block), shmem,
-                                c->stream, nullptr, stop, 0, a);
-        else
-          hipExtLaunchKernelGGL((k_stream<G, E, SMP, SN, false>), dim3(grid), dim3(block), shmem,
-                                c->stream, nullptr, stop, 0, a);
-      };
-      if (!use_lds) pick(go);
-    }
-    if (hot && c->hot_tier) c->hot_uncut = true;  // this launch's deltas stay in the block for bpr_hot_exchange
-    if (a.bias != nullptr && !bias_in_epilogue)
-      hipLaunchKernelGGL(k_bias_narrow, dim3((unsigned)((c->I + 255) / 256)), dim3(256), 0, c->stream,
-                         c->bias_w, c->bias, (int32_t)c->I);
-    if (a.bias != nullptr) c->bias_w_valid = true;  // dense == wide again once the write-back has run
-    if (acut_fold) {
-      // r6: the launch stream keeps only what the NEXT launch needs — the fold of the hot block (+ loss statistics,
-      // + the item_bias write-back): k_stream_epilogue, a few microseconds — and the 2 x I x d x 4-byte transpose
-      // that only the sorter reads goes to the side stream, behind this epilogue and beside the next launch (it
-      // reads Q while that launch updates it: a snapshot cut during the launch instead of before it — a little
-      // FRESHER than lag 1, inside the same budget).  Unlike the r4 form below the block is folded after every
-      // launch, so the LDS-tier kernel (which reads a hot row as Q + its own LDS delta) stays valid.
-      const bool fold = hot && !c->hot_tier;
-      EpilogueArgs ea;
-      memset(&ea, 0, sizeof(ea));
-      ea.partials = a.partials; ea.n_blocks = (int)grid; ea.out = out_scalars;
-      ea.Q = c->Q; ea.delta = c->hot_delta; ea.hot_items = c->hot_items;
-      ea.H = fold ? c->hot_H : 0; ea.R = c->hot_R; ea.d = c->d;
-      ea.fold_blocks = fold ? (int)std::min<int64_t>(((int64_t)c->hot_H * c->d + 255) / 256, 64) : 0;
-      if (bias_in_epilogue) {
-        ea.bias_w = c->bias_w; ea.bias = c->bias; ea.I = (int32_t)c->I;
-        ea.bias_blocks = (int)std::min<int64_t>((c->I + 255) / 256, 256);
-      }
-      hipExtLaunchKernelGGL(k_stream_epilogue, dim3(1 + ea.fold_blocks + ea.bias_blocks), dim3(256), 0, c->stream, nullptr,
-                            c->ev_launch, 0, ea);
-      BPR_HIP_CHECK(hipGetLastError());
-      EpilogueCutArgs ec;
-      memset(&ec, 0, sizeof(ec));
-      ec.Q = c->Q; ec.T = c->keysT; ec.sig_acc = c->sig_acc; ec.d = c->d; ec.I = (int32_t)c->I;  // no hot block, no sums
-      dim3 eg((unsigned)((c->I + 31) / 32), (unsigned)((c->d + 31) / 32) + 1u);
-      BPR_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_launch, 0));
-      hipExtLaunchKernelGGL(k_stream_epilogue_cut, eg, dim3(256), 0, c->side, nullptr, c->ev_keys, 0, ec);
-      BPR_HIP_CHECK(hipGetLastError());
-      c->keys_cut = true;
-      if (c->meta_front != nullptr && c->keysT == c->keys_front) c->keys_front_stale = true;
-      c->keys_event = true;
-      c->keys_on_side = true;
-      c->acut_pending = true;  // (a launch outside the pipeline still waits for this cut: it reads Q)
-      return BPR_OK;
-    }
-    if (acut) {
-      // the cut of the next snapshot on the SIDE stream, behind this launch and beside the next
-      // one: read-only (keys = Q + hot deltas, nothing folded), it also sums the loss partials
-      EpilogueCutArgs ea;
-      memset(&ea, 0, sizeof(ea));
-      ea.partials = a.partials; ea.n_blocks = (int)grid; ea.out = out_scalars;
-      ea.Q = c->Q; ea.delta = c->hot_delta; ea.hot_slot = hot ? c->hot_slot : nullptr;
-      ea.T = c->keysT; ea.sig_acc = c->sig_acc;
-      ea.H = hot ? c->hot_H : 0; ea.R = c->hot_R; ea.d = c->d; ea.I = (int32_t)c->I;
-      ea.fold = 0;
-      dim3 eg((unsigned)((c->I + 31) / 32), (unsigned)((c->d + 31) / 32) + 1u);
-      BPR_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_launch, 0));
-      hipExtLaunchKernelGGL(k_stream_epilogue_cut, eg, dim3(256), 0, c->side, nullptr, c->ev_keys, 0, ea);
-      BPR_HIP_CHECK(hipGetLastError());
-      c->keys_cut = true;
-      if (c->meta_front != nullptr && c->keysT == c->keys_front) c->keys_front_stale = true;
-      c->keys_event = true;
-      c->keys_on_side = true;  // whoever sorts these keys on the launch stream waits for ev_keys
-      c->acut_pending = true;
-      c->hot_unfolded = hot;
-      return BPR_OK;
-    }
-    if (defer) {
-      c->defer_blocks = (int)grid;
-      c->defer_out = out_scalars;
-      c->defer_pending = true;
-    } else if (cut) {
-      // the epilogue also cuts the next snapshot's keys (k_stream_epilogue_cut) — into the key
-      // buffer the split refresh that may still be sorting does NOT read (bpr_ctx.h keysT_buf)
-      EpilogueCutArgs ea;
-      memset(&ea, 0, sizeof(ea));
-      ea.partials = a.partials; ea.n_blocks = (int)grid; ea.out = out_scalars;
-      ea.Q = c->Q; ea.delta = c->hot_delta; ea.hot_slot = hot ? c->hot_slot : nullptr;
-      ea.T = c->keysT; ea.sig_acc = c->sig_acc;
-      ea.H = hot ? c->hot_H : 0; ea.R = c->hot_R; ea.d = c->d; ea.I = (int32_t)c->I;
-      ea.fold = 1;
-      if (bias_in_epilogue) { ea.bias_w = c->bias_w; ea.bias = c->bias; }
-      dim3 eg((unsigned)((c->I + 31) / 32), (unsigned)((c->d + 31) / 32) + 1u);
-      // the split refresh's side stream waits for this cut: the event rides on the kernel's own
-      // completion signal (hipExtLaunchKernelGGL stop event) instead of a marker packet behind it
-      static const bool ride = getenv("BPR_CUT_EVENT") == nullptr || atoi(getenv("BPR_CUT_EVENT")) != 0;
-      if (ride) {
-        hipExtLaunchKernelGGL(k_stream_epilogue_cut, eg, dim3(256), 0, c->stream, nullptr, c->ev_keys,
-                              0, ea);
-      } else {
-        hipLaunchKernelGGL(k_stream_epilogue_cut, eg, dim3(256), 0, c->stream, ea);
-      }
-      c->keys_cut = true;
-      if (c->meta_front != nullptr && c->keysT == c->keys_front) c->keys_front_stale = true;
-      c->keys_event = ride;
-    } else if (out_scalars != nullptr || (hot && !c->hot_tier) || bias_in_epilogue) {
-      const bool fold = hot && !c->hot_tier;  // hot tier: the deltas stay for bpr_hot_exchange
-      EpilogueArgs ea;
-      memset(&ea, 0, sizeof(ea));
-      ea.partials = a.partials; ea.n_blocks = (int)grid; ea.out = out_scalars;
-      ea.Q = c->Q; ea.delta = c->hot_delta; ea.hot_items = c->hot_items;
-      ea.H = fold ? c->hot_H : 0; ea.R = c->hot_R; ea.d = c->d;
-      ea.fold_blocks =
-          fold ? (int)std::min<int64_t>(((int64_t)c->hot_H * c->d + 255) / 256, 64) : 0;
-      if (bias_in_epilogue) {
-        ea.bias_w = c->bias_w; ea.bias = c->bias; ea.I = (int32_t)c->I;
-        ea.bias_blocks = (int)std::min<int64_t>((c->I + 255) / 256, 256);
-      }
-      hipLaunchKernelGGL(k_stream_epilogue, dim3(1 + ea.fold_blocks + ea.bias_blocks), dim3(256), 0, c->stream, ea);
-    }
+  }
+  if (hot && c->hot_tier) c->hot_uncut = true;  // this launch's deltas stay in the block for bpr_hot_exchange
+  if (a.bias != nullptr && !bias_in_epilogue)
+    hipLaunchKernelGGL(k_bias_narrow, dim3((unsigned)((c->I + 255) / 256)), dim3(256), 0, c->stream,
+                       c->bias_w, c->bias, (int32_t)c->I);
+  if (a.bias != nullptr) c->bias_w_valid = true;  // dense == wide again once the write-back has run
+
+  // ---- epilogue
+  const bool fold = hot && !c->hot_tier;  // hot tier: the deltas stay for bpr_hot_exchange
+  if (acut) {
+    // the cut of the next snapshot on the SIDE stream, behind this launch and beside the next one.
+    // r6 (acut_fold): the launch stream keeps only what the NEXT launch needs — the fold of the hot block (+ loss
+    // statistics, + the item_bias write-back): k_stream_epilogue, a few microseconds — and the 2 x I x d x 4-byte
+    // transpose that only the sorter reads goes to the side stream, behind this epilogue (it reads Q while the next
+    // launch updates it: a snapshot cut during the launch instead of before it — a little FRESHER than lag 1, inside
+    // the same budget).  The block is folded after every launch, so the LDS-tier kernel stays valid.
+    // r4: read-only (keys = Q + hot deltas, nothing folded); the cut also sums the loss partials.
+    if (acut_fold)
+      if (int rc = stream_epilogue(c, a.partials, (int)p.grid, out_scalars, fold, bias_in_epilogue, c->ev_launch))
+        return rc;
+    const EpilogueCutArgs ec = acut_fold ? cut_args(c, nullptr, 0, nullptr, false, false, false)
+                                         : cut_args(c, a.partials, (int)p.grid, out_scalars, hot, false, false);
+    BPR_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_launch, 0));
+    hipExtLaunchKernelGGL(k_stream_epilogue_cut, cut_grid(c), dim3(256), 0, c->side, nullptr, c->ev_keys, 0, ec);
     BPR_HIP_CHECK(hipGetLastError());
+    mark_keys_cut(c, true, true);
+    if (!acut_fold) c->hot_unfolded = hot;
     return BPR_OK;
-  });
+  }
+  if (defer) {
+    c->defer_blocks = (int)p.grid;
+    c->defer_out = out_scalars;
+    c->defer_pending = true;
+  } else if (cut) {
+    // the epilogue also cuts the next snapshot's keys (k_stream_epilogue_cut) — into the key
+    // buffer the split refresh that may still be sorting does NOT read (bpr_ctx.h keysT_buf)
+    const EpilogueCutArgs ec = cut_args(c, a.partials, (int)p.grid, out_scalars, hot, true, bias_in_epilogue);
+    // the split refresh's side stream waits for this cut: the event rides on the kernel's own
+    // completion signal (hipExtLaunchKernelGGL stop event) instead of a marker packet behind it
+    static const bool ride = getenv("BPR_CUT_EVENT") == nullptr || atoi(getenv("BPR_CUT_EVENT")) != 0;
+    if (ride)
+      hipExtLaunchKernelGGL(k_stream_epilogue_cut, cut_grid(c), dim3(256), 0, c->stream, nullptr, c->ev_keys, 0, ec);
+    else
+      hipLaunchKernelGGL(k_stream_epilogue_cut, cut_grid(c), dim3(256), 0, c->stream, ec);
+    mark_keys_cut(c, ride, false);
+  } else if (out_scalars != nullptr || fold || bias_in_epilogue) {
+    return stream_epilogue(c, a.partials, (int)p.grid, out_scalars, fold, bias_in_epilogue, nullptr);
+  }
+  BPR_HIP_CHECK(hipGetLastError());
+  return BPR_OK;
 }
 
 float inv_log1mp(float p) { return (float)(1.0 / log1p(-(double)p)); }
@@ -1445,24 +1345,15 @@ int bpr_sync_cut(bpr_ctx* c, float* hot_base, float* hot_tot, int32_t hot_fold_p
     return fail(BPR_ERR_INVALID, "bpr_sync_cut: the hot tier is on: hot_base / hot_tot needed");
   BPR_HIP_CHECK(hipSetDevice(c->device));
   if (int rc = refresh_alloc(c)) return rc;
-  if (c->ev_keys == nullptr) {
-    BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_keys, hipEventDisableTiming));
-    BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_sorted, hipEventDisableTiming));
-  }
+  if (int rc = ensure_cut_events(c)) return rc;
   SyncCutArgs a;
   memset(&a, 0, sizeof(a));
-  const bool hot = c->hot_H > 0;
-  a.e.partials = c->dev_scalars;
-  a.e.n_blocks = c->defer_pending ? c->defer_blocks : 0;
-  a.e.out = c->defer_pending ? c->defer_out : nullptr;
-  a.e.Q = c->Q; a.e.delta = c->hot_delta; a.e.hot_slot = hot ? c->hot_slot : nullptr;
-  a.e.T = c->keysT; a.e.sig_acc = c->sig_acc;
-  a.e.H = hot ? c->hot_H : 0; a.e.R = c->hot_R; a.e.d = c->d; a.e.I = (int32_t)c->I;
+  a.e = cut_args(c, c->dev_scalars, c->defer_pending ? c->defer_blocks : 0, c->defer_pending ? c->defer_out : nullptr,
+                 c->hot_H > 0, false, false);
   a.canon = c->hot_canon; a.hb = hot_base; a.htot = hot_tot;
   a.base = cold_base; a.own = cold_own; a.tot = cold_tot; a.scale = scale;
   a.hot_tier = c->hot_tier ? 1 : 0; a.hot_fold_prev = hot_fold_prev != 0; a.cold_mode = cold_mode;
-  dim3 eg((unsigned)((c->I + 31) / 32), (unsigned)((c->d + 31) / 32) + 1u);
-  hipExtLaunchKernelGGL(k_sync_cut, eg, dim3(256), 0, c->stream, nullptr, c->ev_keys, 0, a);
+  hipExtLaunchKernelGGL(k_sync_cut, cut_grid(c), dim3(256), 0, c->stream, nullptr, c->ev_keys, 0, a);
   BPR_HIP_CHECK(hipGetLastError());
   c->defer_pending = false;
   c->hot_uncut = false;  // (the hot-tier step cut the block)
@@ -1506,6 +1397,22 @@ int bpr_bias_written(bpr_ctx* c) {
 
 int bpr_stream_run_len(bpr_ctx* c) {
   return c == nullptr ? 0 : c->last_run_len;
+}
+
+// Test hook, not API (tests/test_stream_plan_cpu.py sets its signature): the launch plan of a shape given as plain
+// integers — StreamShape's fields in order — and an occupancy; out = StreamPlan's fields in order.  Needs no GPU.
+int bpr_test_stream_plan(const int64_t* in, int32_t occ, int64_t* out) {
+  StreamShape s = {};
+  s.n = in[0]; s.I = in[1]; s.d = (int)in[2]; s.G = (int)in[3]; s.E = (int)in[4];
+  s.sampler = (int)in[5]; s.cap_groups = in[6]; s.run_len = (int)in[7]; s.force_seen = (int)in[8];
+  s.cus = (int)in[9]; s.grid_cap = in[10]; s.hot = in[11] != 0; s.hot_H = (int)in[12];
+  s.tune_hot_lds = (int)in[13]; s.tune_hot_lds_force = in[14] != 0;
+  s.tune_lds_block = (int)in[15]; s.tune_lds_tail = (int)in[16]; s.lds_allowed = in[17] != 0;
+  const StreamPlan p = plan_stream(s, plan_stream_block(s), occ);
+  const int64_t v[] = {p.kernel, p.seen, p.block, p.grid, (int64_t)p.shmem, p.bm_words, p.gpw_active, p.run_len,
+                       p.L, p.tail1, p.tail2};
+  memcpy(out, v, sizeof(v));
+  return BPR_OK;
 }
 
 int bpr_set_stream_opts(bpr_ctx* c, int32_t grouped_by_user, int32_t run_len) {

@@ -1,5 +1,5 @@
 """A numpy restatement of the LDS tier's ALGORITHM (k_stream<..., LDSHOT>, revisit-bpr_amd/csrc/bpr_stream.h, and
-its launcher in csrc/bprcore.hip) — test infrastructure:
+its launch plan in csrc/bpr_stream_plan.h) — test infrastructure:
 
   * the partition of a launch's triples into runs: [0, tail1) in runs of L, [tail1, tail2) in runs of L / 2,
     [tail2, n) in runs of L / 4, every zone whole wave-loads of runs (`zones`, `runs_of`: the host's and the
@@ -14,7 +14,8 @@ import numpy as np
 
 
 def zones(n: int, L: int, gpw: int, tail_percent: int):
-    """(tail1, tail2) as launch_stream computes them: zones hold whole wave-loads of runs; what is left of the chunk
+    """(tail1, tail2) as the launch plan computes them (csrc/bpr_stream_plan.h: plan_stream_lds; held to this
+    function by tests/test_stream_plan_cpu.py): zones hold whole wave-loads of runs; what is left of the chunk
     past the last whole wave-load of full runs always goes in the shortest runs."""
     len2 = max(1, L // 2)
     wl = L * gpw
