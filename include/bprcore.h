@@ -520,6 +520,31 @@ int bpr_set_sampler_iter(bpr_ctx* ctx, int64_t iteration);
 int bpr_auc_rows(const float* scores, int64_t n, int64_t I, const int64_t* pos_indptr, const int32_t* pos_items,
                  float* auc_out, void* hip_stream);
 
+/* ---- recommendation: the k best unseen items of a list of users (the reference ranks through full logits:
+ * example.py:195-230, the preds.jsonl / user-metrics.jsonl savers of experiments/options.py:319-351).  One fused
+ * kernel (csrc/bpr_topk.hip): s(u, i) = <P[u], Q[i]> (+ item_bias[i]) in fp32 over all I items, item 0 and the
+ * items of the user's seen row (the CSR of bpr_bind_seen_csr: int64 [U+1], int32 sorted per row; NULL = only item 0)
+ * left out, and no [n, I] buffer anywhere.  items_out / scores_out [n, k]: rows sorted by score descending, ties by
+ * ascending item id; a row with fewer than k eligible items ends in item -1 / score -inf.  The result is a pure
+ * function of the inputs: its bits do not depend on n, on a user's place in the list (which may repeat users) or on
+ * item_slices (0 = the library chooses; s > 1 cuts the item range over s workgroups per user tile, for lists too
+ * short to fill the chip, and needs the workspace).  d in [1, 1024], 1 <= k <= 128 (more: BPR_ERR_INVALID),
+ * item_slices in [0, 64], n < 2^31.  User ids are not checked.  Arguments are validated before the device is touched; n == 0
+ * is BPR_OK.  Context-free: runs on `hip_stream` of the current device. */
+/* bytes of device workspace bpr_topk_rows needs for this shape (0 with one slice; with s slices s * n * k * 8;
+ * item_slices 0: never less than for a smaller n) */
+int bpr_topk_workspace(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices, int64_t* bytes_host);
+/* the slice count a call of this shape runs with (item_slices 0: the library's choice; a given count is capped at
+ * the item tiles).  Passing it back as item_slices makes bpr_topk_workspace answer exactly that call's need — 0
+ * for one slice — instead of the never-shrinking bound of item_slices 0. */
+int bpr_topk_slices(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices, int32_t* slices_host);
+int bpr_topk_rows(const float* P, const float* Q, const float* item_bias /* or NULL */, int64_t I, int32_t d,
+                  const int32_t* users, int64_t n,
+                  const int64_t* seen_indptr /* or NULL */, const int32_t* seen_indices,
+                  int32_t k, int32_t item_slices /* 0 = choose */,
+                  void* workspace, int64_t workspace_bytes,
+                  int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
+
 /* ---- multi-GPU item-table reconciliation (no reference counterpart: the reference's DDP path is
  * never enabled by a config, experiments/launcher.py:35-73).  The all-reduce itself is RCCL via
  * torch.distributed; these two fused elementwise kernels bracket it (revisit_bpr/distributed.py).

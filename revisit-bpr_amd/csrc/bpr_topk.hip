@@ -1,0 +1,437 @@
+// bpr_topk.hip — fused scoring + top-K of libbprcore: the k best unseen items of a list of users, with no [n, I]
+// score matrix anywhere (bpr_topk_rows / bpr_topk_workspace).
+//
+// The reference ranks through full logits (example.py:195-230; the preds.jsonl / user-metrics.jsonl savers of
+// experiments/options.py:319-351), and revisit_bpr/evaluation.py restates that as P[users] Q^T, a seen scatter and
+// torch.topk per block of users: every score goes to HBM and back, and the selection costs three times the GEMM
+// (profiles/r06_eval_probe.txt).  Here a workgroup of 256 threads owns 64 users and streams the item table past them
+// 128 items x 32 features at a time through LDS into exact f32 MFMA accumulators (v_mfma_f32_32x32x2_f32: items on
+// the A side, users on the B side, so a lane's 16 results are 16 items of ONE user).  A score lives in a register
+// only long enough to be compared with its row's current k-th best.
+//
+// Selection.  Every row keeps in LDS a threshold tau = (score, id) — its k-th best at the last compaction — a
+// buffer of k + 128 candidates and a count.  After an item tile: (A) every lane counts its scores that beat tau;
+// (B) a row whose buffer could overflow is compacted by one wave to its k best, sorted (rank by counting: the
+// order "score descending, id ascending" is strict, so ranks are distinct), which tightens tau; (C) scores that
+// beat the current tau and are not in the user's sorted seen row (binary search, only for these few) are appended.
+// Measured (profiles/recommend_probe.txt): this form LOSES to the composition, 83.5 ms against 63.3 at ML-20M's
+// 138,493 users — (C) runs its searches candidate by candidate, each a chain of dependent CSR loads, 32 unrolled
+// blocks per lane behind each other.  Next step: test seen membership at compaction, for what was appended since
+// the last one, a lane's searches advancing together, so that the tile loop never touches the CSR.
+// After the first tiles almost nothing beats tau (~ k ln(I / k) candidates per row over the whole table).  The
+// appends race for buffer slots, but what a buffer holds as a SET does not depend on the race, and compaction
+// orders it by a strict total order: the output is a pure function of the inputs.
+//
+// Numerics.  An accumulator is carried through every feature chunk, so s(u, i) is one fmaf chain over the
+// features in a fixed order (per 8 features: 0, 4, 1, 5, 2, 6, 3, 7 — a lane half reads 4 consecutive features
+// with one 16-byte LDS read), the same wherever (u, i) falls in a tile, a slice or the user list; features past d
+// are staged as zeros on both sides.  The bias is one fp32 add after the chain.
+//
+// Item slices.  Few users (a serving call, a small evaluation) do not fill the chip: the item tiles are then cut
+// into slices, grid = user tiles x slices, each slice writes its sorted top-k to the workspace and k_topk_merge
+// merges a row's slices (each entry's rank = its index + binary searches in the other slices).  Layout and sizes:
+// bpr_topk_plan.h.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <string.h>
+
+#include <string>
+
+#include "bpr_host.h"
+#include "bpr_topk_plan.h"
+
+namespace bpr {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct Cand {
+  float s;
+  int32_t i;
+};
+
+struct TopkArgs {
+  const float* P;
+  const float* Q;
+  const float* bias;
+  int64_t I;
+  int d;
+  const int32_t* users;
+  int64_t n;
+  const int64_t* indptr;
+  const int32_t* indices;
+  int k, slices;
+  int64_t item_tiles;
+  float* out_scores;   // [n, slices, k]
+  int32_t* out_items;  // [n, slices, k]
+};
+
+// the order of the result: score descending, ties by ascending item id (never true for a NaN score)
+__device__ __forceinline__ bool better(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
+
+__device__ __forceinline__ bool in_sorted(const int32_t* __restrict__ v, int len, int item) {
+  int lo = 0, hi = len;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (v[mid] < item) lo = mid + 1; else hi = mid;
+  }
+  return lo < len && v[lo] == item;
+}
+
+// One wave: the c <= k + TOPK_TI <= 256 candidates of a row -> its min(c, k) best, sorted, in buf[0 ..); tau and
+// count follow.  Every lane of the wave calls it with the same arguments.
+__device__ __forceinline__ void compact_row(Cand* buf, int c, int k, int lane, Cand* tau, int* cnt) {
+  Cand e[4];
+  int rank[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int idx = lane + 64 * q;
+    e[q] = idx < c ? buf[idx] : Cand{0.0f, 0};
+    rank[q] = 0;
+  }
+  for (int j = 0; j < c; ++j) {
+    const Cand o = buf[j];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) rank[q] += better(o.s, o.i, e[q].s, e[q].i) ? 1 : 0;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (lane + 64 * q < c && rank[q] < k) {
+      buf[rank[q]] = e[q];
+      if (rank[q] == k - 1) *tau = e[q];
+    }
+  }
+  if (lane == 0) *cnt = c < k ? c : k;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <bool VEC>
+__device__ __forceinline__ float4 load4(const float* __restrict__ row, int kk, int d) {
+  if (VEC) return kk < d ? *reinterpret_cast<const float4*>(row + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 v;
+  v.x = kk + 0 < d ? row[kk + 0] : 0.f;
+  v.y = kk + 1 < d ? row[kk + 1] : 0.f;
+  v.z = kk + 2 < d ? row[kk + 2] : 0.f;
+  v.w = kk + 3 < d ? row[kk + 3] : 0.f;
+  return v;
+}
+
+// VEC: d % 4 == 0 and 16-byte aligned tables (16-byte global loads); else element loads.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_topk(const TopkArgs a) {
+  constexpr int TU = TOPK_TU, TI = TOPK_TI, KC = TOPK_KC, LD = TOPK_LD;
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int cap = a.k + TI;
+  float* const sQ = reinterpret_cast<float*>(smem);          // [TI][LD]
+  float* const sP = sQ + TI * LD;                            // [TU][LD]
+  Cand* const sBuf = reinterpret_cast<Cand*>(sP + TU * LD);  // [TU][cap]
+  Cand* const sTau = sBuf + TU * cap;                        // [TU]
+  int64_t* const sSeenLo = reinterpret_cast<int64_t*>(sTau + TU);
+  int* const sCnt = reinterpret_cast<int*>(sSeenLo + TU);
+  int* const sNeed = sCnt + TU;
+  int* const sUser = sNeed + TU;
+  int* const sSeenLen = sUser + TU;
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+  const int64_t u0 = (int64_t)blockIdx.x * TU;
+  const int slice = blockIdx.y;
+  const int64_t t0 = a.item_tiles * slice / a.slices, t1 = a.item_tiles * (slice + 1) / a.slices;
+
+  if (tid < TU) {
+    const int64_t row = u0 + tid;
+    const bool live = row < a.n;
+    const int u = live ? a.users[row] : -1;
+    int64_t lo = 0;
+    int len = 0;
+    if (live && a.indptr != nullptr && a.indices != nullptr) {
+      lo = a.indptr[u];
+      len = (int)(a.indptr[u + 1] - lo);
+    }
+    sUser[tid] = u;
+    sSeenLo[tid] = lo;
+    sSeenLen[tid] = len;
+    sCnt[tid] = 0;
+    sNeed[tid] = 0;
+    // nothing seen yet: everything beats tau; a row past n: nothing does
+    sTau[tid] = live ? Cand{-INFINITY, INT_MAX} : Cand{INFINITY, -1};
+  }
+  __syncthreads();
+
+  // the next chunk travels global -> registers while the current one is multiplied, then registers -> LDS
+  float4 qreg[4], preg[2];
+  auto fetch = [&](int64_t t, int c) {
+    const int kc = c * KC;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
+      const int64_t item = t * TI + row;
+      qreg[m] = item < a.I ? load4<VEC>(a.Q + item * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
+      const int u = sUser[row];
+      preg[m] = u >= 0 ? load4<VEC>(a.P + (int64_t)u * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  auto stash = [&]() {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int f = tid + 256 * m;
+      *reinterpret_cast<float4*>(sQ + (f >> 3) * LD + 4 * (f & 7)) = qreg[m];
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int f = tid + 256 * m;
+      *reinterpret_cast<float4*>(sP + (f >> 3) * LD + 4 * (f & 7)) = preg[m];
+    }
+  };
+
+  const int nch = (a.d + KC - 1) / KC;
+  const float* const qa = sQ + (32 * w + r) * LD + 4 * h;
+  const float* const pb0 = sP + r * LD + 4 * h;
+  const float* const pb1 = sP + (32 + r) * LD + 4 * h;
+  if (t0 < t1) fetch(t0, 0);
+  for (int64_t t = t0; t < t1; ++t) {
+    f32x16 acc0 = {0.f}, acc1 = {0.f};
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.f;
+    for (int c = 0; c < nch; ++c) {
+      __syncthreads();
+      stash();
+      __syncthreads();
+      if (c + 1 < nch) fetch(t, c + 1);
+      else if (t + 1 < t1) fetch(t + 1, 0);
+#pragma unroll
+      for (int blk = 0; blk < KC / 8; ++blk) {
+        const float4 a4 = *reinterpret_cast<const float4*>(qa + 8 * blk);
+        const float4 b0 = *reinterpret_cast<const float4*>(pb0 + 8 * blk);
+        const float4 b1 = *reinterpret_cast<const float4*>(pb1 + 8 * blk);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b0.x, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b1.x, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b0.y, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b1.y, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b0.z, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b1.z, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b0.w, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b1.w, acc1, 0, 0, 0);
+      }
+    }
+
+    // ---- epilogue of the item tile: register q of the lane is item ibase + (q & 3) + 8 (q >> 2) of users r, 32 + r
+    const int64_t ibase = t * TI + 32 * w + 4 * h;
+    const bool has_bias = a.bias != nullptr;
+    float bv[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int64_t item = ibase + (q & 3) + 8 * (q >> 2);
+      bv[q] = has_bias && item < a.I ? a.bias[item] : 0.f;
+    }
+    // (A) how many scores beat the row's threshold
+    unsigned m0 = 0, m1 = 0;
+    {
+      const Cand tau0 = sTau[r], tau1 = sTau[32 + r];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int64_t item = ibase + (q & 3) + 8 * (q >> 2);
+        const bool ok = item > 0 && item < a.I;
+        const float s0 = has_bias ? acc0[q] + bv[q] : acc0[q];
+        const float s1 = has_bias ? acc1[q] + bv[q] : acc1[q];
+        if (ok && better(s0, (int)item, tau0.s, tau0.i)) m0 |= 1u << q;
+        if (ok && better(s1, (int)item, tau1.s, tau1.i)) m1 |= 1u << q;
+      }
+      if (m0) atomicAdd(&sNeed[r], __popc(m0));
+      if (m1) atomicAdd(&sNeed[32 + r], __popc(m1));
+    }
+    __syncthreads();
+    // (B) rows whose buffer might not take them all: down to the k best (then count <= k, and a tile adds <= TI)
+    for (int row = w; row < TU; row += 4) {
+      const int c = min(sCnt[row], cap);
+      if (c + sNeed[row] > cap) compact_row(sBuf + row * cap, c, a.k, lane, &sTau[row], &sCnt[row]);
+    }
+    __syncthreads();
+    // (C) append what still beats the threshold and the user has not seen
+    if (tid < TU) sNeed[tid] = 0;
+    if (m0 | m1) {
+      const Cand tau0 = sTau[r], tau1 = sTau[32 + r];
+      const int32_t* const seen0 = a.indices + sSeenLo[r];
+      const int32_t* const seen1 = a.indices + sSeenLo[32 + r];
+      const int len0 = sSeenLen[r], len1 = sSeenLen[32 + r];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int item = (int)(ibase + (q & 3) + 8 * (q >> 2));
+        if ((m0 >> q) & 1u) {
+          const float s0 = has_bias ? acc0[q] + bv[q] : acc0[q];
+          if (better(s0, item, tau0.s, tau0.i) && !in_sorted(seen0, len0, item)) {
+            const int pos = atomicAdd(&sCnt[r], 1);
+            if (pos < cap) sBuf[r * cap + pos] = Cand{s0, item};
+          }
+        }
+        if ((m1 >> q) & 1u) {
+          const float s1 = has_bias ? acc1[q] + bv[q] : acc1[q];
+          if (better(s1, item, tau1.s, tau1.i) && !in_sorted(seen1, len1, item)) {
+            const int pos = atomicAdd(&sCnt[32 + r], 1);
+            if (pos < cap) sBuf[(32 + r) * cap + pos] = Cand{s1, item};
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- the slice's result: every row sorted, padded with (-inf, -1)
+  for (int row = w; row < TU; row += 4) {
+    if (u0 + row >= a.n) break;
+    const int c = min(sCnt[row], cap);
+    Cand* const buf = sBuf + row * cap;
+    if (c > 0) compact_row(buf, c, a.k, lane, &sTau[row], &sCnt[row]);
+    const int have = c < a.k ? c : a.k;
+    const int64_t out = ((u0 + row) * a.slices + slice) * a.k;
+    for (int j = lane; j < a.k; j += 64) {
+      const Cand e = j < have ? buf[j] : Cand{-INFINITY, -1};
+      a.out_scores[out + j] = e.s;
+      a.out_items[out + j] = e.i;
+    }
+  }
+}
+
+// One workgroup per row: S sorted lists of k (padded with id -1 at the end) -> the k best, sorted.
+__global__ __launch_bounds__(256) void k_topk_merge(const float* __restrict__ ps, const int32_t* __restrict__ pi, int S,
+                                                    int k, float* __restrict__ out_s, int32_t* __restrict__ out_i) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  Cand* const sE = reinterpret_cast<Cand*>(smem);  // [S][k]
+  int* const sLen = reinterpret_cast<int*>(sE + S * k);
+  const int tid = threadIdx.x;
+  const int64_t row = blockIdx.x;
+  const int64_t base = row * S * k;
+  if (tid < S) sLen[tid] = 0;
+  __syncthreads();
+  for (int e = tid; e < S * k; e += 256) {
+    const Cand c = {ps[base + e], pi[base + e]};
+    sE[e] = c;
+    if (c.i >= 0) atomicAdd(&sLen[e / k], 1);
+  }
+  __syncthreads();
+  int total = 0;
+  for (int s = 0; s < S; ++s) total += sLen[s];
+  for (int e = tid; e < S * k; e += 256) {
+    const int s = e / k, j = e - s * k;
+    if (j >= sLen[s]) continue;
+    const Cand c = sE[e];
+    int rank = j;
+    for (int b = 0; b < S && rank < k; ++b) {
+      if (b == s) continue;
+      const Cand* const L = sE + b * k;
+      int lo = 0, hi = sLen[b];  // entries of list b that come before c
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (better(L[mid].s, L[mid].i, c.s, c.i)) lo = mid + 1; else hi = mid;
+      }
+      rank += lo;
+    }
+    if (rank < k) {
+      out_s[row * k + rank] = c.s;
+      out_i[row * k + rank] = c.i;
+    }
+  }
+  for (int j = (total < k ? total : k) + tid; j < k; j += 256) {
+    out_s[row * k + j] = -INFINITY;
+    out_i[row * k + j] = -1;
+  }
+}
+
+static int check_shape(const char* who, int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices) {
+  if (n < 0 || I < 1 || I >= ((int64_t)1 << 31))
+    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be >= 0 and I in [1, 2^31)");
+  if (d < 1 || d > 1024) return fail(BPR_ERR_INVALID, std::string(who) + ": d must be in [1, 1024]");
+  if (k < 1 || k > TOPK_MAX)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": k must be in [1, " + std::to_string(TOPK_MAX) + "]");
+  if (item_slices < 0 || item_slices > TOPK_MAX_SLICES)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": item_slices must be 0 (choose) or in [1, " +
+                                     std::to_string(TOPK_MAX_SLICES) + "]");
+  if (n > 0x7FFFFFFF)  // (the merge kernel's grid is one workgroup per row)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be below 2^31");
+  return BPR_OK;
+}
+
+}  // namespace bpr
+
+extern "C" int bpr_topk_workspace(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices,
+                                  int64_t* bytes_host) {
+  using namespace bpr;
+  if (bytes_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_topk_workspace: bytes_host is NULL");
+  if (int rc = check_shape("bpr_topk_workspace", n, I, d, k, item_slices)) return rc;
+  *bytes_host = topk_workspace_bytes(n, I, k, item_slices);
+  return BPR_OK;
+}
+
+extern "C" int bpr_topk_slices(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices, int32_t* slices_host) {
+  using namespace bpr;
+  if (slices_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_topk_slices: slices_host is NULL");
+  if (int rc = check_shape("bpr_topk_slices", n, I, d, k, item_slices)) return rc;
+  *slices_host = plan_topk(n, I, k, item_slices).slices;
+  return BPR_OK;
+}
+
+extern "C" int bpr_topk_rows(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                             const int32_t* users, int64_t n, const int64_t* seen_indptr, const int32_t* seen_indices,
+                             int32_t k, int32_t item_slices, void* workspace, int64_t workspace_bytes,
+                             int32_t* items_out, float* scores_out, void* hip_stream) {
+  using namespace bpr;
+  if (int rc = check_shape("bpr_topk_rows", n, I, d, k, item_slices)) return rc;
+  if (n > 0 && (!P || !Q || !users || !items_out || !scores_out))
+    return fail(BPR_ERR_INVALID, "bpr_topk_rows: P, Q, users, items_out or scores_out is NULL");
+  const TopkPlan p = plan_topk(n, I, k, item_slices);
+  if (p.ws_bytes > 0 && (workspace == nullptr || workspace_bytes < p.ws_bytes))
+    return fail(BPR_ERR_INVALID, "bpr_topk_rows: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                     std::to_string(p.ws_bytes) + " needed (bpr_topk_workspace)");
+  if (n == 0) return BPR_OK;
+
+  hipStream_t stream = (hipStream_t)hip_stream;
+  TopkArgs a = {};
+  a.P = P; a.Q = Q; a.bias = item_bias; a.I = I; a.d = d; a.users = users; a.n = n;
+  a.indptr = seen_indptr; a.indices = seen_indices; a.k = k; a.slices = p.slices; a.item_tiles = p.item_tiles;
+  float* part_s = reinterpret_cast<float*>(workspace);
+  int32_t* part_i = reinterpret_cast<int32_t*>(part_s + (p.slices > 1 ? n * (int64_t)p.slices * k : 0));
+  a.out_scores = p.slices > 1 ? part_s : scores_out;
+  a.out_items = p.slices > 1 ? part_i : items_out;
+  const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Q)) % 16 == 0;
+  const dim3 grid((unsigned)p.user_tiles, (unsigned)p.slices);
+  // one workgroup may ask for most of a CU's LDS: past 64 KiB that is a per-function attribute (set on every
+  // call: the process may hold several devices, and the call costs nothing next to a launch)
+  const int lds_max = (int)topk_lds_bytes(TOPK_MAX);
+  if (vec) {
+    BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    hipLaunchKernelGGL(k_topk<true>, grid, dim3(256), p.lds, stream, a);
+  } else {
+    BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk<false>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    hipLaunchKernelGGL(k_topk<false>, grid, dim3(256), p.lds, stream, a);
+  }
+  BPR_HIP_CHECK(hipGetLastError());
+  if (p.slices > 1) {
+    hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)n), dim3(256), p.merge_lds, stream, part_s, part_i, p.slices, k,
+                       scores_out, items_out);
+    BPR_HIP_CHECK(hipGetLastError());
+  }
+  return BPR_OK;
+}
+
+// Test hook, not API (tests/test_recommend_cpu.py sets its signature): the plan of a shape.  in = {n, I, d, k,
+// item_slices, cus}; out = {slices, user_tiles, item_tiles, tile_users, tile_items, cap, lds, merge_lds, ws_bytes};
+// bounds[0 .. slices] = first item of each slice, then I.  Needs no GPU.
+extern "C" int bpr_test_topk_plan(const int64_t* in, int64_t* out, int64_t* bounds) {
+  using namespace bpr;
+  if (int rc = check_shape("bpr_test_topk_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3], (int32_t)in[4]))
+    return rc;
+  const TopkPlan p = plan_topk(in[0], in[1], (int)in[3], (int)in[4], in[5] > 0 ? (int)in[5] : TOPK_CUS);
+  const int64_t v[] = {p.slices, p.user_tiles, p.item_tiles, TOPK_TU, TOPK_TI, p.cap, (int64_t)p.lds,
+                       (int64_t)p.merge_lds, p.ws_bytes};
+  memcpy(out, v, sizeof(v));
+  for (int s = 0; s <= p.slices; ++s) bounds[s] = std::min<int64_t>(topk_slice_tile(p, s) * TOPK_TI, in[1]);
+  return BPR_OK;
+}

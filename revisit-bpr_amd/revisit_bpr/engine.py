@@ -211,6 +211,18 @@ class Engine:
         self._keep["csr"] = (indptr, indices)
         native.check(self._lib.bpr_bind_seen_csr(self._ctx, indptr.data_ptr(), indices.data_ptr()))
 
+    def recommend(self, users: torch.Tensor, k: int, exclude_seen: bool = True, *, item_slices: int = 0):
+        """The `k` best items of every user of `users` from the bound tables (`bpr_topk_rows`, see
+        revisit_bpr/recommend.py): (items [n, k] int32, scores [n, k] float32), sorted by score descending, ties
+        by ascending id, padded with -1 / -inf.  Item 0 is never returned; exclude_seen also leaves out the user's
+        row of the CSR given to `bind_seen_csr` (none bound: nothing else to leave out).  Rows an Adam / momentum
+        / RMSprop optimizer has not replayed yet are scored as they stand: `flush_lazy()` first
+        (`Model.recommend` does)."""
+        from revisit_bpr.recommend import recommend
+
+        indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
+        return recommend(self.P, self.Q, self.item_bias, users, k, indptr, indices, item_slices=item_slices)
+
     def bind_item_weights(self, weights: Optional[torch.Tensor]) -> None:
         """Item weights of the uniform sampler (count_i ** neg_sampling_alpha of the reference's
         BPRExperiment): [I] non-negative; None = uniform."""

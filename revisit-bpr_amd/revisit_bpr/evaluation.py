@@ -133,3 +133,48 @@ def evaluate_topk(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: torch
     if auc_metric is not None:
         out["auc"] = float(auc_metric.get_metric()) if lib is None else float(auc_sum / max(E, 1))
     return out
+
+
+@torch.no_grad()
+def evaluate_fused(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: torch.Tensor,
+                   eval_indptr: torch.Tensor, eval_items: torch.Tensor, seen_indptr: torch.Tensor,
+                   seen_indices: torch.Tensor, ks=(5, 10, 20, 50, 100)) -> dict:
+    """The NDCG / Recall / Precision keys of `evaluate_topk` from ONE `recommend` call with k = max(ks)
+    (revisit_bpr/recommend.py: scores, seen mask and selection in one kernel, no [n, I] logits and no [n, I]
+    target matrix).  Relevance of a returned item = membership in the user's row of the eval CSR, looked up
+    through a sorted key list (row * I + item).  No AUC: that needs every score (`evaluate_topk(auc=True)`).
+    max(ks) is at most 128, the kernel's largest k (larger cutoffs: `evaluate_topk`).
+    k-th best ties are broken by ascending item id here and by torch.topk's choice there."""
+    from revisit_bpr.recommend import recommend
+
+    dev = P.device
+    I = Q.shape[0]
+    E = eval_users.numel()
+    kmax = min(max(ks), I)
+    if kmax > 128:
+        raise ValueError(f"evaluate_fused ranks at most 128 items per user (max(ks) = {max(ks)}); "
+                         "evaluate_topk has no such limit")
+    items, _ = recommend(P, Q, item_bias, eval_users, kmax, seen_indptr, seen_indices)  # [E, kmax]
+    t_cnt = (eval_indptr[1:E + 1] - eval_indptr[:E])
+    rows = torch.arange(E, device=dev)
+    keys = torch.repeat_interleave(rows, t_cnt) * I + eval_items[int(eval_indptr[0]):int(eval_indptr[E])].long()
+    keys = torch.sort(keys).values
+    probe = rows.unsqueeze(1) * I + items.long()  # (padding, item -1: the key of item I - 1 of the row before, or -1)
+    if keys.numel() > 0:
+        at = torch.searchsorted(keys, probe).clamp(max=keys.numel() - 1)
+        rel = ((keys[at] == probe) & (items >= 0)).float()
+    else:
+        rel = torch.zeros_like(probe, dtype=torch.float)
+    disc = 1.0 / torch.log2(torch.arange(kmax, dtype=torch.float, device=dev) + 2.0)
+    n_pos = t_cnt.float()
+    gains = rel * disc
+    out = {}
+    for k in ks:
+        kk = min(k, I)
+        hits = rel[:, :kk].sum(1)
+        ideal = torch.cumsum(disc, 0)[(n_pos.clamp(max=kk).long() - 1).clamp(min=0)]
+        ideal = torch.where(n_pos > 0, ideal, torch.zeros_like(ideal))
+        out[f"ndcg@{k}"] = float(torch.nan_to_num(gains[:, :kk].sum(1) / ideal).double().sum() / max(E, 1))
+        out[f"recall@{k}"] = float(torch.nan_to_num(hits / n_pos).double().sum() / max(E, 1))
+        out[f"precision@{k}"] = float((hits / kk).double().sum() / max(E, 1))
+    return out

@@ -458,6 +458,24 @@ class Model(torch.nn.Module):
         self.sync()
         return super().state_dict(*args, **kwargs)
 
+    def recommend(self, users: torch.Tensor, k: int, exclude_seen: bool = True):
+        """The `k` best items of every user of `users` (device tensor of user ids): (items [n, k] int32,
+        scores [n, k] float32) from the engine's fused top-K kernel (revisit_bpr/recommend.py), sorted by score
+        descending, ties by ascending id, padded with -1 / -inf; item 0 and — exclude_seen — the items of the
+        CSR given to `bind_seen_csr` are never returned.  Rows behind the optimizer step are replayed first
+        (`sync()`).  A user bias is added to the returned scores (it does not change a user's order).  Only
+        the MF scorer has a fused form."""
+        if not self._fusable():
+            raise NotImplementedError("recommend needs the MF logits model in float32: other scorers have no "
+                                      "fused top-K kernel")
+        eng = self.engine()
+        self.sync()
+        items, scores = eng.recommend(users, k, exclude_seen=exclude_seen)
+        ub = self.logits_model._user_bias
+        if ub is not None:
+            scores += ub.detach()[users.reshape(-1).long()].unsqueeze(1)
+        return items, scores
+
     # ---- forward ----------------------------------------------------------------------------
     def forward(self, inputs: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:
         # inputs.user [B]; inputs.item, inputs.neg [B, n]
