@@ -141,8 +141,25 @@ int bpr_sample_uniform(bpr_ctx* ctx, const int32_t* users, int64_t B, uint64_t s
 int bpr_bind_item_weights(bpr_ctx* ctx, const float* accept, const int32_t* alias);
 
 /* AdaptiveSampler.update_stats (neg_samplers.py:126-132): snapshot the item table as per-factor
- * descending item orders (private scratch, d*I int32) and sigma_f = unbiased std over rows 1.. */
+ * descending item orders (private scratch, d*I int32) and sigma_f = unbiased std over rows 1..
+ * The sorter goes by the table's size (csrc/bpr_refresh_plan.h): 2,048 .. 20,480 items the binned sort with one
+ * workgroup per column, up to 131,071 items with several (16-bit ids to 65,535 items, 17-bit ids beyond — Yelp's
+ * 92,090), otherwise and below the in-LDS radix sort (+ merge of 2 | 4 runs up to 147,456 items), beyond that a
+ * device-wide radix sort; every route gives the same stable order, bit for bit. */
 int bpr_adaptive_refresh(bpr_ctx* ctx);
+/* What the last COMPLETED refresh ran (bpr_adaptive_refresh, _commit or _publish; a split refresh still pending
+ * does not count) — a diagnostic, never on the training path: it waits for the ctx stream.  info_host: HOST
+ * array of BPR_REFRESH_INFO_LEN int32, every entry -1 before the first refresh:
+ *   [0] route  0 in-LDS radix sort (+ merge of sub runs) | 1 binned sort, one workgroup per column |
+ *              2 split binned sort, G workgroups per column | 3 partial order | 4 device-wide radix sort
+ *   [1] G      workgroups per column of the binned sort (0 when the route is not a binned one)
+ *   [2] ITEMS  keys per thread of the route's kernel instantiation (SITEMS of the split binned sort; 0 for route 4)
+ *   [3] sub    workgroups per column of the radix sort: the route's own, or the fallback's behind route 2
+ *   [4] columns the split binned sort handed to its fallback (route 2; -1 on every other route, whose kernels
+ *       leave no trace of it)
+ *   [5..7] reserved, -1 */
+#define BPR_REFRESH_INFO_LEN 8
+int bpr_adaptive_refresh_info(bpr_ctx* ctx, int32_t* info_host);
 /* The same refresh in two halves, so that the sort does not stand between two STREAM launches
  * (the reference sorts inline: update_stats is called from sample(), neg_samplers.py:122-123).
  * _begin: the snapshot's keys are cut from the item table NOW, in the ctx stream's order — that
@@ -421,9 +438,12 @@ int bpr_stream_lds_rows(bpr_ctx* ctx);
  *   "partial_snapshot" 0 / 1, "partial_target" 1..1024: bpr_adaptive_snapshot_partial above;
  *   "binned_sort" 1 (default) / 0: tables of 2,048 .. 20,480 items have their snapshot columns ordered by
  *               k_sort_binned (equi-depth bins + ranking inside the bin: the same stable descending order as
- *               the radix sort, bit for bit, in ~0.4 of its time; up to 65,535 items with several workgroups per
- *               column, k_sort_binned_split) / by the radix sort (a test and measurement aid);
- *   "binned_split" 0 (default: workgroups per column by table size) / 1..4 (tests force the split kernel on small tables);
+ *               the radix sort, bit for bit, in ~0.4 of its time; up to 131,071 items with several workgroups per
+ *               column, k_sort_binned_split and, from 65,536 items on, its 17-bit-id form) / by the radix sort (a
+ *               test and measurement aid);
+ *   "binned_split" 0 (default: workgroups per column by table size) / 1..16 (tests and measurements force the split
+ *               kernel: on small tables, or with more workgroups than the table needs; a value too small for the
+ *               table is raised until a stretch fits a workgroup);
  *   "lds_block" 0 (default: 1,024 threads for d <= 256 at 32-lane groups, 512 above) / a multiple of 64: threads per
  *               workgroup of the LDS-tier kernel (bpr_set_hot_lds) — fewer groups leave more LDS for hot rows;
  *   "plan_input_sorted" 0 (default) / 1: a PROMISE that the users_in handed to bpr_plan_epoch are sorted by user id (the

@@ -80,7 +80,7 @@ struct bpr_ctx {
   // walk's in-bin finish reads it: it outlives the snapshot, see refresh_impl); *_front = the pair the
   // samplers read (meta_front NULL = sorted whole)
   int tune_binned = 1;        // 1: columns of 2,048 .. 20,480 keys are ordered by k_sort_binned (0: the radix sort)
-  int tune_binned_split = 0;  // 0: workgroups per column of the binned sort by shape; 1..4: forced (tests)
+  int tune_binned_split = 0;  // 0: workgroups per column of the binned sort by shape; 1..16: forced (tests)
   int tune_partial = 0;       // 1: the split refresh sorts partially when the shape allows
   int partial_target = 640;   // keys aimed at per exact end (at most 1,024 fit: k_sort_partial's PART_CAP)
   int32_t* snap_meta[2] = {nullptr, nullptr};
@@ -95,6 +95,11 @@ struct bpr_ctx {
   bool side_owned = false;
   hipEvent_t ev_keys = nullptr, ev_sorted = nullptr;
   bool refresh_pending = false;
+  // what the refresh into either snapshot buffer ran (refresh_impl), and the buffer of the last completed one
+  // (bpr_adaptive_refresh_info; -1: none yet)
+  struct RefreshInfo { int route = -1, g = 0, items = 0, sub = 0, f_lo = 0, nf = 0; };
+  RefreshInfo refresh_info[2];
+  int refresh_done = -1;
   bool part_pending = false;  // bpr_adaptive_refresh_part: this rank's columns are sorted, publish pending
   // bpr_train_stream_cut: the launch's epilogue already cut the next snapshot's keys (keysT); the
   // next bpr_adaptive_refresh_begin only queues the sort.  Any call that moves the item table
@@ -200,6 +205,7 @@ int refresh_impl(bpr_ctx* c, bool split, int f_lo, int f_hi);  // bpr_refresh.hi
 int refresh_publish_impl(bpr_ctx* c);       // bpr_refresh.hip
 int refresh_alloc(bpr_ctx* c);             // bpr_refresh.hip: the snapshot buffers (idempotent)
 int refresh_commit_impl(bpr_ctx* c);        // bpr_refresh.hip
+int refresh_info_impl(bpr_ctx* c, int32_t* info_host);  // bpr_refresh.hip
 int snapshot_complete_impl(bpr_ctx* c);     // bpr_refresh.hip: a partial front snapshot is sorted whole, in place
 void refresh_free(bpr_ctx* c);      // bpr_refresh.hip
 void side_free(bpr_ctx* c);         // bpr_refresh.hip

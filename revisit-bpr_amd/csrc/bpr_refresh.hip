@@ -23,6 +23,7 @@
 #include <stdio.h>
 
 #include "bpr_ctx.h"
+#include "bpr_refresh_plan.h"
 
 namespace bpr {
 
@@ -914,7 +915,8 @@ __global__ __launch_bounds__(1024) void k_sort_binned(const float* __restrict__ 
 
 // ---------------------------------------------------------------------------------------------
 // The binned sort with G workgroups per column: workgroup g orders the g-th stretch of RANKS.  For columns
-// that do not fit one workgroup's LDS (20,480 < I <= 65,535: MSD's 41,141).  Every workgroup reads the whole column
+// that do not fit one workgroup's LDS (20,480 < I <= 131,071: MSD's 41,141, Yelp's 92,090).  Every workgroup reads
+// the whole column
 // (L2-resident) and builds the same two-level histogram; nothing is kept in registers between passes — a
 // count pass and a fill pass over the keys replace the remembered ordinals — and only the keys whose bin falls
 // into its stretch are staged: about I / G, at most 1,024 x SITEMS.  The first-of-bin flags live in a bit
@@ -922,19 +924,39 @@ __global__ __launch_bounds__(1024) void k_sort_binned(const float* __restrict__ 
 // of the order starts at (keys above its stretch).  A workgroup that cannot (a bin over BIN_MAX keys, a
 // stretch over its capacity, no spread) flags the column — meta[2f] = -1, cleared to 0 before the launch — and
 // the radix path behind it redoes exactly the flagged columns.
+// WIDE (k_sort_binned_split<SPLIT_WIDE + SITEMS>, 65,536 <= I <= 131,071): the 17th bit of an id lives in a bit array beside the
+// 16-bit ids, one bit per staged entry — 2.5 KB at CAP = 20,480, so the staged stretch stays as long as with 16-bit
+// ids and G as small (32-bit ids would fit 12,288 entries at most: G = 8 instead of 5 for 92,090 items, and every
+// workgroup repeats the five passes over the column).  A window's high bits are one 64-bit word, as its flags are;
+// the ids in final order take theirs from s_hist's first words, which the fill pass leaves dead.
 // ---------------------------------------------------------------------------------------------
 constexpr int SPLIT_BINS = 4096;  // bins per workgroup
 
-template <int SITEMS>
+template <int CAP>
+__device__ __forceinline__ uint32_t* split_high_bits() {  // (only a WIDE instantiation owns the array)
+  __shared__ uint32_t s_hi[CAP / 32];
+  return s_hi;
+}
+
+// SITEMS_W = SITEMS, or SPLIT_WIDE + SITEMS for the WIDE form (one kernel template, and the 16-bit instantiations
+// keep their symbols and their code)
+constexpr int SPLIT_WIDE = 64;
+
+template <int SITEMS_W>
 __global__ __launch_bounds__(1024) void k_sort_binned_split(const float* __restrict__ T, int64_t I,
                                                             int32_t* __restrict__ order,
                                                             float* __restrict__ sigma,
                                                             int32_t* __restrict__ meta) {
+  constexpr bool WIDE = SITEMS_W >= SPLIT_WIDE;
+  constexpr int SITEMS = WIDE ? SITEMS_W - SPLIT_WIDE : SITEMS_W;
   constexpr int CAP = 1024 * SITEMS;
   constexpr int BPT = SPLIT_BINS / 1024;
+  static_assert(CAP / 32 <= SPLIT_BINS, "the final order's high id bits live in s_hist");
   __shared__ uint32_t s_key[CAP + 4];
-  __shared__ uint16_t s_id[CAP];
+  __shared__ uint16_t s_id[CAP];             // the ids' low 16 bits
   __shared__ uint32_t s_flag[CAP / 32 + 4];  // first-of-bin bits
+  uint32_t* s_hi = nullptr;                  // bit 16 of the staged ids
+  if constexpr (WIDE) s_hi = split_high_bits<CAP>();
   __shared__ uint32_t s_hist[SPLIT_BINS];
   __shared__ uint32_t s_coarse[1024], s_cum[1024], s_fine[1024], s_fcum[1024];
   __shared__ uint32_t s_scan[16];
@@ -981,6 +1003,8 @@ __global__ __launch_bounds__(1024) void k_sort_binned_split(const float* __restr
   });
   for (int k = t; k < SPLIT_BINS; k += 1024) s_hist[k] = 0u;
   for (int k = t; k < CAP / 32 + 4; k += 1024) s_flag[k] = 0u;
+  if constexpr (WIDE)
+    for (int k = t; k < CAP / 32; k += 1024) s_hi[k] = 0u;
   s_coarse[t] = 0u;
   s_fine[t] = 0u;
   if (t == 0) {
@@ -1113,9 +1137,13 @@ __global__ __launch_bounds__(1024) void k_sort_binned_split(const float* __restr
       const int at = (int)atomicAdd(&s_hist[b], 1u);
       s_key[at] = orderable_desc(v);
       s_id[at] = (uint16_t)l;
+      if constexpr (WIDE)
+        if (l >> 16) atomicOr(&s_hi[at >> 5], 1u << (at & 31));
     }
   });
   __syncthreads();
+  if constexpr (WIDE)  // (the bins' cursors are dead: the high id bits of the final order; the barrier behind the
+    for (int k = t; k < CAP / 32; k += 1024) s_hist[k] = 0u;  // ranking orders this before the scatter)
   // ---- ranking inside the bins, position by position (k_sort_binned's; a window's flags are one 64-bit word)
   const int lane = t & 63;
   uint32_t out[SITEMS];  // final position << 16 | id ... two words past 32,767 items: position and id apart
@@ -1136,7 +1164,11 @@ __global__ __launch_bounds__(1024) void k_sort_binned_split(const float* __restr
       int hi = after ? base + __ffsll(after) - 1 : bn ? base + 63 + __ffsll(bn) : n_mine;
       if (!valid) lo = hi = 0;
       const uint32_t u = valid ? s_key[p] : 0u;
-      const int id = valid ? (int)s_id[p] : 0;
+      int id = valid ? (int)s_id[p] : 0;
+      if constexpr (WIDE) {
+        const unsigned long long bh = (unsigned long long)s_hi[w] | ((unsigned long long)s_hi[w + 1] << 32);
+        id |= valid ? (int)((bh >> lane) & 1ull) << 16 : 0;
+      }
       int rank = 0, equal = 0;
 #pragma unroll 1
       for (int j = lo; j < hi; j += 4) {
@@ -1145,8 +1177,16 @@ __global__ __launch_bounds__(1024) void k_sort_binned_split(const float* __restr
         equal += (o0 == u ? 1 : 0) + (o1 == u ? 1 : 0) + (o2 == u ? 1 : 0) + (o3 == u ? 1 : 0);
       }
       if (equal > 1) {
+        if constexpr (WIDE) {
 #pragma unroll 1
-        for (int j = lo; j < hi; ++j) rank += s_key[j] == u && (int)s_id[j] < id ? 1 : 0;
+          for (int j = lo; j < hi; ++j) {
+            const int other = (int)s_id[j] | (int)((s_hi[j >> 5] >> (j & 31)) & 1u) << 16;
+            rank += s_key[j] == u && other < id ? 1 : 0;
+          }
+        } else {
+#pragma unroll 1
+          for (int j = lo; j < hi; ++j) rank += s_key[j] == u && (int)s_id[j] < id ? 1 : 0;
+        }
       }
       out[k] = (uint32_t)(lo + rank);
       oid[k] = (uint32_t)id;
@@ -1156,17 +1196,29 @@ __global__ __launch_bounds__(1024) void k_sort_binned_split(const float* __restr
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < SITEMS; ++k)
-    if (((t >> 6) * SITEMS + k) * 64 + lane < n_mine) s_id[out[k]] = (uint16_t)oid[k];
+    if (((t >> 6) * SITEMS + k) * 64 + lane < n_mine) {
+      s_id[out[k]] = (uint16_t)oid[k];
+      if constexpr (WIDE)
+        if (oid[k] >> 16) atomicOr(&s_hist[out[k] >> 5], 1u << (out[k] & 31));
+    }
   __syncthreads();
   int32_t* col = order + (int64_t)f * I + rank0;
-  for (int k = t; k < n_mine; k += 1024) col[k] = (int32_t)s_id[k];
+  if constexpr (WIDE) {
+    for (int k = t; k < n_mine; k += 1024)
+      col[k] = (int32_t)((uint32_t)s_id[k] | ((s_hist[k >> 5] >> (k & 31)) & 1u) << 16);
+  } else {
+    for (int k = t; k < n_mine; k += 1024) col[k] = (int32_t)s_id[k];
+  }
 }
 
 template <int SITEMS>
-static int launch_sort_binned_split(bpr_ctx* c, hipStream_t st, int G, int nf, const float* keysT, int32_t* order,
-                                    float* sigma, int32_t* meta) {
+static int launch_sort_binned_split(bpr_ctx* c, hipStream_t st, int G, bool wide, int nf, const float* keysT,
+                                    int32_t* order, float* sigma, int32_t* meta) {
   BPR_HIP_CHECK(hipMemsetAsync(meta, 0, sizeof(int32_t) * 2 * nf, st));  // a workgroup that gives up writes -1
-  hipLaunchKernelGGL((k_sort_binned_split<SITEMS>), dim3(G, nf), dim3(1024), 0, st, keysT, c->I, order, sigma, meta);
+  if (wide)
+    hipLaunchKernelGGL((k_sort_binned_split<SPLIT_WIDE + SITEMS>), dim3(G, nf), dim3(1024), 0, st, keysT, c->I, order, sigma, meta);
+  else
+    hipLaunchKernelGGL((k_sort_binned_split<SITEMS>), dim3(G, nf), dim3(1024), 0, st, keysT, c->I, order, sigma, meta);
   return BPR_OK;
 }
 
@@ -1994,54 +2046,23 @@ int refresh_impl(bpr_ctx* c, bool split, int f_lo, int f_hi) {
   }
   // ---- sort
   static const bool no_fast = getenv("BPR_NO_FAST_REFRESH") != nullptr;  // (process-wide test aids, read once)
-  const int force_sub = c->tune_refresh_sub;  // bpr_set_tuning("refresh_sub", ...): tests force the split / merge paths on small tables
-  // One 1024-thread workgroup sorts a (sub-)column of <= 36 keys per thread in LDS.  Columns are
-  // split over 2 or 4 workgroups — sorted runs merged pairwise by k_merge_runs — when they do not
-  // fit, or when d workgroups would leave CUs idle and the pieces stay >= 5,000 keys (measured on
-  // ML-20M, refresh + launch gaps per step: d=128 0.106 -> 0.095 ms with 2, d=64 0.100 -> 0.079 ms
-  // with 4; d=256 and Netflix's 4.8 k-item columns are fastest unsplit).  A split refresh shares
-  // the chip with the caller's kernels: it keeps the columns whole (fewer, longer workgroups and
-  // no merge pass) whenever they fit.
-  int sub = 1;
-  while (sub < 4 && (I + sub - 1) / sub > 1024 * 36) sub *= 2;
-  if (!split)
-    while (sub < 4 && nf * sub < 256 && I / (2 * sub) >= 5000) sub *= 2;
-  if (force_sub == 1 || force_sub == 2 || force_sub == 4) sub = force_sub;
-  // BINNED sort (r5): a column of <= 20,480 keys is ordered exactly by one workgroup in about a third of the radix
-  // sort's time (k_sort_binned) — whole columns then beat split-and-merge on the idle chip too
-  const bool binned_ok = c->tune_binned != 0 && !no_fast && force_sub == 0 && I >= 2048 &&
-                         !(split && !part && c->tune_partial != 0);
-  // ... with G workgroups per column (k_sort_binned_split) when a column does not fit one workgroup's LDS
-  // (I <= 65,535: 16-bit ids)
-  int binned_g = 0, binned_sitems = 0;
-  if (binned_ok && I <= 65535) {
-    if (c->tune_binned_split > 0) binned_g = c->tune_binned_split;  // (tests)
-    else if (I > 1024 * 20) binned_g = (int)((I * 106 / 100 + 20 * 1024 - 1) / (20 * 1024));
-    else binned_g = 1;  // (two workgroups per column on the idle chip were measured: 54.6 against 50.7 us per
-                        // ML-20M refresh — every workgroup repeats the histogram passes)
-    if (binned_g > 1) {
-      for (;; ++binned_g) {  // the staged stretch (I / G keys + 6 % + a window) in 8 / 12 / 16 / 20 k entries
-        const int64_t need = (I / binned_g) * 106 / 100 + 64;
-        binned_sitems = need <= 8 * 1024 ? 8 : need <= 12 * 1024 ? 12 : need <= 16 * 1024 ? 16 : need <= 20 * 1024 ? 20 : 0;
-        if (binned_sitems != 0) break;
-      }
-    } else if (I > 1024 * 20) {
-      binned_g = 0;  // (forced to one workgroup per column but the column does not fit: the radix sort)
-    }
-  }
-  const bool binned = binned_g == 1;
-  if (binned || (binned_g > 1 && I <= 1024 * 36)) sub = 1;  // (the fallback of a flagged column: k_sort_flagged)
-  int64_t len = (I + sub - 1) / sub;
-  len = (len + 15) / 16 * 16;
-  // PARTIAL order (r5): the split refresh of a column that one workgroup holds — the exact ends + a
-  // bucketed middle, ~half the sort's work (k_sort_partial); everybody but k_stream gets the snapshot
-  // completed on demand (snapshot_complete_impl)
-  const bool partial = split && !part && c->tune_partial != 0 && sub == 1 && len <= 1024 * 24 && I <= 65535 &&
-                       I >= 2048 && !no_fast;
+  // which sorter, how many workgroups per column, which instantiations: bpr_refresh_plan.h
+  RefreshShape shape = {};
+  shape.I = I; shape.nf = nf; shape.split = split; shape.part = part;
+  shape.tune_binned = c->tune_binned; shape.tune_binned_split = c->tune_binned_split;
+  shape.tune_refresh_sub = c->tune_refresh_sub;  // bpr_set_tuning("refresh_sub", ...): tests force the split / merge paths on small tables
+  shape.tune_partial = c->tune_partial; shape.no_fast = no_fast;
+  const RefreshPlan plan = plan_refresh(shape);
+  const int sub = plan.sub;
+  const int64_t len = plan.len;
+  const bool partial = plan.partial;
+  bpr_ctx::RefreshInfo& ri = c->refresh_info[back];
+  ri.route = plan.route; ri.g = plan.g; ri.sub = plan.sub; ri.f_lo = f_lo; ri.nf = nf;
+  ri.items = plan.route == REFRESH_BINNED_SPLIT ? plan.sitems : plan.items;
   c->snap_partial[back] = partial;
   c->snap_keys[back] = keysT;
   if (partial) {
-    const int items = (int)((len + 1023) / 1024);
+    const int items = plan.items;
     int32_t* meta = c->snap_meta[back];
     const int target = c->partial_target;
     if (items <= 6) launch_sort_partial<6>(c, st, keysT, order, sigma, meta, target);
@@ -2051,8 +2072,8 @@ int refresh_impl(bpr_ctx* c, bool split, int f_lo, int f_hi) {
     else if (items <= 20) launch_sort_partial<20>(c, st, keysT, order, sigma, meta, target);
     else launch_sort_partial<24>(c, st, keysT, order, sigma, meta, target);
     BPR_HIP_CHECK(hipGetLastError());
-  } else if (binned) {
-    const int items = (int)((len + 1023) / 1024);
+  } else if (plan.route == REFRESH_BINNED) {
+    const int items = plan.items;
     int32_t* meta = c->snap_meta[back] + 2 * f_lo;
     if (items <= 6) launch_sort_binned<6>(c, st, nf, keysT, order, sigma, meta);
     else if (items <= 10) launch_sort_binned<10>(c, st, nf, keysT, order, sigma, meta);
@@ -2062,18 +2083,20 @@ int refresh_impl(bpr_ctx* c, bool split, int f_lo, int f_hi) {
   } else {
   // the radix path: every column, or — behind the split binned sort — the columns it flagged
   const int32_t* only_flagged = nullptr;
-  if (binned_g > 1) {
+  if (plan.route == REFRESH_BINNED_SPLIT) {
     int32_t* meta = c->snap_meta[back] + 2 * f_lo;
-    int rc = binned_sitems == 8    ? launch_sort_binned_split<8>(c, st, binned_g, nf, keysT, order, sigma, meta)
-             : binned_sitems == 12 ? launch_sort_binned_split<12>(c, st, binned_g, nf, keysT, order, sigma, meta)
-             : binned_sitems == 16 ? launch_sort_binned_split<16>(c, st, binned_g, nf, keysT, order, sigma, meta)
-                                   : launch_sort_binned_split<20>(c, st, binned_g, nf, keysT, order, sigma, meta);
+    const int G = plan.g;
+    const bool wide = plan.wide;  // 17-bit ids: the WIDE k_sort_binned_split
+    int rc = plan.sitems == 8    ? launch_sort_binned_split<8>(c, st, G, wide, nf, keysT, order, sigma, meta)
+             : plan.sitems == 12 ? launch_sort_binned_split<12>(c, st, G, wide, nf, keysT, order, sigma, meta)
+             : plan.sitems == 16 ? launch_sort_binned_split<16>(c, st, G, wide, nf, keysT, order, sigma, meta)
+                                 : launch_sort_binned_split<20>(c, st, G, wide, nf, keysT, order, sigma, meta);
     if (rc != BPR_OK) return rc;
     BPR_HIP_CHECK(hipGetLastError());
     only_flagged = meta;
   }
-  if (only_flagged != nullptr && sub == 1) {  // a flagged column fits one workgroup: k_sort_flagged
-    const int items = (int)((len + 1023) / 1024);
+  if (plan.fallback == REFRESH_FB_FLAGGED) {  // a flagged column fits one workgroup: k_sort_flagged
+    const int items = plan.fb_items;
     int32_t* meta = c->snap_meta[back] + 2 * f_lo;
     if (items <= 10) hipLaunchKernelGGL((k_sort_flagged<10>), dim3(nf), dim3(1024), 0, st, keysT, c->I, order, meta);
     else if (items <= 20) hipLaunchKernelGGL((k_sort_flagged<20>), dim3(nf), dim3(1024), 0, st, keysT, c->I, order, meta);
@@ -2081,13 +2104,13 @@ int refresh_impl(bpr_ctx* c, bool split, int f_lo, int f_hi) {
     else hipLaunchKernelGGL((k_sort_flagged<36>), dim3(nf), dim3(1024), 0, st, keysT, c->I, order, meta);
     BPR_HIP_CHECK(hipGetLastError());
   } else
-  if (len <= 1024 * 36 && !no_fast) {
+  if (plan.route == REFRESH_RADIX || plan.fallback == REFRESH_FB_RADIX) {
     float* keysA = reinterpret_cast<float*>(c->keys_sorted);
     int32_t* idsA = reinterpret_cast<int32_t*>(keysA + n);
     float* keysB = reinterpret_cast<float*>(idsA + n);
     int32_t* idsB = reinterpret_cast<int32_t*>(keysB + n);
     keysA += foff; idsA += foff; keysB += foff; idsB += foff;  // (the kernels index columns from 0)
-    const int items = (int)((len + 1023) / 1024);
+    const int items = plan.route == REFRESH_RADIX ? plan.items : plan.fb_items;
     if (items <= 6) launch_sort_sub<6>(c, st, nf, keysT, sig_acc, order, sigma, sub, len, keysA, idsA, only_flagged);
     else if (items <= 10) launch_sort_sub<10>(c, st, nf, keysT, sig_acc, order, sigma, sub, len, keysA, idsA, only_flagged);
     else if (items <= 12) launch_sort_sub<12>(c, st, nf, keysT, sig_acc, order, sigma, sub, len, keysA, idsA, only_flagged);
@@ -2107,7 +2130,7 @@ int refresh_impl(bpr_ctx* c, bool split, int f_lo, int f_hi) {
       std::swap(idsA, idsB);
     }
     BPR_HIP_CHECK(hipGetLastError());
-  } else if (only_flagged == nullptr) {  // device-wide sort: always every column (a sharded refresh is merely redundant here)
+  } else if (plan.route == REFRESH_DEVICE) {  // device-wide sort: always every column (a sharded refresh is merely redundant here)
     hipLaunchKernelGGL(k_sigma, dim3(d), dim3(256), 0, st, keysT - foff, I, sigma - f_lo);
     uint64_t* k64 = reinterpret_cast<uint64_t*>(c->keys_sorted);
     hipLaunchKernelGGL(k_compose_keys, dim3(2048), dim3(256), 0, st, keysT - foff, k64, n, I);
@@ -2129,6 +2152,7 @@ int refresh_impl(bpr_ctx* c, bool split, int f_lo, int f_hi) {
     return BPR_OK;
   }
   c->snap_front = back;
+  c->refresh_done = back;
   c->order = order;
   c->sigma = sigma;
   c->meta_front = c->snap_partial[back] ? c->snap_meta[back] : nullptr;
@@ -2180,6 +2204,7 @@ int refresh_publish_impl(bpr_ctx* c) {
   }
   const int back = c->have_snapshot ? (c->snap_front ^ 1) : c->snap_front;
   c->snap_front = back;
+  c->refresh_done = back;
   c->order = c->order_alloc[back] + BPR_ORDER_PAD;
   c->sigma = c->sigma_buf[back];
   c->meta_front = nullptr;  // (a sharded refresh is always sorted whole)
@@ -2198,6 +2223,7 @@ int refresh_commit_impl(bpr_ctx* c) {
   BPR_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_sorted, 0));
   const int back = c->have_snapshot ? (c->snap_front ^ 1) : c->snap_front;
   c->snap_front = back;
+  c->refresh_done = back;
   c->order = c->order_alloc[back] + BPR_ORDER_PAD;
   c->sigma = c->sigma_buf[back];
   c->meta_front = c->snap_partial[back] ? c->snap_meta[back] : nullptr;
@@ -2205,6 +2231,29 @@ int refresh_commit_impl(bpr_ctx* c) {
   c->keys_front_stale = false;
   c->have_snapshot = true;
   c->refresh_pending = false;
+  return BPR_OK;
+}
+
+// What the last completed refresh ran (bpr_adaptive_refresh_info): the plan's figures as refresh_impl recorded them,
+// and the columns the split binned sort flagged, read back from its meta — memset to 0 before the launch; a
+// workgroup that gives up writes -1, which the radix fallback leaves and k_sort_flagged replaces by I.
+int refresh_info_impl(bpr_ctx* c, int32_t* info_host) {
+  for (int k = 0; k < BPR_REFRESH_INFO_LEN; ++k) info_host[k] = -1;
+  if (c->refresh_done < 0) return BPR_OK;  // no refresh yet: every field -1
+  const bpr_ctx::RefreshInfo& ri = c->refresh_info[c->refresh_done];
+  info_host[0] = ri.route;
+  info_host[1] = ri.g;
+  info_host[2] = ri.items;
+  info_host[3] = ri.sub;
+  if (ri.route == REFRESH_BINNED_SPLIT) {
+    BPR_HIP_CHECK(hipStreamSynchronize(c->stream));
+    std::vector<int32_t> meta(2 * (size_t)ri.nf);
+    BPR_HIP_CHECK(hipMemcpy(meta.data(), c->snap_meta[c->refresh_done] + 2 * ri.f_lo, sizeof(int32_t) * meta.size(),
+                            hipMemcpyDeviceToHost));
+    int flagged = 0;
+    for (int f = 0; f < ri.nf; ++f) flagged += meta[2 * (size_t)f] != 0 ? 1 : 0;
+    info_host[4] = flagged;
+  }
   return BPR_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "bpr_kernels.h"
 #include "bpr_host.h"
 #include "bpr_stream_plan.h"
+#include "bpr_refresh_plan.h"
 
 namespace bpr {
 static_assert(ORDER_PAD == BPR_ORDER_PAD, "walk vector width vs snapshot padding");
@@ -858,6 +859,13 @@ int bpr_adaptive_snapshot_partial(bpr_ctx* c, int32_t* partial_host) {
   return BPR_OK;
 }
 
+int bpr_adaptive_refresh_info(bpr_ctx* c, int32_t* info_host) {
+  if (int rc = check_bound(c, "bpr_adaptive_refresh_info")) return rc;
+  if (info_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_adaptive_refresh_info: info_host is NULL");
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  return refresh_info_impl(c, info_host);
+}
+
 int bpr_adaptive_refresh_pending(bpr_ctx* c, int32_t* pending_host) {
   if (c == nullptr || pending_host == nullptr)
     return fail(BPR_ERR_INVALID, "bpr_adaptive_refresh_pending: NULL argument");
@@ -1370,7 +1378,7 @@ int bpr_set_tuning(bpr_ctx* c, const char* key, int32_t value) {
   else if (k == "adam_closed" && (value == 0 || value == 1)) c->tune_adam_closed = value;
   else if (k == "partial_snapshot" && (value == 0 || value == 1)) c->tune_partial = value;
   else if (k == "binned_sort" && (value == 0 || value == 1)) c->tune_binned = value;
-  else if (k == "binned_split" && value >= 0 && value <= 4) c->tune_binned_split = value;
+  else if (k == "binned_split" && value >= 0 && value <= 16) c->tune_binned_split = value;
   else if (k == "partial_target" && value >= 1 && value <= 1024) c->partial_target = value;
   else if (k == "refresh_sub" && (value == 0 || value == 1 || value == 2 || value == 4)) c->tune_refresh_sub = value;
   else if (k == "lds_block" && value >= 0 && value <= 1024 && value % 64 == 0) c->tune_lds_block = value;
@@ -1411,6 +1419,19 @@ int bpr_test_stream_plan(const int64_t* in, int32_t occ, int64_t* out) {
   const StreamPlan p = plan_stream(s, plan_stream_block(s), occ);
   const int64_t v[] = {p.kernel, p.seen, p.block, p.grid, (int64_t)p.shmem, p.bm_words, p.gpw_active, p.run_len,
                        p.L, p.tail1, p.tail2};
+  memcpy(out, v, sizeof(v));
+  return BPR_OK;
+}
+
+// Test hook, not API (tests/test_refresh_plan_cpu.py sets its signature): the sorter plan of a refresh given as plain
+// integers — RefreshShape's fields in order; out = RefreshPlan's fields in order.  Needs no GPU.
+int bpr_test_refresh_plan(const int64_t* in, int64_t* out) {
+  RefreshShape s = {};
+  s.I = in[0]; s.nf = (int)in[1]; s.split = in[2] != 0; s.part = in[3] != 0;
+  s.tune_binned = (int)in[4]; s.tune_binned_split = (int)in[5]; s.tune_refresh_sub = (int)in[6];
+  s.tune_partial = (int)in[7]; s.no_fast = in[8] != 0;
+  const RefreshPlan p = plan_refresh(s);
+  const int64_t v[] = {p.route, p.sub, p.len, p.g, p.sitems, p.items, p.fallback, p.fb_items, p.wide, p.partial};
   memcpy(out, v, sizeof(v));
   return BPR_OK;
 }

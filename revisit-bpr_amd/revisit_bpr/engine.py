@@ -161,7 +161,8 @@ class Engine:
 
     def set_tuning(self, key: str, value: int) -> None:
         """``bpr_set_tuning``: "seen" 0 auto | 1 csr | 2 bitmap | 3 list; "vs_direct" -1 auto | 0 | 1;
-        "refresh_sub" 0 | 1 | 2 | 4; "partial_snapshot" 0 | 1; "partial_target" 1..1024; "binned_sort" 1 | 0."""
+        "refresh_sub" 0 | 1 | 2 | 4; "partial_snapshot" 0 | 1; "partial_target" 1..1024; "binned_sort" 1 | 0;
+        "binned_split" 0 by shape | 1..16 workgroups per column of the split binned sort."""
         native.check(self._lib.bpr_set_tuning(self._ctx, key.encode(), int(value)))
         self.__dict__.setdefault("_tuning", {})[key] = int(value)
 
@@ -386,6 +387,21 @@ class Engine:
 
     def comm_destroy(self) -> None:
         native.check(self._lib.bpr_comm_destroy(self._ctx))
+
+    REFRESH_ROUTES = ("radix", "binned", "binned_split", "partial", "device")
+
+    def refresh_info(self) -> dict:
+        """``bpr_adaptive_refresh_info``: what the last completed refresh ran — {"route": one of REFRESH_ROUTES (None
+        before the first refresh), "route_id", "g": workgroups per column of the binned sort, "items": keys per
+        thread of the kernel instantiation, "sub": workgroups per column of the radix sort or fallback,
+        "fallback_columns": columns the split binned sort handed to its fallback (None on the other routes)}.
+        A diagnostic: it waits for the stream."""
+        self._sync_stream()
+        out = (ctypes.c_int32 * native.REFRESH_INFO_LEN)()
+        native.check(self._lib.bpr_adaptive_refresh_info(self._ctx, out))
+        route, g, items, sub, fell = (int(v) for v in out[:5])
+        return {"route": self.REFRESH_ROUTES[route] if route >= 0 else None, "route_id": route, "g": g, "items": items,
+                "sub": sub, "fallback_columns": fell if fell >= 0 else None}
 
     def refresh_pending(self) -> bool:
         out = ctypes.c_int32(0)

@@ -21,6 +21,7 @@ OPT_SGD, OPT_MOMENTUM, OPT_ADAM, OPT_RMSPROP = 0, 1, 2, 3
 MODE_STRICT, MODE_STREAM = 0, 1
 NEG_GIVEN, NEG_UNIFORM, NEG_ADAPTIVE = 0, 1, 2
 SCALARS = 4
+REFRESH_INFO_LEN = 8  # BPR_REFRESH_INFO_LEN: int32 entries bpr_adaptive_refresh_info fills
 
 
 class OptParams(ctypes.Structure):
@@ -64,6 +65,7 @@ SIGNATURES = {
     "bpr_bind_opt_state": (c_int, [c_void_p] + [c_void_p] * 6),
     "bpr_sample_uniform": (c_int, [c_void_p, c_void_p, c_int64, c_uint64, c_uint64, c_void_p]),
     "bpr_adaptive_refresh": (c_int, [c_void_p]),
+    "bpr_adaptive_refresh_info": (c_int, [c_void_p, POINTER(c_int32)]),
     "bpr_adaptive_refresh_begin": (c_int, [c_void_p]),
     "bpr_adaptive_refresh_commit": (c_int, [c_void_p]),
     "bpr_adaptive_refresh_pending": (c_int, [c_void_p, POINTER(c_int32)]),

@@ -1,6 +1,9 @@
 #!/usr/bin/env python
-"""Time of one adaptive-snapshot refresh (cut + sort) on the idle chip: k_sort_binned against the radix sort.
-    python tools/sort_time.py [I d]          (default: the ML-20M shape)"""
+"""Time of one adaptive-snapshot refresh (cut + sort) on the idle chip: the binned sort against the radix sort.
+    python tools/sort_time.py [I d [G ...]]      (default: the ML-20M shape; G: extra legs with `binned_split` forced)
+Every leg: 5 refreshes to warm up, then REPS repetitions of BATCH refreshes between two events; the line shows the
+median (min .. max) of the repetitions in us per refresh and what Engine.refresh_info says the refresh ran."""
+import statistics
 import sys
 from pathlib import Path
 
@@ -11,7 +14,9 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "revisit-bpr_amd"))
 from revisit_bpr.engine import Engine  # noqa: E402
 
+REPS, BATCH = 7, 20
 shapes = [(int(sys.argv[1]), int(sys.argv[2]))] if len(sys.argv) > 2 else [(20109, 128), (17771, 64), (4801, 64), (20109, 64)]
+forced = [int(g) for g in sys.argv[3:]]
 for I, d in shapes:
     rng = np.random.default_rng(1)
     for kind in ("random-init", "trained-like"):
@@ -21,16 +26,24 @@ for I, d in shapes:
             Q[cold] *= 0.02
             Q[:, : d // 4] *= 5.0
         Q[0] = 0
-        for binned in (0, 1):
+        for leg, tune in [("binned=0", {"binned_sort": 0}), ("binned=1", {"binned_sort": 1})] + \
+                         [(f"split={g}", {"binned_split": g}) for g in forced]:
             e = Engine(torch.zeros(4, d, device="cuda"), torch.from_numpy(Q).cuda(), None)
-            e.set_tuning("binned_sort", binned)
+            for k, v in tune.items():
+                e.set_tuning(k, v)
             for _ in range(5):
                 e.adaptive_refresh()
             torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(50):
-                e.adaptive_refresh()
-            b.record()
-            torch.cuda.synchronize()
-            print(f"I={I} d={d} {kind:12s} binned={binned}: {a.elapsed_time(b) / 50 * 1000:.1f} us per refresh", flush=True)
+            us = []
+            for _ in range(REPS):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(BATCH):
+                    e.adaptive_refresh()
+                b.record()
+                torch.cuda.synchronize()
+                us.append(a.elapsed_time(b) / BATCH * 1000)
+            info = e.refresh_info() if hasattr(e, "refresh_info") else {}
+            ran = " ".join(f"{k}={info[k]}" for k in ("route", "g", "items", "sub", "fallback_columns") if k in info)
+            print(f"I={I} d={d} {kind:12s} {leg:9s}: {statistics.median(us):.1f} ({min(us):.1f} .. {max(us):.1f}) "
+                  f"us per refresh  {ran}", flush=True)
