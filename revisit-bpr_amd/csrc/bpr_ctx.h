@@ -1,4 +1,4 @@
-// bpr_ctx.h — private state of a bpr_ctx (shared by bprcore.hip and bpr_refresh.hip).
+// bpr_ctx.h — private state of a bpr_ctx (shared by bprcore.hip, bpr_refresh.hip, bpr_plan.hip, bpr_hot.hip and the other translation units).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -209,16 +209,16 @@ int refresh_info_impl(bpr_ctx* c, int32_t* info_host);  // bpr_refresh.hip
 int snapshot_complete_impl(bpr_ctx* c);     // bpr_refresh.hip: a partial front snapshot is sorted whole, in place
 void refresh_free(bpr_ctx* c);      // bpr_refresh.hip
 void side_free(bpr_ctx* c);         // bpr_refresh.hip
-int heavy_build_impl(bpr_ctx* c);   // bpr_refresh.hip
-void heavy_free(bpr_ctx* c);        // bpr_refresh.hip
-int hot_build_impl(bpr_ctx* c, const int32_t* pos, int64_t n);  // bpr_refresh.hip
-int hot_set_items_impl(bpr_ctx* c, const int32_t* items, int H, const uint32_t* counts);  // bpr_refresh.hip
+int heavy_build_impl(bpr_ctx* c);   // bpr_hot.hip
+void heavy_free(bpr_ctx* c);        // bpr_hot.hip
+int hot_build_impl(bpr_ctx* c, const int32_t* pos, int64_t n);  // bpr_hot.hip
+int hot_set_items_impl(bpr_ctx* c, const int32_t* items, int H, const uint32_t* counts);  // bpr_hot.hip
 int flush_deferred_stats(bpr_ctx* c);  // bprcore.hip: loss partials a hot-tier cut launch left behind
 int hot_fold_impl(bpr_ctx* c);  // bprcore.hip: fold deltas left by bpr_train_stream_acut (no-op otherwise)
-void hot_free(bpr_ctx* c);                                       // bpr_refresh.hip
-int plan_chunk_impl(bpr_ctx* c, const int32_t* users_in, const int32_t* pos_in, int64_t n, int64_t chunk,
+void hot_free(bpr_ctx* c);                                       // bpr_hot.hip
+int plan_chunk_impl(bpr_ctx* c, const int32_t* users_in, const int32_t* pos_in, int64_t n, int64_t chunk,  // bpr_plan.hip
                     uint64_t seed, int64_t index, int32_t* users_out, int32_t* pos_out, hipStream_t st);
-int plan_epoch_impl(bpr_ctx* c, const int32_t* users_in, const int32_t* pos_in, int64_t n,
+int plan_epoch_impl(bpr_ctx* c, const int32_t* users_in, const int32_t* pos_in, int64_t n,  // bpr_plan.hip
                     int64_t chunk, uint64_t seed, int32_t* users_out, int32_t* pos_out);
 }  // namespace bpr
 

@@ -309,7 +309,7 @@ static_assert(WALK_UNROLL == 4, "the walk fetches one dwordx4 per lane and trip"
 // overhang; overhanging entries are masked to 0 (the pad item: never a candidate).
 constexpr int ORDER_PAD = WALK_UNROLL;  // == BPR_ORDER_PAD (bpr_ctx.h), checked in bprcore.hip
 
-// PARTIAL snapshots (bpr_refresh.hip k_sort_partial): only the two ends of a column are in exact order,
+// PARTIAL snapshots (bpr_sort.h k_sort_partial): only the two ends of a column are in exact order,
 // [0, kt) and [I - kb, I); the middle is bucketed — bins in order, any order inside a bin, the first
 // entry of a bin flagged in its top bit (item ids are < 2^30).  `keys_f` = the column of keys the
 // snapshot was sorted from (NULL: an ordinary, fully sorted snapshot — kt, kb unused).

@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void k_stream_epilogue(const EpilogueArgs a) {
 // every element of the item table is read once anyway to be transposed into the snapshot's key
 // buffer T [d, I]; rows of the hot block take their delta on the way (Q += delta, delta = 0).  Block
 // (0, 0) of the extra row gridDim.y - 1 sums the loss statistics.  Replaces k_stream_epilogue +
-// k_transpose (bpr_refresh.hip) and one kernel boundary between two STREAM launches.
+// k_transpose (bpr_sort.h) and one kernel boundary between two STREAM launches.
 struct EpilogueCutArgs {
   const float* partials;
   float* out;

@@ -66,7 +66,7 @@ struct StreamArgs {
   const uint32_t* heavy_off;
   const uint32_t* heavy_bits;
   int32_t heavy_T;
-  // a PARTIAL adaptive snapshot (bpr_refresh.hip k_sort_partial): {kt, kb} per column and the key columns
+  // a PARTIAL adaptive snapshot (bpr_sort.h k_sort_partial): {kt, kb} per column and the key columns
   // the snapshot was sorted from (NULL: `order` is sorted whole)
   const int32_t* snap_meta;
   const float* snap_keys;
@@ -130,7 +130,7 @@ struct SigmaLds {
 // (occupancy: the adaptive sampler over the staged-list structure needs a few registers more than
 // 5 waves per SIMD leave; measured on MI355X, 4 and 5 waves run the kernel equally fast — it is not
 // bound by occupancy — so that variant asks for 4 instead of spilling)
-// PART: the adaptive snapshot may be partial (bpr_refresh.hip k_sort_partial) — its own instantiations
+// PART: the adaptive snapshot may be partial (bpr_sort.h k_sort_partial) — its own instantiations
 // (its in-bin finish needs ~20 registers more than 5 waves per SIMD leave: it asks for 4 — the kernel is
 // not bound by occupancy, see above — instead of spilling)
 //

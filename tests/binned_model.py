@@ -1,4 +1,4 @@
-"""A numpy restatement of k_sort_binned's ALGORITHM (revisit-bpr_amd/csrc/bpr_refresh.hip) — test infrastructure:
+"""A numpy restatement of k_sort_binned's ALGORITHM (revisit-bpr_amd/csrc/bpr_sort.h, bpr_sort_shared.h) — test infrastructure:
 the two-level interpolated rank (float32 arithmetic as the kernel has it), the equi-depth bins, the counting sort and
 the ranking inside a bin.  It pins the argument the kernel's exactness rests on — the bin is a monotone function of
 the key, equal keys share a bin — on the CPU; the HIP kernel itself is compared with the oracle's order in

@@ -1,24 +1,29 @@
 #!/usr/bin/env python
-"""Builds tools/ubench/binned_bench: k_sort_binned (cut out of csrc/bpr_refresh.hip as it stands) timed alone on
-the idle chip, with variants that leave phases out (WRONG orders: bounds on what each phase costs).
+"""Builds tools/ubench/binned_bench: k_sort_binned (cut out of csrc/bpr_sort.h as it stands, with the sorters' shared
+pieces of csrc/bpr_sort_shared.h) timed alone on the idle chip, with variants that leave phases out (WRONG orders:
+bounds on what each phase costs).
     python tools/ubench/make_binned_bench.py && tools/ubench/binned_bench"""
 import subprocess
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[2]
-src = (ROOT / "revisit-bpr_amd/csrc/bpr_refresh.hip").read_text()
-body = src[src.index("constexpr int BIN_MAX = 64;"):src.index("// The binned sort with G workgroups per column")]
-body = body[:body.rindex("// -----")]  # (the one-workgroup kernel only)
+shared = (ROOT / "revisit-bpr_amd/csrc/bpr_sort_shared.h").read_text()
+shared = shared[shared.index("constexpr int BIN_MAX = 64;"):shared.rindex("}  // namespace bpr")]
+src = (ROOT / "revisit-bpr_amd/csrc/bpr_sort.h").read_text()
+kernel = src[src.index("// BINNED snapshot sort"):src.index("// The binned sort with G workgroups per column")]
+kernel = kernel[kernel.index("template <int ITEMS>"):kernel.rindex("// -----")]  # (the one-workgroup kernel only)
+body = shared + kernel
 
 
 def variant(name, text):
     return "namespace " + name + " {\n" + text + "\n}\n"
 
 
-no_rank = body.replace("      for (int j = lo; j < hi; j += 4) {", "      for (int j = lo; j < lo; j += 4) {", 1)
+no_rank = body.replace("  for (int j = lo; j < hi; j += 4) {", "  for (int j = lo; j < lo; j += 4) {", 1)
 no_scatter = no_rank.replace("    if (l < n) {\n      s_key[at] = orderable_desc(keys[k]);", "    if (l < n && at < 0) {\n      s_key[at] = orderable_desc(keys[k]);")
 assert no_rank != body and no_scatter != no_rank
-onetrip = body.replace("      for (int j = lo; j < hi; j += 4) {", "      for (int j = lo; j < min(hi, lo + 1); j += 4) {", 1)
+onetrip = body.replace("  for (int j = lo; j < hi; j += 4) {", "  for (int j = lo; j < min(hi, lo + 1); j += 4) {", 1)
+assert onetrip != body
 r1 = body.replace("  // ---- coarse histogram: 1,024 value-linear bins", "  return;\n  // ---- coarse histogram: 1,024 value-linear bins")
 r2 = body.replace("  // ---- a key's bin from its interpolated rank", "  return;\n  // ---- a key's bin from its interpolated rank")
 r3 = body.replace("  // ---- the bins' sizes -> first positions", "  return;\n  // ---- the bins' sizes -> first positions")
