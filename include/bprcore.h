@@ -565,6 +565,39 @@ int bpr_topk_rows(const float* P, const float* Q, const float* item_bias /* or N
                   void* workspace, int64_t workspace_bytes,
                   int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
 
+/* ---- fold-in: user rows for users who arrive after training, learnt against the FROZEN item table (the reference
+ * has no such step: its held-out users' histories are part of the training file, full-train-with-fold-in.jsonl, which
+ * is why configs/RQ3/user-split has no BPR entry).  One kernel (csrc/bpr_foldin.hip); Q and item_bias are never
+ * written.  The new users are the rows of a CSR — indptr [n+1] int64 (indptr[0] need not be 0: a slice of a larger
+ * CSR works), items int32, sorted ascending inside a row, no duplicates, ids in [1, I) — and P_new [n, d] holds the
+ * caller's initial rows on entry and the learnt rows on return.  With nnz = indptr[n] - indptr[0], row r of length m
+ * takes `epochs` * m sequential SGD steps, epoch by epoch, position by position; the step of epoch e, position j has
+ *     triple index   t = e * nnz + (indptr[r] - indptr[0]) + j
+ *     positive       i = items[indptr[r] + j]
+ *     negative       BPR_NEG_GIVEN: neg_in[t];  BPR_NEG_UNIFORM: the negative bpr_sample_uniform draws for counter
+ *                    offset + t on a context whose seen row of the user is this row (same seed; no item weights);
+ *                    it is also written to neg_out[t] when neg_out is not NULL
+ *     update, fp32   x = <p, q_i - q_j> (+ b_i - b_j),  w = sigma(-x),  p <- p - lr (-w (q_i - q_j) + alpha_user p)
+ * SKIP RULE: a triple whose negative is 0 is skipped (p unchanged) — what the sampler returns when the row covers
+ * every item; so is one whose positive or given negative lies outside [1, I).  A row of length 0 keeps its initial
+ * values.  The result is a pure function of these definitions: its bits do not depend on `order`, on n or on the
+ * launch.  order [n] int32 or NULL: a permutation of the rows, the sequence in which they are handed to the groups of
+ * the launch (longest rows first evens out the tail; NULL = list order; an entry outside [0, n) is passed over).
+ * d in [1, 1024] (0: BPR_ERR_INVALID, more: BPR_ERR_UNSUPPORTED); n below 2^31; I * d and epochs * nnz below 2^31
+ * (BPR_ERR_UNSUPPORTED); BPR_NEG_ADAPTIVE: BPR_ERR_UNSUPPORTED.  Arguments are validated before the device is
+ * touched; n == 0 is BPR_OK.  indptr is read by the kernel only, except for ONE host read: the call copies indptr[0]
+ * and indptr[n] back for the bound on epochs * nnz and waits for `hip_stream` to do so (the launch itself is
+ * asynchronous; the call cannot be captured into a graph).  A device's first call allocates a few ticket words that
+ * live as long as the process.  Context-free: runs on `hip_stream` of the current device. */
+int bpr_fold_in_rows(const float* Q, const float* item_bias /* or NULL */, int64_t I, int32_t d,
+                     const int64_t* indptr /* [n+1] */, const int32_t* items, int64_t n,
+                     const int32_t* order /* [n] or NULL */,
+                     int32_t epochs, float lr, float alpha_user,
+                     int32_t sampler /* BPR_NEG_GIVEN | BPR_NEG_UNIFORM */,
+                     const int32_t* neg_in /* [epochs*nnz], GIVEN */, int32_t* neg_out /* [epochs*nnz] or NULL */,
+                     uint64_t seed, uint64_t offset,
+                     float* P_new /* [n,d], in/out: the caller's initial rows */, void* hip_stream);
+
 /* ---- multi-GPU item-table reconciliation (no reference counterpart: the reference's DDP path is
  * never enabled by a config, experiments/launcher.py:35-73).  The all-reduce itself is RCCL via
  * torch.distributed; these two fused elementwise kernels bracket it (revisit_bpr/distributed.py).

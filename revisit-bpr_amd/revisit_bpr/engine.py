@@ -224,6 +224,24 @@ class Engine:
         indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
         return recommend(self.P, self.Q, self.item_bias, users, k, indptr, indices, item_slices=item_slices)
 
+    def fold_in(self, indptr: torch.Tensor, items: torch.Tensor, *, epochs: int, lr: Optional[float] = None,
+                **kwargs) -> torch.Tensor:
+        """User rows for NEW users (the rows of the CSR `indptr` / `items`) learnt against the engine's item
+        table and bias, which are not changed (`bpr_fold_in_rows`, see revisit_bpr/foldin.py for the keywords).
+        `reg_user` defaults to the alpha_user of `set_reg`, `lr` to the learning rate of `set_optimizer`.  The
+        item table is made whole first: the hot block an asynchronous cut left is folded and rows a lazy
+        optimizer has not replayed yet are flushed."""
+        from revisit_bpr.foldin import fold_in
+
+        if lr is None:
+            lr = getattr(self, "_lr", None)
+            if lr is None:
+                raise ValueError("fold_in needs `lr`: no optimizer was set on this engine")
+        kwargs.setdefault("reg_user", getattr(self, "_reg", (0.0, 0.0, 0.0))[0])
+        self.hot_fold()
+        self.flush_items()
+        return fold_in(self.Q, self.item_bias, indptr, items, epochs=epochs, lr=lr, **kwargs)
+
     def bind_item_weights(self, weights: Optional[torch.Tensor]) -> None:
         """Item weights of the uniform sampler (count_i ** neg_sampling_alpha of the reference's
         BPRExperiment): [I] non-negative; None = uniform."""
@@ -240,6 +258,7 @@ class Engine:
 
     def set_reg(self, user: float, item: float, neg: float) -> None:
         native.check(self._lib.bpr_set_reg(self._ctx, user, item, neg))
+        self._reg = (float(user), float(item), float(neg))
 
     def set_optimizer(self, kind: int, lr: float, momentum: float = 0.0, dampening: float = 0.0,
                       nesterov: bool = False, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -249,6 +268,7 @@ class Engine:
         native.check(self._lib.bpr_set_optimizer(self._ctx, kind, ctypes.byref(prm)))
         self.opt_kind = kind
         self._momentum = momentum
+        self._lr = float(lr)
 
     def bind_opt_state(self, mP=None, vP=None, mQ=None, vQ=None, mb=None, vb=None) -> None:
         self._keep["opt_state"] = (mP, vP, mQ, vQ, mb, vb)

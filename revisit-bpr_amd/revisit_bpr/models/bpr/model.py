@@ -476,6 +476,22 @@ class Model(torch.nn.Module):
             scores += ub.detach()[users.reshape(-1).long()].unsqueeze(1)
         return items, scores
 
+    def fold_in(self, indptr: torch.Tensor, items: torch.Tensor, *, epochs: int, lr: float, **kwargs) -> torch.Tensor:
+        """User rows [n, d] for NEW users (the rows of the CSR `indptr` int64 / `items` int32) learnt against the
+        model's frozen item table and item bias by the engine's fold-in kernel (revisit_bpr/foldin.py holds the
+        keywords); `reg_user` defaults to the model's user regularisation.  The model is not changed: the rows
+        are returned, ready for `revisit_bpr.recommend.recommend` or `evaluate_topk`.  Rows behind the optimizer
+        step are replayed first (`sync()`).  Only the MF scorer has a fused form."""
+        if not self._fusable():
+            raise NotImplementedError("fold_in needs the MF logits model in float32: other scorers have no "
+                                      "fold-in kernel")
+        eng = self.engine()
+        self.sync()
+        from revisit_bpr.engine import resolve_reg_alphas
+
+        kwargs.setdefault("reg_user", resolve_reg_alphas(self._reg_alphas)[0])
+        return eng.fold_in(indptr, items, epochs=epochs, lr=lr, **kwargs)
+
     # ---- forward ----------------------------------------------------------------------------
     def forward(self, inputs: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:
         # inputs.user [B]; inputs.item, inputs.neg [B, n]

@@ -1,0 +1,155 @@
+#!/usr/bin/env python
+"""Two questions about fold-in (`revisit_bpr.foldin.fold_in`, csrc/bpr_foldin.hip), answered by measurement only.
+
+(i) What does one call cost?  10,000 held-out users against a trained-scale item table at the ML-20M shape
+(I = 20,109, d = 128; row lengths log-normal, median 37, tail in the thousands) for 5 and 20 epochs, and at the MSD
+shape (I = 41,140, d = 256, median 30), sampled negatives, rows handed out longest first (`balance`) and in list
+order.  hipEvents around one call (it includes the wrapper's argsort and its one host read), median and range of 5
+runs after a warm-up.
+
+(ii) Strong generalisation on `synthetic.generate_latent`: train on all users but 10 %, fold those in from their
+training-side histories, and report `evaluate_topk` nDCG@100 on their held-out items beside the same users trained
+jointly with everybody else (and beside untrained rows, the floor).
+
+Usage: python tools/foldin_probe.py [--reps 5] [--skip-study] [--skip-timing] [--out profiles/foldin_probe.txt]"""
+import argparse
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path[:0] = [str(ROOT), str(ROOT / "revisit-bpr_amd")]
+from revisit_bpr import engine as eng  # noqa: E402
+from revisit_bpr.datasets import synthetic  # noqa: E402
+from revisit_bpr.evaluation import evaluate_topk  # noqa: E402
+from revisit_bpr.foldin import fold_in  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--skip-study", action="store_true")
+ap.add_argument("--skip-timing", action="store_true")
+ap.add_argument("--out", type=str, default=str(ROOT / "profiles" / "foldin_probe.txt"))
+opt = ap.parse_args()
+dev = torch.device("cuda")
+lines = []
+
+
+def say(s=""):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def histories(n, I, median, sigma, seed):
+    """n sorted rows of distinct items in [1, I), lengths log-normal(median, sigma) clipped to [1, I // 3]"""
+    rng = np.random.default_rng(seed)
+    lens = np.clip(np.round(median * np.exp(sigma * rng.standard_normal(n))), 1, I // 3).astype(np.int64)
+    rows = [np.sort(rng.choice(I - 1, size=int(k), replace=False) + 1) for k in lens]
+    indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return torch.from_numpy(indptr).to(dev), torch.from_numpy(np.concatenate(rows).astype(np.int32)).to(dev), lens
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def timing():
+    say(f"(i) one fold_in call, sampled negatives, lr 0.05, reg_user 0.01; ms: median  min .. max of {opt.reps}")
+    say(f"{'shape':30s} {'users':>6s} {'nnz':>9s} {'longest':>7s} {'epochs':>6s} {'balance':>7s} | "
+        f"{'ms':>26s} | {'M triples/s':>11s}")
+    for name, I, d, median, sigma, epoch_list in (("ML-20M I=20109 d=128", 20_109, 128, 37.0, 1.4, (5, 20)),
+                                                  ("MSD I=41140 d=256", 41_140, 256, 30.0, 1.0, (5,))):
+        g = torch.Generator(device=dev).manual_seed(1)
+        Q = (torch.rand(I, d, device=dev, generator=g) - 0.5) / d
+        b = (torch.rand(I, device=dev, generator=g) - 0.5) / d
+        indptr, items, lens = histories(10_000, I, median, sigma, seed=2)
+        nnz = int(lens.sum())
+        for epochs in epoch_list:
+            res = {}
+            for balance in (True, False):
+                call = lambda: fold_in(Q, b, indptr, items, epochs=epochs, lr=0.05, reg_user=0.01, init_std=0.01,  # noqa: E731
+                                       seed=3, balance=balance)
+                res[balance] = call()
+                ms = sorted(timed(call) for _ in range(opt.reps))
+                say(f"{name:30s} {10_000:6d} {nnz:9d} {int(lens.max()):7d} {epochs:6d} {str(balance):>7s} | "
+                    f"{ms[len(ms) // 2]:10.3f}  {ms[0]:6.3f} .. {ms[-1]:6.3f} | {epochs * nnz / ms[len(ms) // 2] / 1e3:11.1f}")
+            assert torch.equal(res[True], res[False])
+        del Q, b, indptr, items
+
+
+def train(users, items, indptr, indices, U, I, d, epochs, lr, reg, seed):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    P = torch.randn(U, d, device=dev, generator=g) * 0.1
+    Q = torch.randn(I, d, device=dev, generator=g) * 0.1
+    P[0] = 0
+    Q[0] = 0
+    e = eng.Engine(P, Q)
+    e.set_reg(reg, reg, reg)
+    e.set_optimizer(eng.OPT_SGD, lr=lr)
+    e.bind_seen_csr(indptr, indices)
+    e.set_stream_opts(True, 0)
+    n = users.numel()
+    for ep in range(epochs):
+        pu, pi = e.plan_epoch(users, items, n, seed=seed + ep)
+        e.train_stream(pu, pi, sampler=eng.NEG_UNIFORM, seed=seed, offset=ep * n)
+    e.hot_fold()
+    torch.cuda.synchronize()
+    e.close()
+    return P, Q
+
+
+def study():
+    U0, I0, d, epochs, lr, reg = 4000, 1500, 32, 60, 0.05, 0.002
+    data = synthetic.generate_latent(U0, I0, 240_000, factors=16, seed=5)
+    rng = np.random.default_rng(6)
+    held = np.sort(rng.choice(np.arange(1, data.num_users), size=U0 // 10, replace=False))
+    is_held = np.zeros(data.num_users, bool)
+    is_held[held] = True
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    # jointly: everybody trains
+    Pj, Qj = train(t(data.users), t(data.items), t(data.indptr), t(data.indices), data.num_users, data.num_items, d,
+                   epochs, lr, reg, seed=7)
+    # without the held-out users: their triples leave the training set, their CSR rows are empty
+    keep = ~is_held[data.users]
+    cnt = np.diff(data.indptr) * ~is_held
+    Pw, Qw = train(t(data.users[keep]), t(data.items[keep]), t(np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)),
+                   t(data.indices[keep]), data.num_users, data.num_items, d, epochs, lr, reg, seed=7)
+    # the held-out users as a list of their own: histories (seen CSR) and targets (eval CSR), re-based
+    h_cnt = np.diff(data.indptr)[held]
+    h_indptr = np.concatenate([[0], np.cumsum(h_cnt)]).astype(np.int64)
+    h_items = np.concatenate([data.indices[data.indptr[u]:data.indptr[u + 1]] for u in held]).astype(np.int32)
+    pos = np.searchsorted(data.eval_users, held)
+    assert np.array_equal(data.eval_users[pos], held)
+    e_cnt = np.diff(data.eval_indptr)[pos]
+    e_indptr = np.concatenate([[0], np.cumsum(e_cnt)]).astype(np.int64)
+    e_items = np.concatenate([data.eval_items[data.eval_indptr[k]:data.eval_indptr[k + 1]] for k in pos]).astype(np.int32)
+    rows = torch.arange(len(held), dtype=torch.int32, device=dev)
+
+    def ndcg(P, Q):
+        return evaluate_topk(P, Q, None, rows, t(e_indptr), t(e_items), t(h_indptr), t(h_items), ks=(100,))["ndcg@100"]
+
+    say()
+    say(f"(ii) generate_latent({U0} users, {I0} items, 240,000 actions, 16 factors), d = {d}, SGD lr {lr}, reg {reg}, "
+        f"{epochs} epochs of uniform-negative STREAM training; {len(held)} users held out; nDCG@100 of those users on "
+        f"their held-out items")
+    say(f"  trained jointly with everybody                      {ndcg(Pj[t(held).long()], Qj):.4f}")
+    for fe in (5, 20, 60):
+        Pn = fold_in(Qw, None, t(h_indptr), t(h_items), epochs=fe, lr=lr, reg_user=reg, init_std=0.1, seed=8)
+        say(f"  folded in against the table trained without them, {fe:2d} epochs   {ndcg(Pn, Qw):.4f}")
+    say(f"  untrained rows (N(0, 0.1^2)) against that table     "
+        f"{ndcg(torch.randn(len(held), d, device=dev) * 0.1, Qw):.4f}")
+
+
+say(f"device {torch.cuda.get_device_name(0)}")
+if not opt.skip_timing:
+    timing()
+if not opt.skip_study:
+    study()
+Path(opt.out).parent.mkdir(parents=True, exist_ok=True)
+Path(opt.out).write_text("\n".join(lines) + "\n")
