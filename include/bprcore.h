@@ -565,6 +565,41 @@ int bpr_topk_rows(const float* P, const float* Q, const float* item_bias /* or N
                   void* workspace, int64_t workspace_bytes,
                   int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
 
+/* ---- ranking of held-out items: where each target of a row stands among the user's eligible items (the reference
+ * measures through full logits: example.py:195-230 and experiments/bpr/exp.py:369-374, an argsort of I scores per
+ * metric object; metrics/auc.py:70-130; metrics/map.py; the user-metrics.jsonl saver of experiments/options.py:319-351).
+ * Fused kernels (csrc/bpr_rank.hip), no [n, I] buffer anywhere.  A row r is a user users[r] with the targets
+ * tgt_items[tgt_indptr[r] .. tgt_indptr[r + 1]) (tgt_indptr [n+1] int64, need not start at 0; the same user may
+ * appear in several rows; at most 112 targets in a row, more: BPR_ERR_INVALID, the caller splits the row).  Item j is
+ * ELIGIBLE for row r if 1 <= j < I and j is not in the seen row of users[r] (the CSR of bpr_bind_seen_csr: int64
+ * [U+1], int32 sorted and unique per row; NULL = only item 0 is left out): bpr_topk_rows' rule.  s(u, j) =
+ * <P[u], Q[j]> (+ item_bias[j]) in fp32, bit for bit the score bpr_topk_rows gives the pair.  For the target t at
+ * position p of tgt_items, over the eligible items j != t of its row's user:
+ *     rank_out[p]       #{ s_j > s_t, or s_j == s_t and j < t }   (t's index in bpr_topk_rows' order)
+ *     not_below_out[p]  #{ s_j >= s_t }                           (not_below - rank = ties that come after t)
+ *     score_out[p]      s_t
+ * A target that is itself not eligible (id 0, outside [0, I), or seen by the user): rank = not_below = -1, score =
+ * -inf; it never faults.  A NaN score is never "before" or ">=" anything.  Other targets of the row count as ordinary
+ * eligible items; a duplicated target gets the same answer at both positions.  The result is a pure function of these
+ * definitions: it does not depend on n, on the order of the rows, on how a user's targets are spread over rows, or on
+ * item_slices (0 = the library chooses; s > 1 cuts the item range over s workgroups per row tile and needs the
+ * workspace).  d in [1, 1024], item_slices in [0, 64], n below 2^31 / 112.  User ids are not checked.  Arguments are
+ * validated before the device is touched; n == 0 is BPR_OK.  tgt_indptr is read by the kernels, except for ONE host
+ * read: the call copies back its two ends and its longest row and waits for `hip_stream` to do so (the launches
+ * themselves are asynchronous; the call cannot be captured into a graph).  Context-free: runs on `hip_stream` of the
+ * current device. */
+/* bytes of device workspace bpr_rank_rows needs for this shape (0 with one slice; with more n * 112 * 12;
+ * item_slices 0: never less than for a smaller n) */
+int bpr_rank_workspace(int64_t n, int64_t I, int32_t d, int32_t item_slices, int64_t* bytes_host);
+/* the slice count a call of this shape runs with (as bpr_topk_slices) */
+int bpr_rank_slices(int64_t n, int64_t I, int32_t d, int32_t item_slices, int32_t* slices_host);
+int bpr_rank_rows(const float* P, const float* Q, const float* item_bias /* or NULL */, int64_t I, int32_t d,
+                  const int32_t* users, int64_t n,
+                  const int64_t* tgt_indptr /* [n+1] */, const int32_t* tgt_items,
+                  const int64_t* seen_indptr /* or NULL */, const int32_t* seen_indices,
+                  int32_t item_slices /* 0 = choose */, void* workspace, int64_t workspace_bytes,
+                  int32_t* rank_out, int32_t* not_below_out, float* score_out, void* hip_stream);
+
 /* ---- fold-in: user rows for users who arrive after training, learnt against the FROZEN item table (the reference
  * has no such step: its held-out users' histories are part of the training file, full-train-with-fold-in.jsonl, which
  * is why configs/RQ3/user-split has no BPR entry).  One kernel (csrc/bpr_foldin.hip); Q and item_bias are never

@@ -224,6 +224,19 @@ class Engine:
         indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
         return recommend(self.P, self.Q, self.item_bias, users, k, indptr, indices, item_slices=item_slices)
 
+    def rank_items(self, users: torch.Tensor, tgt_indptr: torch.Tensor, tgt_items: torch.Tensor,
+                   exclude_seen: bool = True, *, item_slices: int = 0):
+        """(rank, not_below, score) of every target of every row (row r: user `users[r]`, targets
+        `tgt_items[tgt_indptr[r]:tgt_indptr[r + 1]]`) among the user's eligible items, from the bound tables
+        (`bpr_rank_rows`, see revisit_bpr/ranks.py).  Item 0 is never eligible; exclude_seen also leaves out the
+        user's row of the CSR given to `bind_seen_csr`.  Rows an Adam / momentum / RMSprop optimizer has not
+        replayed yet are scored as they stand: `flush_lazy()` first (`Model.rank_items` does)."""
+        from revisit_bpr.ranks import rank_items
+
+        indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
+        return rank_items(self.P, self.Q, self.item_bias, users, tgt_indptr, tgt_items, indptr, indices,
+                          item_slices=item_slices)
+
     def fold_in(self, indptr: torch.Tensor, items: torch.Tensor, *, epochs: int, lr: Optional[float] = None,
                 **kwargs) -> torch.Tensor:
         """User rows for NEW users (the rows of the CSR `indptr` / `items`) learnt against the engine's item

@@ -178,3 +178,114 @@ def evaluate_fused(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: torc
         out[f"recall@{k}"] = float(torch.nan_to_num(hits / n_pos).double().sum() / max(E, 1))
         out[f"precision@{k}"] = float((hits / kk).double().sum() / max(E, 1))
     return out
+
+
+@torch.no_grad()
+def evaluate_ranked(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: torch.Tensor,
+                    eval_indptr: torch.Tensor, eval_items: torch.Tensor, seen_indptr, seen_indices,
+                    ks=(5, 10, 20, 50, 100), auc: bool = False, extra: bool = False, per_user: bool = False,
+                    masked_negatives: bool = True):
+    """The keys of `evaluate_topk` from ONE `rank_items` call (revisit_bpr/ranks.py: the exact position of every
+    held-out item among its user's unseen items, no [n, I] logits, no target matrix) and segment arithmetic on
+    the few numbers per target it returns.  No cutoff limit: any k in `ks` (k > I behaves as k = I, as in
+    `evaluate_topk`).  A target counts once per user however often the eval CSR lists it, and a target that is
+    itself not eligible (id 0, or seen by the user) counts as never retrieved.  Ties are broken by ascending item
+    id, as in `evaluate_fused`.
+
+    auc=True adds `auc`, the quantity of RocAucMany / RocAucManySlow (pairs with the positive STRICTLY above the
+    negative, over positives x negatives; a user without positives gives 0 / 0 = NaN, as the metric classes).
+    masked_negatives=True counts it as the reference's eval loop and `evaluate_topk(auc=True)` do: item 0 and the
+    seen items carry -1e13 and are negatives below every positive (n_neg = I - T).  False: over the eligible
+    items only (n_neg = I - 1 - |seen_u| - T_u; the metric classes with their `mask` argument).
+    extra=True adds `mrr` (1 / (1 + best rank of a target), 0 without one) and `map@k` for every k, the
+    reference's metrics/map.py with its default normalisation: sum over the targets retrieved in the top k of
+    (targets retrieved up to it) / (its position), over min(n_pos, k).
+    per_user=True returns (means, per-user tensors [E] by the same keys), the role of the reference's
+    save_user_metrics."""
+    from revisit_bpr.ranks import rank_items
+
+    dev = P.device
+    I = Q.shape[0]
+    E = eval_users.numel()
+    first, last = (int(v) for v in eval_indptr[[0, E]].tolist())
+    ptr = (eval_indptr[:E + 1] - first).to(torch.int64)
+    items = eval_items[first:last].to(torch.int32)
+    rank, not_below, score = rank_items(P, Q, item_bias, eval_users, ptr, items, seen_indptr, seen_indices)
+    t_cnt = ptr[1:] - ptr[:-1]
+    rows = torch.repeat_interleave(torch.arange(E, device=dev), t_cnt)
+    total = rows.numel()
+    # the first listing of an id in its row
+    in_range = (items >= 0) & (items < I)
+    key = rows * I + items.long().clamp(0, I - 1)
+    order = torch.argsort(key, stable=True)
+    sk = key[order]
+    lead = torch.ones(total, dtype=torch.bool, device=dev)
+    lead[1:] = sk[1:] != sk[:-1]
+    uniq = torch.empty_like(lead)
+    uniq[order] = lead
+    hit = uniq & (rank >= 0)  # targets that can be retrieved at all
+    r = rank.long()
+
+    def per_row(values):
+        return torch.zeros(E, device=dev, dtype=torch.float64).index_add_(0, rows, values.double())
+
+    n_pos = t_cnt.double()
+    kmax = max(min(max(ks), I), 1)
+    disc = 1.0 / torch.log2(torch.arange(kmax, dtype=torch.float, device=dev) + 2.0)
+    ideal_at = torch.cumsum(disc, 0).double()
+    gain = torch.where(hit, 1.0 / torch.log2(r.clamp(min=0).float() + 2.0), torch.zeros((), device=dev)).double()
+    per = {}
+    if extra:  # place of a retrievable target among its row's, by rank: 1 + retrievable targets in front of it
+        hi_idx = torch.nonzero(hit).reshape(-1)
+        o2 = hi_idx[torch.argsort(rows[hi_idx] * I + r[hi_idx])]
+        m_row = per_row(hit).long()
+        starts = torch.cumsum(m_row, 0) - m_row
+        place = torch.zeros(total, dtype=torch.float64, device=dev)
+        place[o2] = (torch.arange(o2.numel(), device=dev) - starts[rows[o2]] + 1).double()
+        prec_at = place / (r.clamp(min=0) + 1).double()
+        best = torch.full((E,), I, dtype=torch.int64, device=dev)
+        best.scatter_reduce_(0, rows[hi_idx], r[hi_idx], reduce="amin")
+        per["mrr"] = torch.where(best < I, 1.0 / (best + 1).double(), torch.zeros((), device=dev, dtype=torch.float64))
+    for k in ks:
+        kk = min(k, I)
+        in_k = hit & (r < kk)
+        hits = per_row(in_k)
+        ideal = ideal_at[(n_pos.clamp(max=kk).long() - 1).clamp(min=0)]
+        ideal = torch.where(n_pos > 0, ideal, torch.zeros_like(ideal))
+        per[f"ndcg@{k}"] = torch.nan_to_num(per_row(torch.where(in_k, gain, torch.zeros_like(gain))) / ideal)
+        per[f"recall@{k}"] = torch.nan_to_num(hits / n_pos)
+        per[f"precision@{k}"] = hits / kk
+        if extra:
+            ap = per_row(torch.where(in_k, prec_at, torch.zeros_like(prec_at)))
+            per[f"map@{k}"] = torch.nan_to_num(ap / n_pos.clamp(max=kk))
+    if auc:
+        users = eval_users.long()
+        n_seen = (seen_indptr[users + 1] - seen_indptr[users]) if seen_indptr is not None else torch.zeros_like(users)
+        n_elig = I - 1 - n_seen  # eligible items of the user
+        # a retrievable target's other retrievable targets that score strictly below it: order the row's by
+        # (rank), i.e. score descending; those after the last one of its score
+        hi_idx = torch.nonzero(hit).reshape(-1)
+        o2 = hi_idx[torch.argsort(rows[hi_idx] * I + r[hi_idx])]
+        m = o2.numel()
+        m_row = per_row(hit).long()
+        ends = torch.cumsum(m_row, 0)  # one past the row's last place in o2
+        at = torch.arange(m, device=dev)
+        last_of_run = torch.ones(m, dtype=torch.bool, device=dev)
+        if m > 1:
+            last_of_run[:-1] = (rows[o2][1:] != rows[o2][:-1]) | (score[o2][1:] != score[o2][:-1])
+        run_end = torch.where(last_of_run, at, torch.full_like(at, m))
+        run_end = torch.flip(torch.cummin(torch.flip(run_end, [0]), 0).values, [0])
+        tgt_below = torch.zeros(total, dtype=torch.int64, device=dev)
+        tgt_below[o2] = ends[rows[o2]] - 1 - run_end
+        below = n_elig[rows] - 1 - not_below.long() - tgt_below  # eligible non-targets strictly below the target
+        if masked_negatives:
+            out_of_play = per_row(uniq & in_range & (rank < 0)).long()  # positives among the masked entries
+            below = below + torch.where(score > -1e13, (n_seen + 1 - out_of_play)[rows], torch.zeros_like(below))
+            T = per_row(uniq & in_range)
+            n_neg = I - T
+        else:
+            T = m_row.double()
+            n_neg = n_elig.double() - T
+        per["auc"] = per_row(torch.where(hit, below, torch.zeros_like(below))) / (T * n_neg)
+    out = {k: float(v.sum() / max(E, 1)) for k, v in per.items()}
+    return (out, per) if per_user else out

@@ -476,6 +476,26 @@ class Model(torch.nn.Module):
             scores += ub.detach()[users.reshape(-1).long()].unsqueeze(1)
         return items, scores
 
+    def rank_items(self, users: torch.Tensor, tgt_indptr: torch.Tensor, tgt_items: torch.Tensor,
+                   exclude_seen: bool = True):
+        """(rank, not_below, score), aligned with `tgt_items`, of every target of every row (row r: user
+        `users[r]`, targets `tgt_items[tgt_indptr[r]:tgt_indptr[r + 1]]`) among the user's eligible items, from
+        the engine's fused ranking kernel (revisit_bpr/ranks.py): item 0 and — exclude_seen — the items of the
+        CSR given to `bind_seen_csr` are not eligible.  Rows behind the optimizer step are replayed first
+        (`sync()`).  A user bias is added to the returned scores (it does not change a user's order).  Only the
+        MF scorer has a fused form."""
+        if not self._fusable():
+            raise NotImplementedError("rank_items needs the MF logits model in float32: other scorers have no "
+                                      "fused ranking kernel")
+        eng = self.engine()
+        self.sync()
+        rank, not_below, score = eng.rank_items(users, tgt_indptr, tgt_items, exclude_seen=exclude_seen)
+        ub = self.logits_model._user_bias
+        if ub is not None:
+            cnt = tgt_indptr[1:] - tgt_indptr[:-1]
+            score += torch.repeat_interleave(ub.detach()[users.reshape(-1).long()], cnt)
+        return rank, not_below, score
+
     def fold_in(self, indptr: torch.Tensor, items: torch.Tensor, *, epochs: int, lr: float, **kwargs) -> torch.Tensor:
         """User rows [n, d] for NEW users (the rows of the CSR `indptr` int64 / `items` int32) learnt against the
         model's frozen item table and item bias by the engine's fold-in kernel (revisit_bpr/foldin.py holds the

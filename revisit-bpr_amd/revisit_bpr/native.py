@@ -119,6 +119,11 @@ SIGNATURES = {
     "bpr_topk_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     "bpr_topk_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
                               c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "bpr_rank_workspace": (c_int, [c_int64, c_int64, c_int32, c_int32, POINTER(c_int64)]),
+    "bpr_rank_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, POINTER(c_int32)]),
+    "bpr_rank_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
     "bpr_fold_in_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p,
                                  c_int32, c_float, c_float, c_int32, c_void_p, c_void_p, c_uint64, c_uint64,
                                  c_void_p, c_void_p]),
