@@ -633,6 +633,33 @@ int bpr_fold_in_rows(const float* Q, const float* item_bias /* or NULL */, int64
                      uint64_t seed, uint64_t offset,
                      float* P_new /* [n,d], in/out: the caller's initial rows */, void* hip_stream);
 
+/* bpr_fold_in_rows with ADAPTIVE negatives (csrc/bpr_foldin_adaptive.hip).  The CSR contract, the triple index t, the
+ * update, the SKIP RULE, row_order (bpr_fold_in_rows' `order`), the bounds, the one host read of indptr's ends, n == 0
+ * and "validated before the device is touched; Q and item_bias are never written" are bpr_fold_in_rows'; so is the
+ * purity: the bits of every output do not depend on row_order, on n, on the launch or on the seen structure the
+ * kernel chooses.  What differs is the negative of triple t: it is the item bpr_sample_adaptive returns for counter
+ * offset + t under `seed` and `p` (the geometric parameter, in (0, 1)) on a context whose user row is THIS row's
+ * value just before that triple's update, whose seen row is this CSR row and whose snapshot is `order` / `sigma` —
+ * the same device code with the (G, E) bpr_sample_adaptive dispatches for this d, so factor, rank and item agree
+ * exactly.  neg_out / factor_out / rank_out [epochs * nnz] (each may be NULL) receive that call's three outputs at
+ * index t.  A row with nothing unseen draws 0 and is skipped.
+ * SNAPSHOT: sigma [d] fp32, the per-factor std; order [d * I] int32, column f = every item id 0..I-1 by descending
+ * q_if, FULLY sorted (a partial snapshot is not accepted; the top bit of an entry is masked off and not
+ * interpreted).  order needs 4 READABLE int32 BEFORE AND AFTER the array: the walk's 16-byte loads overhang a
+ * column's ends by up to 3 entries, which it masks.  The pointer bpr_adaptive_snapshot_ptrs hands out satisfies
+ * this.  An order entry outside [0, I) never becomes an address: it is treated as item 0 (never a candidate).
+ * order and sigma are not written.  Item ids may not exceed 2^30: I - 1 > 2^30 is BPR_ERR_UNSUPPORTED; order or sigma
+ * NULL and p outside (0, 1) (or NaN) are BPR_ERR_INVALID.  Context-free: runs on `hip_stream` of the current
+ * device. */
+int bpr_fold_in_rows_adaptive(const float* Q, const float* item_bias /* or NULL */, int64_t I, int32_t d,
+                              const int32_t* order /* [d*I] */, const float* sigma /* [d] */,
+                              const int64_t* indptr /* [n+1] */, const int32_t* items, int64_t n,
+                              const int32_t* row_order /* [n] or NULL */,
+                              int32_t epochs, float lr, float alpha_user, float p /* geometric, in (0,1) */,
+                              int32_t* neg_out, int32_t* factor_out, int32_t* rank_out /* [epochs*nnz] or NULL */,
+                              uint64_t seed, uint64_t offset,
+                              float* P_new /* [n,d] in/out */, void* hip_stream);
+
 /* ---- multi-GPU item-table reconciliation (no reference counterpart: the reference's DDP path is
  * never enabled by a config, experiments/launcher.py:35-73).  The all-reduce itself is RCCL via
  * torch.distributed; these two fused elementwise kernels bracket it (revisit_bpr/distributed.py).

@@ -35,6 +35,7 @@
 
 #include "bpr_device.h"
 #include "bpr_foldin_plan.h"
+#include "bpr_foldin_shared.h"
 #include "bpr_host.h"
 
 namespace bpr {
@@ -122,21 +123,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin(const FoldinArgs a) {
 #pragma unroll
     for (int s = 0; s < PF; ++s) {
       // ---- update: the triple whose rows were issued PF steps ago
-      {
-        float xl = 0.f;
-#pragma unroll
-        for (int e = 0; e < E; ++e) xl = fmaf(p[e], qi[s][e] - qj[s][e], xl);
-        float x = group_sum<G>(xl, lane);
-        x += bi[s] - bj[s];
-        const float w = 1.0f / (1.0f + expf(x));
-        const bool upd = rn[s] != 0;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          const float pe = p[e];
-          const float du = -a.lr * (-w * (qi[s][e] - qj[s][e]) + a.au * pe);
-          p[e] = upd ? pe + du : pe;
-        }
-      }
+      foldin_update<G, E>(p, qi[s], qj[s], bi[s], bj[s], rn[s] != 0, a.lr, a.au, lane);
       // ---- rows: issue the loads of the triple fetched PF steps ago
       {
         const int32_t i = fi[s], j = fn[s];
@@ -186,7 +173,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin(const FoldinArgs a) {
   }
 }
 
-static int check_shape(const char* who, int64_t n, int64_t I, int32_t d) {
+int foldin_check_shape(const char* who, int64_t n, int64_t I, int32_t d) {
   if (n < 0 || n > 0x7FFFFFFF) return fail(BPR_ERR_INVALID, std::string(who) + ": n must be in [0, 2^31)");
   if (d < 1) return fail(BPR_ERR_INVALID, std::string(who) + ": d must be in [1, 1024]");
   if (d > FOLDIN_MAX_D) return fail(BPR_ERR_UNSUPPORTED, std::string(who) + ": d must be in [1, 1024]");
@@ -204,10 +191,10 @@ static uint32_t* g_tickets[FOLDIN_MAX_DEV];
 static unsigned g_ticket_next[FOLDIN_MAX_DEV];
 static int g_cus[FOLDIN_MAX_DEV];
 
-static int next_ticket(uint32_t** out, int* cus) {
+int foldin_next_ticket(const char* who, uint32_t** out, int* cus) {
   int dev = 0;
   BPR_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= FOLDIN_MAX_DEV) return fail(BPR_ERR_UNSUPPORTED, "bpr_fold_in_rows: device index too large");
+  if (dev < 0 || dev >= FOLDIN_MAX_DEV) return fail(BPR_ERR_UNSUPPORTED, std::string(who) + ": device index too large");
   std::lock_guard<std::mutex> lock(g_ticket_mu);
   if (g_tickets[dev] == nullptr) {
     BPR_HIP_CHECK(hipDeviceGetAttribute(&g_cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
@@ -225,7 +212,7 @@ extern "C" int bpr_fold_in_rows(const float* Q, const float* item_bias, int64_t 
                                 float alpha_user, int32_t sampler, const int32_t* neg_in, int32_t* neg_out,
                                 uint64_t seed, uint64_t offset, float* P_new, void* hip_stream) {
   using namespace bpr;
-  if (int rc = check_shape("bpr_fold_in_rows", n, I, d)) return rc;
+  if (int rc = foldin_check_shape("bpr_fold_in_rows", n, I, d)) return rc;
   if (epochs < 1) return fail(BPR_ERR_INVALID, "bpr_fold_in_rows: epochs must be at least 1");
   if (sampler == BPR_NEG_ADAPTIVE)
     return fail(BPR_ERR_UNSUPPORTED, "bpr_fold_in_rows: adaptive negatives are not implemented for fold-in");
@@ -253,7 +240,7 @@ extern "C" int bpr_fold_in_rows(const float* Q, const float* item_bias, int64_t 
 
   uint32_t* ticket = nullptr;
   int cus = FOLDIN_CUS;
-  if (int rc = next_ticket(&ticket, &cus)) return rc;
+  if (int rc = foldin_next_ticket("bpr_fold_in_rows", &ticket, &cus)) return rc;
   BPR_HIP_CHECK(hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream));
   const FoldinPlan p = plan_foldin(n, d, cus);
   FoldinArgs a = {};
@@ -277,7 +264,7 @@ extern "C" int bpr_fold_in_rows(const float* Q, const float* item_bias, int64_t 
 // default)}; out = {G, E, block, groups_per_block, pf, groups, grid, resident}.  Needs no GPU.
 extern "C" int bpr_test_foldin_plan(const int64_t* in, int64_t* out) {
   using namespace bpr;
-  if (int rc = check_shape("bpr_test_foldin_plan", in[0], 1, (int32_t)in[1])) return rc;
+  if (int rc = foldin_check_shape("bpr_test_foldin_plan", in[0], 1, (int32_t)in[1])) return rc;
   const FoldinPlan p = plan_foldin(in[0], (int)in[1], in[2] > 0 ? (int)in[2] : FOLDIN_CUS);
   const int64_t v[] = {p.G, p.E, p.block, p.groups_per_block, p.pf, p.groups, p.grid, FOLDIN_RESIDENT};
   memcpy(out, v, sizeof(v));

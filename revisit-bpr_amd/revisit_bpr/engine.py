@@ -238,13 +238,20 @@ class Engine:
                           item_slices=item_slices)
 
     def fold_in(self, indptr: torch.Tensor, items: torch.Tensor, *, epochs: int, lr: Optional[float] = None,
-                **kwargs) -> torch.Tensor:
+                sampler: str = "uniform", refresh: bool = True, **kwargs) -> torch.Tensor:
         """User rows for NEW users (the rows of the CSR `indptr` / `items`) learnt against the engine's item
         table and bias, which are not changed (`bpr_fold_in_rows`, see revisit_bpr/foldin.py for the keywords).
         `reg_user` defaults to the alpha_user of `set_reg`, `lr` to the learning rate of `set_optimizer`.  The
         item table is made whole first: the hot block an asynchronous cut left is folded and rows a lazy
-        optimizer has not replayed yet are flushed."""
-        from revisit_bpr.foldin import fold_in
+        optimizer has not replayed yet are flushed.
+
+        `sampler="adaptive"` (`bpr_fold_in_rows_adaptive`; `adaptive_p` as in foldin.fold_in) draws from the
+        engine's own snapshot buffers, without a copy.  `refresh=True` runs `adaptive_refresh()` first, after the
+        fold and the flush, so the snapshot is the item table's as it stands — and it REPLACES the snapshot the
+        training samplers read: a training loop that folds users in mid-epoch should pass `refresh=False`, or
+        refresh on its own schedule.  `refresh=False` needs an existing snapshot, and the caller vouches for its
+        age: the kernel cannot tell a stale order from a fresh one."""
+        from revisit_bpr import foldin
 
         if lr is None:
             lr = getattr(self, "_lr", None)
@@ -253,7 +260,22 @@ class Engine:
         kwargs.setdefault("reg_user", getattr(self, "_reg", (0.0, 0.0, 0.0))[0])
         self.hot_fold()
         self.flush_items()
-        return fold_in(self.Q, self.item_bias, indptr, items, epochs=epochs, lr=lr, **kwargs)
+        if sampler == "adaptive":
+            if "snapshot" in kwargs:
+                raise ValueError("Engine.fold_in draws from the engine's own snapshot")
+            if refresh:
+                self.adaptive_refresh()
+            elif not self._has_snapshot():
+                raise RuntimeError("fold_in(sampler='adaptive', refresh=False) needs a snapshot: call "
+                                   "adaptive_refresh() first")
+            order, sigma = self._snapshot_views(back=False)
+            kwargs["snapshot"] = (foldin._PaddedOrder(order), sigma)  # (the engine's buffer carries the slack)
+        return foldin.fold_in(self.Q, self.item_bias, indptr, items, epochs=epochs, lr=lr, sampler=sampler, **kwargs)
+
+    def _has_snapshot(self) -> bool:
+        """True once a refresh has published a snapshot (`adaptive_snapshot()` would succeed)."""
+        self._sync_stream()
+        return self._lib.bpr_adaptive_get_snapshot(self._ctx, None, None) == native.OK
 
     def bind_item_weights(self, weights: Optional[torch.Tensor]) -> None:
         """Item weights of the uniform sampler (count_i ** neg_sampling_alpha of the reference's

@@ -1,5 +1,6 @@
 """Fold new users into a trained model on the HIP engine: learn p_u from a new user's history against
-the FROZEN item table (`bpr_fold_in_rows`, csrc/bpr_foldin.hip).  The result is a [n, d] user table for
+the FROZEN item table (`bpr_fold_in_rows`, csrc/bpr_foldin.hip; with adaptive negatives
+`bpr_fold_in_rows_adaptive`, csrc/bpr_foldin_adaptive.hip).  The result is a [n, d] user table for
 `recommend`, `evaluate_topk` and `evaluate_fused`, which take any such table plus a seen CSR.
 
 The reference has no such step (its held-out users' histories are part of the training file,
@@ -9,6 +10,7 @@ There is no CPU path: tensors must live on a ROCm device.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -30,11 +32,49 @@ def _table(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
     return t.detach().contiguous()
 
 
+ORDER_PAD = 4  # int32 entries that must be readable before and after `order` (include/bprcore.h)
+
+
+class _PaddedOrder:
+    """An `order` [d, I] that is known to have ORDER_PAD readable entries on both sides (a view into a padded
+    buffer, or the engine's own snapshot): `fold_in` passes it to the kernel without a copy."""
+
+    def __init__(self, order: torch.Tensor, keep=None) -> None:
+        self.order, self.keep = order, keep
+
+
+def _padded(order: torch.Tensor) -> _PaddedOrder:
+    buf = torch.zeros(order.numel() + 2 * ORDER_PAD, dtype=torch.int32, device=order.device)
+    view = buf[ORDER_PAD:ORDER_PAD + order.numel()].view(order.shape)
+    view.copy_(order)
+    return _PaddedOrder(view, buf)
+
+
+@torch.no_grad()
+def snapshot_of(Q: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The adaptive sampler's snapshot of an item table Q [I, d], in torch: (order [d, I] int32 — per factor every
+    item id by descending q_if, ties by ascending id (a stable descending argsort over all I rows) — and sigma [d]
+    float32, the unbiased std of the factor over rows 1..I-1).  sigma is computed the way `Engine.adaptive_refresh`
+    computes it on the device (csrc/bpr_sort_shared.h): float64 sums of c = q_if - q_1f and of c^2 over those
+    rows, sigma = sqrt(max(sum c^2 - (sum c)^2 / n, 0) / (n - 1)) with n = I - 1, rounded to float32 once."""
+    if Q.dim() != 2 or Q.dtype != torch.float32:
+        raise ValueError("Q must be float32 [I, d]")
+    if Q.shape[0] < 3:
+        raise ValueError("a snapshot needs at least two items besides the pad row")
+    order = torch.argsort(Q.detach().t().contiguous(), dim=1, descending=True, stable=True).to(torch.int32)
+    c = Q.detach()[1:].double() - Q.detach()[1].double()  # shifted by row 1: the mean's magnitude leaves the sums
+    n = float(Q.shape[0] - 1)
+    a, b = c.sum(dim=0), (c * c).sum(dim=0)
+    sigma = torch.sqrt(torch.clamp(b - a * a / n, min=0.0) / (n - 1.0)).float()
+    return order.contiguous(), sigma.contiguous()
+
+
 @torch.no_grad()
 def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Tensor, items: torch.Tensor, *,
             epochs: int, lr: float, reg_user: float = 0.0, init: Optional[torch.Tensor] = None,
             init_std: float = 0.0, seed: int = 0, offset: int = 0, neg: Optional[torch.Tensor] = None,
-            return_neg: bool = False, balance: bool = True):
+            return_neg: bool = False, balance: bool = True, sampler: str = "uniform", adaptive_p: float = 0.01,
+            snapshot: Optional[tuple] = None, return_draws: bool = False, _seen_mode: int = 0):
     """User rows P_new [n, d] for the n new users whose histories are the rows of the CSR (`indptr`
     int64 [n+1], `items` int32, sorted per row, no duplicates, ids in [1, I)), learnt by `epochs`
     sequential BPR-SGD passes over each history against the frozen `Q` [I, d] (+ `item_bias` [I]):
@@ -50,10 +90,27 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
     `return_neg=True` returns (P_new, negatives used).  Runs on the current stream, and waits for it
     TWICE before the launch: this wrapper reads the two ends of `indptr` to size and check `neg`, and
     `bpr_fold_in_rows` reads them again for its own bound (it takes no nnz argument).
+
+    `sampler="adaptive"` (`neg` must be None): the negative of a triple is `Engine.sample_adaptive`'s draw for
+    counter `offset` + that index under `seed` and `adaptive_p`, for a user whose row is the row as it stands
+    just before that triple's update and whose seen items are this history, from `snapshot` = (order [d, I]
+    int32, sigma [d] float32) of the item table; None: `snapshot_of(Q)`.  `return_draws=True` appends the
+    (factor, rank) pairs: (P_new[, negatives], factors, ranks), int32 [epochs * nnz] each.
     """
     epochs = int(epochs)
     if epochs < 1:
         raise ValueError("epochs must be at least 1")
+    if sampler not in ("uniform", "adaptive"):
+        raise ValueError("sampler must be 'uniform' or 'adaptive'")
+    adaptive = sampler == "adaptive"
+    if adaptive and neg is not None:
+        raise ValueError("given negatives (`neg`) and sampler='adaptive' exclude each other")
+    if adaptive and not 0.0 < float(adaptive_p) < 1.0:
+        raise ValueError("adaptive_p must be in (0, 1)")
+    if return_draws and not adaptive:
+        raise ValueError("return_draws needs sampler='adaptive'")
+    if snapshot is not None and not adaptive:
+        raise ValueError("snapshot needs sampler='adaptive'")
     Q, item_bias = _table(Q, "Q"), _table(item_bias, "item_bias")
     if Q.dim() != 2:
         raise ValueError("Q must be [I, d]")
@@ -78,11 +135,22 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
             raise ValueError("neg must be int32")
         if neg.numel() != epochs * nnz:
             raise ValueError(f"neg must have epochs * nnz = {epochs * nnz} entries")
+    padded = None
+    if snapshot is not None:
+        order, sigma = snapshot
+        padded = order if isinstance(order, _PaddedOrder) else None
+        order = padded.order if padded is not None else order
+        if order.dtype != torch.int32 or sigma.dtype != torch.float32:
+            raise ValueError("snapshot must be (order int32, sigma float32)")
+        if tuple(order.shape) != (d, I) or tuple(sigma.shape) != (d,):
+            raise ValueError("snapshot must be (order [d, I], sigma [d])")
     # (the shapes are checked on any device; the work is not done on any)
     if not (Q.is_cuda and indptr.is_cuda and items.is_cuda):
         raise RuntimeError("fold_in needs the item table and the histories on a ROCm device; there is no "
                            "CPU path in libbprcore")
     if any(t is not None and t.device != Q.device for t in (item_bias, indptr, items, init, neg)):
+        raise RuntimeError("fold_in needs every tensor on the device of Q")
+    if snapshot is not None and (order.device != Q.device or sigma.device != Q.device):
         raise RuntimeError("fold_in needs every tensor on the device of Q")
     lib = native.load()
     if init is not None:
@@ -98,7 +166,29 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
         used = neg
     else:
         used = torch.zeros(epochs * nnz, dtype=torch.int32, device=dev) if return_neg else None
-    if n and nnz:
+    fac = rnk = None
+    if return_draws:
+        fac = torch.zeros(epochs * nnz, dtype=torch.int32, device=dev)
+        rnk = torch.zeros(epochs * nnz, dtype=torch.int32, device=dev)
+    if adaptive and n and nnz:
+        if snapshot is None:
+            order, sigma = snapshot_of(Q)
+        if padded is None or not order.is_contiguous():
+            padded = _padded(order)
+        sigma = sigma.contiguous()
+        rows = balance_order(indptr[1:] - indptr[:-1]) if balance else None
+        fn, tail = lib.bpr_fold_in_rows_adaptive, ()
+        if _seen_mode:  # tests: the library's launch entry with the seen structure forced (1 CSR, 2 bitmap)
+            fn, tail = lib.bpr_test_fold_in_rows_adaptive, (int(_seen_mode),)
+            fn.restype, fn.argtypes = ctypes.c_int, native.SIGNATURES["bpr_fold_in_rows_adaptive"][1] + [ctypes.c_int32]
+        with torch.cuda.device(dev):
+            native.check(fn(
+                Q.data_ptr(), None if item_bias is None else item_bias.data_ptr(), I, d, padded.order.data_ptr(),
+                sigma.data_ptr(), indptr.data_ptr(), items.data_ptr(), n, None if rows is None else rows.data_ptr(),
+                epochs, float(lr), float(reg_user), float(adaptive_p), None if used is None else used.data_ptr(),
+                None if fac is None else fac.data_ptr(), None if rnk is None else rnk.data_ptr(), int(seed),
+                int(offset), P_new.data_ptr(), torch.cuda.current_stream(dev).cuda_stream, *tail))
+    elif n and nnz:
         order = balance_order(indptr[1:] - indptr[:-1]) if balance else None
         with torch.cuda.device(dev):
             native.check(lib.bpr_fold_in_rows(
@@ -108,4 +198,5 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
                 None if neg is None else neg.data_ptr(),
                 None if (neg is not None or used is None) else used.data_ptr(), int(seed), int(offset),
                 P_new.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-    return (P_new, used) if return_neg else P_new
+    out = (P_new,) + ((used,) if return_neg else ()) + ((fac, rnk) if return_draws else ())
+    return out if len(out) > 1 else P_new

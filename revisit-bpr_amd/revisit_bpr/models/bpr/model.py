@@ -501,7 +501,9 @@ class Model(torch.nn.Module):
         model's frozen item table and item bias by the engine's fold-in kernel (revisit_bpr/foldin.py holds the
         keywords); `reg_user` defaults to the model's user regularisation.  The model is not changed: the rows
         are returned, ready for `revisit_bpr.recommend.recommend` or `evaluate_topk`.  Rows behind the optimizer
-        step are replayed first (`sync()`).  Only the MF scorer has a fused form."""
+        step are replayed first (`sync()`).  Only the MF scorer has a fused form.  `sampler="adaptive"`,
+        `adaptive_p` and `refresh` are `Engine.fold_in`'s: adaptive negatives from the engine's snapshot, which
+        `refresh=True` (the default) replaces with one of the item table as it stands."""
         if not self._fusable():
             raise NotImplementedError("fold_in needs the MF logits model in float32: other scorers have no "
                                       "fold-in kernel")

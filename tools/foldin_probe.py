@@ -11,7 +11,15 @@ runs after a warm-up.
 training-side histories, and report `evaluate_topk` nDCG@100 on their held-out items beside the same users trained
 jointly with everybody else (and beside untrained rows, the floor).
 
-Usage: python tools/foldin_probe.py [--reps 5] [--skip-study] [--skip-timing] [--out profiles/foldin_probe.txt]"""
+`--sampler adaptive` answers both for adaptive negatives (`fold_in(sampler="adaptive")`, csrc/bpr_foldin_adaptive.hip):
+(i) on the same two shapes at 5 epochs, list order: the uniform kernel beside the adaptive one with its per-group LDS
+bitmap and with the CSR search forced, snapshot built once outside the timed call, and the ratio adaptive / uniform
+per triple; (ii) the same study with adaptive fold-in at `adaptive_p` 0.01 and `--study-p`, beside the uniform rows.
+The prefetch depth is a compile-time constant of the library: point BPR_LIB_PATH at a build made with
+-DBPR_FOLDIN_ADAPTIVE_PF=N and pass --label to name it in the output.
+
+Usage: python tools/foldin_probe.py [--reps 5] [--skip-study] [--skip-timing] [--sampler uniform|adaptive]
+                                    [--study-p 0.05] [--label TEXT] [--append] [--out profiles/foldin_probe.txt]"""
 import argparse
 import sys
 from pathlib import Path
@@ -24,14 +32,20 @@ sys.path[:0] = [str(ROOT), str(ROOT / "revisit-bpr_amd")]
 from revisit_bpr import engine as eng  # noqa: E402
 from revisit_bpr.datasets import synthetic  # noqa: E402
 from revisit_bpr.evaluation import evaluate_topk  # noqa: E402
-from revisit_bpr.foldin import fold_in  # noqa: E402
+from revisit_bpr.foldin import fold_in, snapshot_of  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--skip-study", action="store_true")
 ap.add_argument("--skip-timing", action="store_true")
-ap.add_argument("--out", type=str, default=str(ROOT / "profiles" / "foldin_probe.txt"))
+ap.add_argument("--sampler", choices=("uniform", "adaptive"), default="uniform")
+ap.add_argument("--study-p", type=float, default=0.05, help="second adaptive_p of the study (beside 0.01)")
+ap.add_argument("--label", type=str, default="")
+ap.add_argument("--append", action="store_true")
+ap.add_argument("--out", type=str, default=None)
 opt = ap.parse_args()
+if opt.out is None:
+    opt.out = str(ROOT / "profiles" / ("foldin_probe.txt" if opt.sampler == "uniform" else "foldin_probe_adaptive.txt"))
 dev = torch.device("cuda")
 lines = []
 
@@ -81,6 +95,34 @@ def timing():
                     f"{ms[len(ms) // 2]:10.3f}  {ms[0]:6.3f} .. {ms[-1]:6.3f} | {epochs * nnz / ms[len(ms) // 2] / 1e3:11.1f}")
             assert torch.equal(res[True], res[False])
         del Q, b, indptr, items
+
+
+def timing_adaptive():
+    say(f"(i) one fold_in call, 5 epochs, lr 0.05, reg_user 0.01, list order (balance off); adaptive_p 0.01, snapshot "
+        f"built outside the timed call; ms: median  min .. max of {opt.reps}  [{opt.label or 'library as built'}]")
+    say(f"{'shape':24s} {'nnz':>9s} {'negatives':>18s} | {'ms':>28s} | {'M triples/s':>11s} | {'x uniform':>9s}")
+    for name, I, d, median, sigma in (("ML-20M I=20109 d=128", 20_109, 128, 37.0, 1.4),
+                                      ("MSD I=41140 d=256", 41_140, 256, 30.0, 1.0)):
+        g = torch.Generator(device=dev).manual_seed(1)
+        Q = (torch.rand(I, d, device=dev, generator=g) - 0.5) / d
+        b = (torch.rand(I, device=dev, generator=g) - 0.5) / d
+        indptr, items, lens = histories(10_000, I, median, sigma, seed=2)
+        nnz, epochs = int(lens.sum()), 5
+        snap = snapshot_of(Q)  # (built once; the timed call copies `order` into its padded buffer, 4 d I bytes)
+        kw = dict(epochs=epochs, lr=0.05, reg_user=0.01, init_std=0.01, seed=3, balance=False)
+        legs = (("uniform", dict()), ("adaptive, bitmap", dict(sampler="adaptive", snapshot=snap, _seen_mode=2)),
+                ("adaptive, CSR", dict(sampler="adaptive", snapshot=snap, _seen_mode=1)))
+        base, outs = None, {}
+        for leg, extra in legs:
+            call = lambda: fold_in(Q, b, indptr, items, **kw, **extra)  # noqa: E731
+            outs[leg] = call()
+            ms = sorted(timed(call) for _ in range(opt.reps))
+            med = ms[len(ms) // 2]
+            base = med if base is None else base
+            say(f"{name:24s} {nnz:9d} {leg:>18s} | {med:10.3f}  {ms[0]:7.3f} .. {ms[-1]:7.3f} | "
+                f"{epochs * nnz / med / 1e3:11.1f} | {med / base:9.2f}")
+        assert torch.equal(outs["adaptive, bitmap"], outs["adaptive, CSR"])
+        del Q, b, indptr, items, snap
 
 
 def train(users, items, indptr, indices, U, I, d, epochs, lr, reg, seed):
@@ -142,14 +184,22 @@ def study():
     for fe in (5, 20, 60):
         Pn = fold_in(Qw, None, t(h_indptr), t(h_items), epochs=fe, lr=lr, reg_user=reg, init_std=0.1, seed=8)
         say(f"  folded in against the table trained without them, {fe:2d} epochs   {ndcg(Pn, Qw):.4f}")
+    if opt.sampler == "adaptive":
+        snap = snapshot_of(Qw)
+        for ap_ in (0.01, opt.study_p):
+            for fe in (5, 20, 60):
+                Pn = fold_in(Qw, None, t(h_indptr), t(h_items), epochs=fe, lr=lr, reg_user=reg, init_std=0.1, seed=8,
+                             sampler="adaptive", adaptive_p=ap_, snapshot=snap)
+                say(f"  folded in with ADAPTIVE negatives, adaptive_p {ap_:<5g} {fe:2d} epochs   {ndcg(Pn, Qw):.4f}")
     say(f"  untrained rows (N(0, 0.1^2)) against that table     "
         f"{ndcg(torch.randn(len(held), d, device=dev) * 0.1, Qw):.4f}")
 
 
 say(f"device {torch.cuda.get_device_name(0)}")
 if not opt.skip_timing:
-    timing()
+    timing() if opt.sampler == "uniform" else timing_adaptive()
 if not opt.skip_study:
     study()
 Path(opt.out).parent.mkdir(parents=True, exist_ok=True)
-Path(opt.out).write_text("\n".join(lines) + "\n")
+with open(opt.out, "a" if opt.append else "w") as fh:
+    fh.write("\n".join(lines) + "\n")
