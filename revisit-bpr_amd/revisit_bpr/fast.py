@@ -8,6 +8,7 @@ launch (sample negative → gather → gradient → SGD scatter).  The host ship
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
@@ -137,7 +138,9 @@ def hot_lds_rows(lr: float, launch_triples: int, world: int = 1, budget: Optiona
     With the tier a workgroup sees the OTHER workgroups' updates of those rows one launch late.  One rank: that is
     the staleness of the lagged snapshot, so the same rule — lr x 2 x launch <= LAG_BUDGET (inside at the reference
     configs' lr 0.001 and up to 0.005 for an ML-20M period, outside at 0.01 and 0.05;
-    tests/test_gpu_fullscale_reference.py gates both sides).  Several ranks: a rank never sees the other ranks'
+    tests/test_gpu_fullscale_reference.py gates both sides).  `launch_triples` is what the caller passes: a trainer
+    asks with the triples that SHARE A SNAPSHOT, not with one of the `launch_split` launches it cuts them into
+    (`resolve_schedule`: half an lr-0.01 ML-20M period reads 1,992 <= 2,000 here, and the tier stays off).  Several ranks: a rank never sees the other ranks'
     updates of a launch anyway ((N - 1) / N of them; the hot tier exchanges them after the launch); the tier makes
     that (N - 1/256) / N — priced as one more rank in the cadence's own budget: lr x (N + 1) x launch <=
     STALENESS_BUDGET (reasoned from the r4 study, not measured with the tier on)."""
@@ -155,6 +158,88 @@ def launches_per_period(lr: float, world: int, period: int, budget: Optional[flo
         return 1
     budget = STALENESS_BUDGET if budget is None else budget
     return int(min(max(math.ceil(period * lr * world / budget), 1), MAX_CHUNKS_PER_RANK_SHARE * world))
+
+
+@dataclass(frozen=True)
+class Schedule:
+    """What `resolve_schedule` answers: `period` triples of the whole job between two snapshots of the reference, cut
+    into `per_period` rank shares x refresh_split x `launch_split` launches of `chunk` triples; the snapshot's
+    `refresh_lag` and the CUs of its sort (`refresh_cus`: 0 = no masked side stream, -1 = `auto_refresh_cus` once
+    the device is known); rows of the LDS tier; `warn_lag`: an explicit refresh_lag 1 outside the one-rank budget."""
+    period: int
+    per_period: int
+    launch_split: int
+    chunk: int
+    refresh_lag: float
+    refresh_cus: int
+    hot_lds: int
+    warn_lag: bool = False
+
+
+def resolve_schedule(I: int, d: int, n: int, batch_size: int, lr: float, sampler: str = "adaptive", world: int = 1,
+                     item_sync: bool = False, cadence: str = "job", refresh_split: int = 1,
+                     launch_split: int | str = "auto", refresh_lag: float | str = "auto",
+                     refresh_cus: int | str = "auto", hot_lds: int | str = "auto") -> Schedule:
+    """The launch and snapshot schedule of a `StreamTrainer` over `n` triples, from numbers alone (no device, no
+    engine: tests/test_stream_schedule_cpu.py sweeps it).  `item_sync`: is there an item reconciliation?  Each of
+    launch_split / refresh_lag / refresh_cus / hot_lds is "auto" or the caller's value (refresh_cus "auto" beside an
+    explicit lag: -1); what is explicit is honoured or refused with a ValueError, never changed.
+
+    One rank decides by ONE staleness figure, lr x 2 x the triples that share a snapshot (`lag_within_budget`):
+      * launch_split "auto": 2 when the period is outside the budget, else 1 (1 as well with several ranks, an item
+        reconciliation, a refresh_split or an explicit lag).  Where it answers 2, everything still on "auto" is the
+        reference's schedule — refresh_lag 0, no masked sort, LDS tier off: the two launches share the period's
+        snapshot, so neither the halved launch nor a short triple list (n < period) brings the lag or the tier back.
+      * an explicit launch_split k > 1: refresh_lag "auto" is 0 (k launches of one snapshot cannot lag it) and
+        hot_lds "auto" asks `hot_lds_rows` with the k launches together.
+      * launch_split 1: the launch IS what shares the snapshot — `auto_schedule` and `hot_lds_rows` of the chunk.
+    Several ranks keep their cadence's rules (`launches_per_period`, `hot_lds_rows(world=N)`)."""
+    auto_lag = isinstance(refresh_lag, str)
+    if auto_lag and refresh_lag != "auto":
+        raise ValueError("refresh_lag must be in [0, 1] or 'auto'")
+    if not auto_lag and not 0.0 <= refresh_lag <= 1.0 or refresh_split < 1:
+        raise ValueError("refresh_lag must be in [0, 1], refresh_split >= 1")
+    adaptive = {"adaptive": True, "uniform": False}[sampler]
+    world = max(world, 1)
+    every = max(1, int(I * math.log(I) / batch_size))
+    # one refresh period = every*batch_size triples of the WHOLE job: with the users sharded
+    # over `world` ranks each rank advances 1/world of it per chunk, so the snapshot refresh
+    # and the item reconciliation keep their single-GPU cadence
+    period = every * batch_size
+    if cadence not in ("job", "rank", "auto"):
+        raise ValueError("cadence must be 'job', 'rank' or 'auto'")
+    per_period = (world if cadence == "job" else 1 if cadence == "rank" else
+                  launches_per_period(lr, world, period, STALENESS_BUDGET))
+    auto_split = isinstance(launch_split, str)
+    if auto_split:
+        if launch_split != "auto":
+            raise ValueError("launch_split must be an int >= 1 or 'auto'")
+        launch_split = 1 if (world > 1 or item_sync or refresh_split != 1 or (not auto_lag and refresh_lag != 0.0)
+                             or lag_within_budget(lr, period) or period < 2) else 2  # (a period of ONE triple: nothing to halve)
+    launch_split = max(1, int(launch_split))
+    if launch_split > 1 and (item_sync or refresh_split != 1):
+        raise ValueError("launch_split > 1: one GPU, refresh_split 1")
+    shared = period // (per_period * refresh_split)  # triples between two snapshots
+    chunk = max(1, min(shared // launch_split, n))
+    reference = auto_split and launch_split > 1  # the period is outside the one-rank budget
+    span = min(shared, chunk * launch_split)  # triples that share a snapshot (launch_split 1: the launch)
+    if isinstance(hot_lds, str):
+        hot_lds = 0 if reference else hot_lds_rows(lr, span if world == 1 else chunk, world)
+    if isinstance(refresh_cus, str):
+        if refresh_cus != "auto":
+            raise ValueError("refresh_cus must be an int or 'auto'")
+        refresh_cus = -1
+    warn_lag = False
+    if auto_lag:  # by shape and learning rate; one GPU (several ranks keep their cadence's schedule)
+        refresh_lag, refresh_cus = (auto_schedule(I, d, chunk, lr=lr)
+                                    if not item_sync and adaptive and launch_split == 1 else (0.0, 0))
+    elif refresh_lag >= 1.0 and adaptive and not item_sync and not lag_within_budget(lr, chunk):
+        warn_lag = True
+    refresh_lag = float(refresh_lag) if adaptive else 0.0
+    if refresh_lag != 0.0 and launch_split > 1:
+        raise ValueError("launch_split > 1 needs refresh_lag 0")
+    return Schedule(period, per_period, launch_split, chunk, refresh_lag, int(refresh_cus) if refresh_lag > 0.0 else 0,
+                    int(hot_lds), warn_lag)
 
 
 class StreamTrainer:
@@ -176,7 +261,7 @@ class StreamTrainer:
           refresh_split k   the period is cut into k launches and the snapshot retaken before each;
           refresh_lag       "auto": 1 with the sort on masked CUs when the shape gains from it AND the learning
                             rate keeps the older snapshot inside the staleness budget (`auto_schedule`,
-                            `lag_within_budget`), else 0.
+                            `lag_within_budget`), else 0 — always 0 where launch_split is above 1.
                             0: the snapshot is sorted between launches (the launch waits for it).
                             1: the snapshot a launch reads was cut BEFORE the previous launch and
                                sorted beside it (`adaptive_refresh_begin` / `_commit`): its age runs
@@ -218,6 +303,14 @@ class StreamTrainer:
         hot_lds: rows of the hot block a CU keeps in LDS during a launch (`bpr_set_hot_lds`; r6): "auto" =
         `hot_lds_rows` — on inside the staleness budget, off outside; 0 = off; n = asked for whatever the rate.
 
+        The single rule (`resolve_schedule`, which decides all of the above without a device): one rank has ONE
+        staleness figure, lr x 2 x the triples that share a snapshot, held against LAG_BUDGET.  Inside, one launch per
+        period, and the lagged snapshot and the LDS tier as `auto_schedule` / `hot_lds_rows` say for that launch;
+        outside, launch_split "auto" is 2 and whatever else is on "auto" is the reference's schedule (refresh_lag 0,
+        no masked sort, tier off) — the halved launch is never put to the budget again, so the defaults construct
+        at every learning rate.  Explicit values are honoured or refused (launch_split > 1 with refresh_lag != 0), an
+        explicit hot_lds = n included.
+
         async_cut (refresh_lag = 1, one GPU): the transpose of the next snapshot's keys leaves the launch stream —
         a read-only pass on the side stream beside the NEXT launch (`bpr_train_stream_acut`; r6: the fold of the
         hot block stays on the launch stream, so the LDS tier stays in use): +1.4 % on the metric's configuration,
@@ -225,13 +318,17 @@ class StreamTrainer:
         stream where the sorter has slack (tables of 2,048 .. 20,480 items)."""
         if users.dtype != torch.int32 or items.dtype != torch.int32:
             raise ValueError("users / items must be int32 device tensors")
-        auto_lag = isinstance(refresh_lag, str)
-        if auto_lag and refresh_lag != "auto":
-            raise ValueError("refresh_lag must be in [0, 1] or 'auto'")
-        if not auto_lag and not 0.0 <= refresh_lag <= 1.0 or refresh_split < 1:
-            raise ValueError("refresh_lag must be in [0, 1], refresh_split >= 1")
         self.model = model
         self.engine = model.engine()
+        I = self.engine.I
+        if world is None:
+            world = item_sync.world if item_sync is not None else 1
+        # every decision about the schedule is `resolve_schedule`'s (pure); what follows only acts on it
+        sched = resolve_schedule(I, self.engine.d, users.numel(), batch_size, lr, sampler=sampler, world=world,
+                                 item_sync=item_sync is not None, cadence=cadence, refresh_split=refresh_split,
+                                 launch_split=launch_split, refresh_lag=refresh_lag, refresh_cus=refresh_cus,
+                                 hot_lds=hot_lds)
+        self.schedule = sched
         self.users, self.items = users.contiguous(), items.contiguous()
         self.n = users.numel()
         self._users_sorted = eng.Engine.users_sorted(self.users)  # (CSR order: the plan takes one radix pass)
@@ -240,39 +337,16 @@ class StreamTrainer:
         self.engine.set_optimizer(eng.OPT_SGD, lr=lr)
         self.sampler = {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM}[sampler]
         self.adaptive_p = adaptive_p
-        I = self.engine.I
-        every = max(1, int(I * math.log(I) / batch_size))
-        # one refresh period = every*batch_size triples of the WHOLE job: with the users sharded
-        # over `world` ranks each rank advances 1/world of it per chunk, so the snapshot refresh
-        # and the item reconciliation keep their single-GPU cadence
-        if world is None:
-            world = item_sync.world if item_sync is not None else 1
-        if cadence not in ("job", "rank", "auto"):
-            raise ValueError("cadence must be 'job', 'rank' or 'auto'")
         self.cadence = cadence
-        per_period = (max(world, 1) if cadence == "job" else 1 if cadence == "rank" else
-                      launches_per_period(lr, max(world, 1), every * batch_size, STALENESS_BUDGET))
-        if isinstance(launch_split, str):
-            if launch_split != "auto":
-                raise ValueError("launch_split must be an int >= 1 or 'auto'")
-            launch_split = 1 if (max(world, 1) > 1 or refresh_split != 1 or (not auto_lag and refresh_lag != 0.0)
-                                 or lag_within_budget(lr, every * batch_size)) else 2
-        self.launch_split = max(1, int(launch_split))
-        if self.launch_split > 1 and (item_sync is not None or refresh_split != 1):
-            raise ValueError("launch_split > 1: one GPU, refresh_split 1")
-        self.chunk = max(1, min(every * batch_size // (per_period * refresh_split * self.launch_split), self.n))
+        self.launch_split, self.chunk = sched.launch_split, sched.chunk
         self.hot_split = max(1, int(hot_split))
-        self.hot_lds = hot_lds_rows(lr, self.chunk, max(world, 1)) if isinstance(hot_lds, str) else int(hot_lds)
+        self.hot_lds = sched.hot_lds
         self.engine.set_hot_lds(self.hot_lds)
         U = self.engine.U
         # staleness budget: at most ~U/4 triples in flight against one parameter cut
         self.max_inflight = max(64, U // 4) if max_inflight is None else max_inflight
         self.engine.set_stream_opts(True, run_len)
-        if auto_lag:  # by shape and learning rate; one GPU (several ranks keep their cadence's schedule)
-            refresh_lag, refresh_cus = (auto_schedule(I, self.engine.d, self.chunk, lr=lr)
-                                        if item_sync is None and self.sampler == eng.NEG_ADAPTIVE else (0.0, 0))
-        elif refresh_lag >= 1.0 and self.sampler == eng.NEG_ADAPTIVE and item_sync is None and \
-                not lag_within_budget(lr, self.chunk):
+        if sched.warn_lag:
             import warnings
 
             warnings.warn(f"refresh_lag 1 at lr {lr} with launches of {self.chunk} triples is outside the staleness "
@@ -280,9 +354,7 @@ class StreamTrainer:
                           "rising part of the curve leaves the reference's by more than 0.002 nDCG@100 "
                           "(profiles/r05_fullepoch_reference.md, r06_parity_study.md); refresh_lag='auto' picks by learning rate",
                           stacklevel=2)
-        self.refresh_lag = float(refresh_lag) if self.sampler == eng.NEG_ADAPTIVE else 0.0
-        if self.refresh_lag != 0.0 and self.launch_split > 1:
-            raise ValueError("launch_split > 1 needs refresh_lag 0")
+        self.refresh_lag, refresh_cus = sched.refresh_lag, sched.refresh_cus
         self.shard_refresh = bool(shard_refresh) and item_sync is not None and item_sync.world > 1
         if self.shard_refresh and self.refresh_lag != 0.0:
             raise ValueError("shard_refresh needs refresh_lag = 0")

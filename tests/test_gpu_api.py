@@ -565,3 +565,82 @@ def test_stream_trainer_launch_split_shares_one_snapshot_per_period(golden_dir):
     assert trainer(lr=0.5, launch_split="auto", refresh_lag=1.0).launch_split == 1
     with pytest.raises(ValueError):
         trainer(lr=0.05, launch_split=2, refresh_lag=1.0)
+
+
+def _e2e_stream_trainers(golden_dir):
+    """`trainer(**kw)` on the e2e set at d 32 as the launch-split test above builds it, the set's refresh period, and
+    the learning rates LAG_BUDGET / 2 < lr x period <= LAG_BUDGET at which the period is outside the one-rank budget
+    and half of it inside — from `fast`'s own functions; with refresh_lag "auto" the constructor used to answer
+    launch_split 2 AND refresh_lag 1 there, and refuse itself."""
+    from revisit_bpr import fast
+    from revisit_bpr.models import BPR
+    from revisit_bpr.models.bpr import MF
+
+    d = np.load(golden_dir / "e2e_data.npz")
+    U, I = int(d["num_users"]), int(d["num_items"])
+    t = {k: torch.from_numpy(d[k]).cuda() for k in ("users", "items", "indptr", "indices")}
+
+    def trainer(**kw):
+        torch.manual_seed(1)
+        model = BPR(fuse_forward=True, reg_alphas={"user": 0.001, "item": 0.001, "neg": 0.001},
+                    logits_model=MF(torch.nn.Embedding(U, 32, padding_idx=0), torch.nn.Embedding(I, 32, padding_idx=0))).cuda()
+        return fast.StreamTrainer(model, t["users"], t["items"], t["indptr"], t["indices"], sampler="adaptive",
+                                  adaptive_p=0.05, seed=3, **kw)
+
+    period = max(1, int(I * math.log(I) / 256)) * 256  # (batch_size 256: the constructor's default)
+    lo, hi = fast.LAG_BUDGET / (2 * period), fast.LAG_BUDGET / period
+    assert 0.0 < lo < hi and t["users"].numel() >= period
+    mid = (lo + hi) / 2  # about 0.14: the window is about 0.093 .. 0.186 for this set
+    assert not fast.lag_within_budget(mid, period) and fast.lag_within_budget(mid, period // 2)
+    assert fast.auto_schedule(I, 32, period // 2, lr=mid)[0] == 1.0 and fast.hot_lds_rows(mid, period // 2) > 0
+    return trainer, period, (lo, mid, hi), (I, t["users"].numel())
+
+
+def test_stream_trainer_all_auto_constructs_inside_the_window(golden_dir):
+    """Everything on "auto" (refresh_lag too: its default is the reference's 0) at a rate inside the window: two
+    launches per period of the reference's schedule — no lagged snapshot, no side stream, no LDS tier."""
+    trainer, period, (lo, mid, hi), _ = _e2e_stream_trainers(golden_dir)
+    tr = trainer(lr=mid, refresh_lag="auto")  # used to raise ValueError("launch_split > 1 needs refresh_lag 0")
+    assert tr.launch_split == 2 and tr.refresh_lag == 0.0 and tr.hot_lds == 0 and tr._side is None
+    assert tr.chunk * 2 == trainer(lr=0.05).chunk == period and not tr.async_cut
+    # the same arguments given explicitly resolve to the same trainer
+    ex = trainer(lr=mid, launch_split=2, refresh_lag=0.0, refresh_cus=0, hot_lds=0)
+    assert (ex.chunk, ex.rounds, ex.launch_split, ex.refresh_lag, ex.hot_lds) == \
+        (tr.chunk, tr.rounds, tr.launch_split, tr.refresh_lag, tr.hot_lds) and ex._side is None
+
+
+def test_stream_trainer_all_auto_epoch_inside_the_window(golden_dir):
+    """One epoch of that trainer: every triple, ONE snapshot per period (not per launch), no launch of the LDS-tier
+    kernel, a finite loss."""
+    trainer, period, (lo, mid, hi), (I, n) = _e2e_stream_trainers(golden_dir)
+    tr = trainer(lr=mid, refresh_lag="auto")
+    assert tr.rounds == -(-n // tr.chunk)
+    calls = []
+    real = tr.engine.adaptive_refresh
+    tr.engine.adaptive_refresh = lambda: (calls.append(1), real())[1]
+    stats = tr.train_epoch()
+    assert stats["triples"] == n and len(calls) == -(-tr.rounds // 2)
+    assert tr.engine.lds_launches == 0
+    assert math.isfinite(stats["loss"]) and math.isfinite(stats["bpr_loss"]) and stats["bpr_loss"] > 0.0
+
+
+def test_stream_trainer_auto_on_both_sides_of_the_window(golden_dir):
+    """One ulp below the window the period is inside the budget: one launch, lag and tier as `auto_schedule` /
+    `hot_lds_rows` say for the FULL period; one ulp above it (and, as before, at lr 0.5) two launches of the
+    reference's schedule; lr 0.05 stays one launch."""
+    from revisit_bpr import fast
+
+    trainer, period, (lo, mid, hi), (I, n) = _e2e_stream_trainers(golden_dir)
+    below, above = math.nextafter(lo, 0.0), math.nextafter(hi, math.inf)
+    assert fast.lag_within_budget(below, period) and not fast.lag_within_budget(above, period // 2)
+    for lr in (below, 0.05):
+        tr = trainer(lr=lr, refresh_lag="auto")
+        lag, cus = fast.auto_schedule(I, 32, period, lr=lr)
+        assert (tr.launch_split, tr.chunk, tr.refresh_lag, tr.hot_lds) == (1, period, lag, fast.hot_lds_rows(lr, period))
+        assert lag == 1.0 and cus > 0 and tr._side is not None and tr.hot_lds == fast.HOT_LDS_ROWS
+    for lr in (math.nextafter(lo, math.inf), hi, above, 0.5):  # the window's own two ends, and beyond
+        assert not fast.lag_within_budget(lr, period)
+        tr = trainer(lr=lr, refresh_lag="auto")
+        assert (tr.launch_split, tr.chunk, tr.refresh_lag, tr.hot_lds) == (2, period // 2, 0.0, 0) and tr._side is None
+    assert trainer(lr=0.05, launch_split="auto").launch_split == 1
+    assert trainer(lr=0.5, launch_split="auto").launch_split == 2

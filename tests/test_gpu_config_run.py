@@ -60,6 +60,42 @@ def test_config_run_learns(tmp_path, variant, mode):
         assert exp._train_mode == ("stream" if variant == "uniform-sgd-bias" else "strict")
 
 
+def test_config_run_stream_inside_the_auto_window(tmp_path):
+    """train_mode "stream" builds its StreamTrainer with refresh_lag, launch_split and hot_lds on "auto".  At a
+    learning rate with LAG_BUDGET / 2 < lr x period <= LAG_BUDGET (0.56 .. 1.1 on this set) that constructor used to
+    refuse its own choice; it runs two launches per period of the reference's schedule.  No tuned rate: the run must
+    complete, every epoch and every evaluation, with finite numbers."""
+    import math
+
+    from click.testing import CliRunner
+
+    from experiments import run as run_mod
+    from revisit_bpr import fast
+    from revisit_bpr.datasets import interactions, synthetic
+
+    data = synthetic.generate_latent(900, 320, 24000, seed=6)
+    interactions.write_dataset(data, tmp_path / "data")
+    I = data.num_items
+    period = max(1, int(I * math.log(I) / 256)) * 256
+    lo, hi = fast.LAG_BUDGET / (2 * period), fast.LAG_BUDGET / period
+    lr = (lo + hi) / 2
+    assert lo < hi and not fast.lag_within_budget(lr, period)
+    assert fast.auto_schedule(I, 32, period // 2, lr=lr)[0] == 1.0  # half a period: inside, and lag 1 pays
+    assert fast.resolve_schedule(I, 32, data.users.size, 256, lr).launch_split == 2
+    extra = (f"dataset={tmp_path / 'data'};num_users={data.num_users - 1};num_items={data.num_items - 1};"
+             f"embedding_dim=32;train_batch_size=256;epochs=2;adaptive=1;item_bias=false;lr={lr!r}")
+    res = CliRunner().invoke(run_mod.main, [str(CONFIG), "--extra-vars", extra, "-d", str(tmp_path / "exp"),
+                                            "--train-mode", "stream"],
+                             catch_exceptions=False, standalone_mode=False)
+    assert res.exit_code == 0
+    exp = res.return_value
+    evals = [r for r in exp.history if r["engine"] == "eval"]
+    trains = [r for r in exp.history if r["engine"] == "train"]
+    assert exp._train_mode == "stream" and len(evals) == 3 and len(trains) == 2
+    assert all(math.isfinite(r["bpr_loss"]) for r in trains)
+    assert all(0.0 <= r["ndcg@100"] <= 1.0 and 0.0 <= r["auc"] <= 1.0 for r in evals)
+
+
 def test_fused_evaluation_equals_the_eval_engine_loop(tmp_path):
     """r6: with whole epochs inside the library the evaluation is ONE pass too (`evaluate_topk` instead of the
     eval engine's DataLoader -> model(batch) -> 4 metric objects): the same numbers for the same model — the
