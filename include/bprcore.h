@@ -660,6 +660,48 @@ int bpr_fold_in_rows_adaptive(const float* Q, const float* item_bias /* or NULL 
                               uint64_t seed, uint64_t offset,
                               float* P_new /* [n,d] in/out */, void* hip_stream);
 
+/* ---- item fold-in: item rows (and biases) for ITEMS that enter the catalogue after training, learnt against the
+ * FROZEN user table, item table and item bias (the reference has no such step: its time-split and user-split
+ * protocols put every item into the training file).  The mirror image of bpr_fold_in_rows, with its own kernel
+ * (csrc/bpr_foldin_items.hip): every triple of a new item meets a different user, and its negative must be unseen by
+ * THAT user.  P, Q, item_bias and the seen CSR are never written.  The new items are the rows of a CSR — indptr [m+1]
+ * int64 (indptr[0] need not be 0: a slice of a larger CSR works), users int32, sorted ascending inside a row, no
+ * duplicates, ids in [0, U) — and Q_new [m, d] (with bias_new [m]) holds the caller's initial rows on entry and the
+ * learnt rows on return.  With nnz = indptr[m] - indptr[0], row r of length L takes `epochs` * L sequential SGD steps,
+ * epoch by epoch, position by position; the step of epoch e, position k has
+ *     triple index   t = e * nnz + (indptr[r] - indptr[0]) + k
+ *     user           u = users[indptr[r] + k]
+ *     negative       BPR_NEG_GIVEN: neg_in[t];  BPR_NEG_UNIFORM: exactly the item bpr_sample_uniform draws for user u
+ *                    at counter offset + t under `seed` on a context whose seen CSR is (seen_indptr [U+1],
+ *                    seen_indices) (no item weights); it is also written to neg_out[t] when neg_out is not NULL.
+ *                    Both seen pointers NULL: nothing is seen besides item 0; one NULL and one not: BPR_ERR_INVALID.
+ *                    Negatives come from the frozen table only, [1, I): a new item is never a negative.
+ *     update, fp32   x = <p_u, q - q_j> (+ b - b_j),  w = sigma(-x),  q <- q - lr (-w p_u + alpha_item q),
+ *                    b <- b + lr w   (q, b: the row being learnt; the bias has no L2, as Model.regularization has none)
+ * item_bias and bias_new are both NULL (no bias term) or both given; anything else is BPR_ERR_INVALID.
+ * SKIP RULE: a triple whose negative is 0 is skipped (q and b unchanged) — what the sampler returns for a user who has
+ * seen every item; so is one whose user lies outside [0, U) (its neg_out entry is 0) or whose given negative lies
+ * outside [1, I).  A row of length 0 keeps its initial values.  The result is a pure function of these definitions:
+ * the bits of Q_new, bias_new and neg_out do not depend on `order`, on m or the other rows, on the launch or on the
+ * kernel's prefetch depth.  order [m] int32 or NULL: as bpr_fold_in_rows' (an entry outside [0, m) is passed over).
+ * d in [1, 1024] (0: BPR_ERR_INVALID, more: BPR_ERR_UNSUPPORTED); m below 2^31; I * d, U * d and epochs * nnz below
+ * 2^31 (BPR_ERR_UNSUPPORTED); BPR_NEG_ADAPTIVE: BPR_ERR_UNSUPPORTED; NaN lr or alpha_item: BPR_ERR_INVALID.  Arguments
+ * are validated before the device is touched; m == 0 is BPR_OK.  indptr is read by the kernel only, except for ONE
+ * host read, bpr_fold_in_rows': the call copies indptr[0] and indptr[m] back for the bound on epochs * nnz and waits
+ * for `hip_stream` to do so (the launch itself is asynchronous; the call cannot be captured into a graph).  It shares
+ * bpr_fold_in_rows' ticket words.  Context-free: runs on `hip_stream` of the current device. */
+int bpr_fold_in_item_rows(const float* P, int64_t U, const float* Q, const float* item_bias /* or NULL */,
+                          int64_t I, int32_t d,
+                          const int64_t* seen_indptr /* [U+1] or NULL */, const int32_t* seen_indices,
+                          const int64_t* indptr /* [m+1] */, const int32_t* users, int64_t m,
+                          const int32_t* order /* [m] or NULL */,
+                          int32_t epochs, float lr, float alpha_item,
+                          int32_t sampler /* BPR_NEG_GIVEN | BPR_NEG_UNIFORM */,
+                          const int32_t* neg_in /* [epochs*nnz], GIVEN */, int32_t* neg_out /* [epochs*nnz] or NULL */,
+                          uint64_t seed, uint64_t offset,
+                          float* Q_new /* [m,d] in/out */, float* bias_new /* [m] in/out, or NULL */,
+                          void* hip_stream);
+
 /* ---- multi-GPU item-table reconciliation (no reference counterpart: the reference's DDP path is
  * never enabled by a config, experiments/launcher.py:35-73).  The all-reduce itself is RCCL via
  * torch.distributed; these two fused elementwise kernels bracket it (revisit_bpr/distributed.py).

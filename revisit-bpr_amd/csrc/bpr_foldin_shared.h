@@ -1,6 +1,7 @@
-// bpr_foldin_shared.h — what the two fold-in kernels (k_foldin, bpr_foldin.hip; k_foldin_adaptive,
-// bpr_foldin_adaptive.hip) have in common: the update of a user row by one triple, the shape check of their entry
-// points and the ticket words their launches hand rows out with.
+// bpr_foldin_shared.h — what the fold-in kernels have in common.  The two user fold-in kernels (k_foldin,
+// bpr_foldin.hip; k_foldin_adaptive, bpr_foldin_adaptive.hip) share the update of a user row by one triple; they and
+// the item fold-in kernel (k_foldin_items, bpr_foldin_items.hip, which has an update of its own) share the shape
+// check of their entry points and the ticket words their launches hand rows out with.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

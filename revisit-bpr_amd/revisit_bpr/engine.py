@@ -272,6 +272,34 @@ class Engine:
             kwargs["snapshot"] = (foldin._PaddedOrder(order), sigma)  # (the engine's buffer carries the slack)
         return foldin.fold_in(self.Q, self.item_bias, indptr, items, epochs=epochs, lr=lr, sampler=sampler, **kwargs)
 
+    def fold_in_items(self, indptr: torch.Tensor, users: torch.Tensor, *, epochs: int, lr: Optional[float] = None,
+                      exclude_seen: bool = True, **kwargs):
+        """Item rows (and biases, when the engine has an item bias) for NEW items (the rows of the CSR `indptr` /
+        `users`: who interacted with each) learnt against the engine's user table, item table and bias, none of
+        which is changed (`bpr_fold_in_item_rows`, see revisit_bpr/foldin_items.py for the keywords and the
+        return value).  The rows are returned, not appended: `torch.cat((engine.Q, Q_new))` and
+        `torch.cat((engine.item_bias, bias_new))` go straight into `recommend`, `rank_items` and `evaluate_*`.
+        `reg_item` defaults to the item alpha of `set_reg`, `lr` to the learning rate of `set_optimizer`.
+        `exclude_seen`: sampled negatives are unseen by the triple's user according to the CSR given to
+        `bind_seen_csr` (False, or none bound: any item but 0).  Both tables are made whole first: the hot block an
+        asynchronous cut left is folded and rows a lazy optimizer has not replayed yet are flushed."""
+        from revisit_bpr import foldin_items
+
+        if lr is None:
+            lr = getattr(self, "_lr", None)
+            if lr is None:
+                raise ValueError("fold_in_items needs `lr`: no optimizer was set on this engine")
+        kwargs.setdefault("reg_item", getattr(self, "_reg", (0.0, 0.0, 0.0))[1])
+        if "seen_indptr" in kwargs or "seen_indices" in kwargs:
+            raise ValueError("Engine.fold_in_items draws against the engine's own seen CSR")
+        if exclude_seen:
+            kwargs["seen_indptr"], kwargs["seen_indices"] = self._keep.get("csr", (None, None))
+        self.hot_fold()
+        self.flush_items()
+        self.flush_lazy()
+        return foldin_items.fold_in_items(self.P, self.Q, self.item_bias, indptr, users, epochs=epochs, lr=lr,
+                                          **kwargs)
+
     def _has_snapshot(self) -> bool:
         """True once a refresh has published a snapshot (`adaptive_snapshot()` would succeed)."""
         self._sync_stream()

@@ -514,6 +514,25 @@ class Model(torch.nn.Module):
         kwargs.setdefault("reg_user", resolve_reg_alphas(self._reg_alphas)[0])
         return eng.fold_in(indptr, items, epochs=epochs, lr=lr, **kwargs)
 
+    def fold_in_items(self, indptr: torch.Tensor, users: torch.Tensor, *, epochs: int, lr: float, **kwargs):
+        """Item rows [m, d] (and biases [m], when the model has an item bias: a pair) for NEW items (the rows of the
+        CSR `indptr` int64 / `users` int32: who interacted with each) learnt against the model's frozen user table,
+        item table and item bias by the engine's item fold-in kernel (revisit_bpr/foldin_items.py holds the
+        keywords); `reg_item` defaults to the model's item regularisation.  The model is not changed: the rows are
+        returned, and `torch.cat` of the item table (bias) with them goes straight into
+        `revisit_bpr.recommend.recommend`, `rank_items` or `evaluate_*`, where the new items have the ids I, I + 1,
+        ...  Rows behind the optimizer step are replayed first (`sync()`).  Only the MF scorer has a fused form; a
+        user bias is no obstacle (a per-user constant cancels in x)."""
+        if not self._fusable():
+            raise NotImplementedError("fold_in_items needs the MF logits model in float32: other scorers have no "
+                                      "fold-in kernel")
+        eng = self.engine()
+        self.sync()
+        from revisit_bpr.engine import resolve_reg_alphas
+
+        kwargs.setdefault("reg_item", resolve_reg_alphas(self._reg_alphas)[1])
+        return eng.fold_in_items(indptr, users, epochs=epochs, lr=lr, **kwargs)
+
     # ---- forward ----------------------------------------------------------------------------
     def forward(self, inputs: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:
         # inputs.user [B]; inputs.item, inputs.neg [B, n]
