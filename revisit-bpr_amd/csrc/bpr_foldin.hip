@@ -20,9 +20,11 @@
 // takes which row.  PF is BPR_FOLDIN_PF (bpr_foldin_plan.h).
 //
 // Work distribution.  Row lengths span three orders of magnitude, so groups take rows by an atomic ticket, in the
-// caller's `order` (longest first) when given.  The two groups of a G = 32 wave walk different rows in lockstep:
-// every cross-lane step (the DPP sum, the sampler's ballots, the ticket broadcast) runs with the whole wave active
-// and per-group predicates; a group whose row ends mid-ring idles to slot 0.
+// caller's `order` (longest first) when given: FOLDIN_NEXT_ROWS (bpr_foldin_shared.h), the loop all three fold-in
+// kernels share, with its whole-wave contract and the argument for its termination.  The two groups of a G = 32
+// wave walk different rows in lockstep: every cross-lane step (the DPP sum, the sampler's ballots, the ticket
+// broadcast) runs with the whole wave active and per-group predicates; a group whose row ends mid-ring idles to
+// slot 0.
 //
 // Nothing here writes Q or item_bias, and no index can take a load outside the tables: a positive, a given negative
 // or an `order` entry out of range skips its triple / row.
@@ -67,12 +69,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin(const FoldinArgs a) {
   const int32_t I = (int32_t)a.I;
   const int64_t base0 = a.indptr[0];
   const int64_t nnz = a.indptr[a.n] - base0;
-  bool finished = ((int64_t)blockIdx.x * FOLDIN_BLOCK + threadIdx.x) / G >= a.groups;
-
-  // the row this group holds (the same in every lane of the group)
-  int64_t row = -1, lo = 0;
-  int32_t m = 0, total = 0;  // positives of the row, triples of the row (epochs * m < 2^31, checked by the host)
-  int64_t left = 0;          // pipeline steps until the row's last update is applied: total + 2 PF may pass 2^31
+  FOLDIN_ROW_STATE(G, m, a.groups);  // the row this group holds: m positives, drained in 2 PF steps
   int32_t fc = 0, fe = 0, fj = 0;  // fetch stage: triples fetched, epoch and position of the next one
   float p[E];
 #pragma unroll
@@ -91,33 +88,9 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin(const FoldinArgs a) {
 
   for (;;) {
     // ---- ring slot 0: groups whose row is done write it back and take the next ticket
-    bool need = !finished && left == 0;
-    while (__any(need)) {
-      if (need && row >= 0) store_row<G, E>(a.P + row * d, p, d, gl);
-      uint32_t tk = 0u;
-      if (need && gl == 0) tk = atomicAdd(a.ticket, 1u);
-      tk = group_bcast<G>(tk, 0, lane);
-      if (need) {
-        row = -1;
-        m = total = 0;
-        left = 0;
-        if ((int64_t)tk >= a.n) {
-          finished = true;
-        } else {
-          const int64_t r = a.order != nullptr ? (int64_t)a.order[tk] : (int64_t)tk;
-          if (r >= 0 && r < a.n) {
-            row = r;
-            lo = a.indptr[r];
-            m = (int32_t)(a.indptr[r + 1] - lo);
-            total = a.epochs * m;
-            left = total > 0 ? (int64_t)total + 2 * PF : 0;
-            fc = fe = fj = 0;
-            load_row<G, E>(p, a.P + r * d, d, gl);
-          }
-        }
-      }
-      need = !finished && left == 0;
-    }
+    FOLDIN_NEXT_ROWS(G, m, a.ticket, a.n, a.order, a.indptr, a.epochs, 2 * PF,
+                     (store_row<G, E>(a.P + row * d, p, d, gl);),
+                     (fc = fe = fj = 0; load_row<G, E>(p, a.P + row * d, d, gl);));
     if (__all(finished)) break;
 
 #pragma unroll
@@ -140,7 +113,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin(const FoldinArgs a) {
       // ---- fetch: the next triple of the row, if it has one left
       {
         const bool valid = !finished && fc < total;
-        const int64_t t = (int64_t)fe * nnz + (lo - base0) + fj;
+        const int64_t t = FOLDIN_TRIPLE(fe, fj);
         int32_t i = 0, j = 0;
         if (valid) i = a.items[lo + fj];
         if constexpr (SAMPLED) {
@@ -160,13 +133,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin(const FoldinArgs a) {
         const bool ok = valid && i >= 1 && i < I && j >= 1 && j < I;
         fi[s] = ok ? i : 0;
         fn[s] = ok ? j : 0;
-        if (valid) {
-          ++fc;
-          if (++fj == m) {
-            fj = 0;
-            ++fe;
-          }
-        }
+        if (valid) FOLDIN_ADVANCE(fc, fe, fj, m);
       }
       left -= left > 0 ? 1 : 0;
     }
@@ -191,6 +158,27 @@ static uint32_t* g_tickets[FOLDIN_MAX_DEV];
 static unsigned g_ticket_next[FOLDIN_MAX_DEV];
 static int g_cus[FOLDIN_MAX_DEV];
 
+int foldin_check_sampler(const char* who, const char* noun, int32_t sampler) {
+  if (sampler == BPR_NEG_ADAPTIVE)
+    return fail(BPR_ERR_UNSUPPORTED, std::string(who) + ": adaptive negatives are not implemented for " + noun);
+  if (sampler != BPR_NEG_GIVEN && sampler != BPR_NEG_UNIFORM)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": unknown sampler " + std::to_string(sampler));
+  return BPR_OK;
+}
+
+int foldin_read_nnz(const char* who, const int64_t* indptr, int64_t rows, int32_t epochs, hipStream_t stream,
+                    int64_t* nnz) {
+  int64_t ends[2] = {0, 0};
+  BPR_HIP_CHECK(hipMemcpyAsync(&ends[0], indptr, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  BPR_HIP_CHECK(hipMemcpyAsync(&ends[1], indptr + rows, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  BPR_HIP_CHECK(hipStreamSynchronize(stream));
+  *nnz = ends[1] - ends[0];
+  if (ends[0] < 0 || *nnz < 0) return fail(BPR_ERR_INVALID, std::string(who) + ": indptr does not ascend");
+  if (*nnz > 0x7FFFFFFF / (int64_t)epochs)
+    return fail(BPR_ERR_UNSUPPORTED, std::string(who) + ": epochs * nnz must be below 2^31");
+  return BPR_OK;
+}
+
 int foldin_next_ticket(const char* who, uint32_t** out, int* cus) {
   int dev = 0;
   BPR_HIP_CHECK(hipGetDevice(&dev));
@@ -205,6 +193,12 @@ int foldin_next_ticket(const char* who, uint32_t** out, int* cus) {
   return BPR_OK;
 }
 
+int foldin_begin(const char* who, hipStream_t stream, uint32_t** ticket, int* cus) {
+  if (int rc = foldin_next_ticket(who, ticket, cus)) return rc;
+  BPR_HIP_CHECK(hipMemsetAsync(*ticket, 0, sizeof(uint32_t), stream));
+  return BPR_OK;
+}
+
 }  // namespace bpr
 
 extern "C" int bpr_fold_in_rows(const float* Q, const float* item_bias, int64_t I, int32_t d, const int64_t* indptr,
@@ -212,12 +206,10 @@ extern "C" int bpr_fold_in_rows(const float* Q, const float* item_bias, int64_t 
                                 float alpha_user, int32_t sampler, const int32_t* neg_in, int32_t* neg_out,
                                 uint64_t seed, uint64_t offset, float* P_new, void* hip_stream) {
   using namespace bpr;
-  if (int rc = foldin_check_shape("bpr_fold_in_rows", n, I, d)) return rc;
+  const char* who = "bpr_fold_in_rows";
+  if (int rc = foldin_check_shape(who, n, I, d)) return rc;
   if (epochs < 1) return fail(BPR_ERR_INVALID, "bpr_fold_in_rows: epochs must be at least 1");
-  if (sampler == BPR_NEG_ADAPTIVE)
-    return fail(BPR_ERR_UNSUPPORTED, "bpr_fold_in_rows: adaptive negatives are not implemented for fold-in");
-  if (sampler != BPR_NEG_GIVEN && sampler != BPR_NEG_UNIFORM)
-    return fail(BPR_ERR_INVALID, "bpr_fold_in_rows: unknown sampler " + std::to_string(sampler));
+  if (int rc = foldin_check_sampler(who, "fold-in", sampler)) return rc;
   if (!(lr == lr) || !(alpha_user == alpha_user))
     return fail(BPR_ERR_INVALID, "bpr_fold_in_rows: lr or alpha_user is NaN");
   if (n == 0) return BPR_OK;
@@ -227,21 +219,13 @@ extern "C" int bpr_fold_in_rows(const float* Q, const float* item_bias, int64_t 
     return fail(BPR_ERR_INVALID, "bpr_fold_in_rows: sampler BPR_NEG_GIVEN needs neg_in");
 
   hipStream_t stream = (hipStream_t)hip_stream;
-  // the one host read: the first and the last entry of indptr, for the 2^31 bound on the triple counter
-  int64_t ends[2] = {0, 0};
-  BPR_HIP_CHECK(hipMemcpyAsync(&ends[0], indptr, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-  BPR_HIP_CHECK(hipMemcpyAsync(&ends[1], indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-  BPR_HIP_CHECK(hipStreamSynchronize(stream));
-  const int64_t nnz = ends[1] - ends[0];
-  if (ends[0] < 0 || nnz < 0) return fail(BPR_ERR_INVALID, "bpr_fold_in_rows: indptr does not ascend");
-  if (nnz > 0x7FFFFFFF / (int64_t)epochs)
-    return fail(BPR_ERR_UNSUPPORTED, "bpr_fold_in_rows: epochs * nnz must be below 2^31");
+  int64_t nnz = 0;
+  if (int rc = foldin_read_nnz(who, indptr, n, epochs, stream, &nnz)) return rc;
   if (nnz == 0) return BPR_OK;
 
   uint32_t* ticket = nullptr;
   int cus = FOLDIN_CUS;
-  if (int rc = foldin_next_ticket("bpr_fold_in_rows", &ticket, &cus)) return rc;
-  BPR_HIP_CHECK(hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream));
+  if (int rc = foldin_begin(who, stream, &ticket, &cus)) return rc;
   const FoldinPlan p = plan_foldin(n, d, cus);
   FoldinArgs a = {};
   a.Q = Q; a.bias = item_bias; a.I = I; a.d = d; a.indptr = indptr; a.items = items; a.n = n; a.order = order;

@@ -5,7 +5,8 @@
 //
 // Shape of the problem.  An adaptive negative depends on the live row, so the draw of triple t + 1 comes after the
 // update of triple t: unlike k_foldin, only the model-independent half of a triple can run ahead.  One group of G
-// lanes owns one row at a time (rows by atomic ticket, the row in registers from its first triple to its last) and
+// lanes owns one row at a time (rows by atomic ticket: FOLDIN_NEXT_ROWS, bpr_foldin_shared.h, the loop all three
+// fold-in kernels share; the row in registers from its first triple to its last) and
 // keeps a ring of PF static slots with, per triple fetched ahead: the positive's id, its row q_i and bias b_i, and
 // the triple's AdaptiveRandoms (seed, counter and the row's length only).  A step of the ring, slot s:
 //   consume  the triple fetched PF steps ago:  sample_adaptive(p, ...) -> load q_j, b_j -> foldin_update
@@ -24,19 +25,12 @@
 // ballot, scan and broadcast inside sample_adaptive / adaptive_walk / foldin_update must run with the whole wave
 // active.  So the sampler is called under `__any(consume)`, a condition the whole wave agrees on, and a group with
 // nothing to draw (ring still filling, row finished, group out of tickets, or a row with nothing unseen) takes a
-// DUMMY draw: an empty seen row and geometric rank 1.  Why neither loop can hang:
-//  - adaptive_walk: its for-loop is bounded by `base < I` whatever the lanes see, so it ends after at most
-//    ceil(I / 4G) trips; `__all(done)` is only the early exit.  A dummy draw skips 0 unseen entries of an empty
-//    seen row, so it is done in the first trip that holds a non-pad entry and never prolongs the real draw next to
-//    it by more than that.  A real draw's rank is below the row's unseen count, so it is done inside the column.
-//    With I == 1 nobody has anything unseen and sample_adaptive walks nothing, uniformly.
-//  - the ticket loop `while (__any(need))`: a group with `need` takes a ticket in every trip; the ticket either
-//    gives it a row with triples (left > 0: need drops), or is past the list (finished: need drops), or names an
-//    empty / out-of-range row and the next trip takes another ticket.  Tickets only grow and the list is finite, so
-//    every group reaches `finished` after at most n + groups tickets in all.  `left` falls by one per step while
-//    positive, so a group comes back to the ticket loop after total + PF steps, rounded up to the ring's PF.
-//  - the outer loop ends on `__all(finished)`, evaluated by the whole wave right after the ticket loop, where no
-//    lane is masked off; lanes beyond the launch's groups start `finished`.
+// DUMMY draw: an empty seen row and geometric rank 1.  Why adaptive_walk cannot hang (the ticket loop and the outer
+// loop: see FOLDIN_NEXT_ROWS): its for-loop is bounded by `base < I` whatever the lanes see, so it ends after at
+// most ceil(I / 4G) trips; `__all(done)` is only the early exit.  A dummy draw skips 0 unseen entries of an empty
+// seen row, so it is done in the first trip that holds a non-pad entry and never prolongs the real draw next to it
+// by more than that.  A real draw's rank is below the row's unseen count, so it is done inside the column.  With
+// I == 1 nobody has anything unseen and sample_adaptive walks nothing, uniformly.
 //
 // Nothing here writes Q, item_bias, order or sigma, and no index becomes an address unchecked: a positive outside
 // [1, I) skips its triple, a drawn item outside [1, I) likewise, a row_order entry outside [0, n) is passed over,
@@ -107,6 +101,23 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// The group's bitmap BM of the row it has just taken (items [lo, lo + m) of ITEMS), built once for the row's
+// epochs * m walks.  A macro for the reason FOLDIN_NEXT_ROWS is one (a function changes the kernel's schedule); it
+// names the kernel's `lo`, `m` and `gl`, and runs under the group's own predicate.
+#define FOLDIN_BUILD_BITMAP(LANES, BM, WORDS, ITEMS, NUM_ITEMS)                                                   \
+  do {                                                                                                            \
+    uint4* bm4 = reinterpret_cast<uint4*>(BM);                                                                    \
+    for (int k = gl; k < ((WORDS) >> 2); k += (LANES)) bm4[k] = make_uint4(0u, 0u, 0u, 0u);                       \
+    wave_lds_sync();                                                                                              \
+    for (int32_t k = gl; k < m; k += 8 * (LANES)) {                                                               \
+      int32_t it[8];                                                                                              \
+      _Pragma("unroll") for (int q = 0; q < 8; ++q) it[q] = k + q * (LANES) < m ? (ITEMS)[lo + k + q * (LANES)] : -1; \
+      _Pragma("unroll") for (int q = 0; q < 8; ++q)                                                               \
+        if ((uint32_t)it[q] < (uint32_t)(NUM_ITEMS)) atomicOr(&(BM)[it[q] >> 5], 1u << (it[q] & 31));             \
+    }                                                                                                             \
+    wave_lds_sync();                                                                                              \
+  } while (0)
+
 template <int G, int E, bool BM, int PF>
 __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_adaptive(const FoldinAdaptiveArgs a) {
   const int lane = threadIdx.x & 63;
@@ -115,17 +126,13 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_adaptive(const FoldinAd
   const int32_t I = (int32_t)a.I;
   const int64_t base0 = a.indptr[0];
   const int64_t nnz = a.indptr[a.n] - base0;
-  bool finished = ((int64_t)blockIdx.x * FOLDIN_BLOCK + threadIdx.x) / G >= a.groups;
   uint32_t* const bm = BM ? reinterpret_cast<uint32_t*>(foldin_adaptive_smem) + (threadIdx.x / G) * a.bm_words
                           : nullptr;
 
   float sg[E];  // the snapshot's sigma, in the row layout
   load_row<G, E>(sg, a.sigma, d, gl);
 
-  // the row this group holds (the same in every lane of the group)
-  int64_t row = -1, lo = 0;
-  int32_t m = 0, total = 0;        // positives of the row, triples of the row (epochs * m < 2^31, checked by the host)
-  int64_t left = 0;                // steps until the row's last update is applied: total + PF may pass 2^31
+  FOLDIN_ROW_STATE(G, m, a.groups);  // the row this group holds: m positives, drained in PF steps
   int32_t fc = 0, fe = 0, fj = 0;  // fetch: triples fetched, epoch and position of the next one
   int32_t ce = 0, cj = 0;          // consume: epoch and position of the next one
   float p[E];
@@ -147,49 +154,10 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_adaptive(const FoldinAd
 
   for (;;) {
     // ---- ring slot 0: groups whose row is done write it back and take the next ticket
-    bool need = !finished && left == 0;
-    while (__any(need)) {
-      if (need && row >= 0) store_row<G, E>(a.P + row * d, p, d, gl);
-      uint32_t tk = 0u;
-      if (need && gl == 0) tk = atomicAdd(a.ticket, 1u);
-      tk = group_bcast<G>(tk, 0, lane);
-      if (need) {
-        row = -1;
-        m = total = 0;
-        left = 0;
-        if ((int64_t)tk >= a.n) {
-          finished = true;
-        } else {
-          const int64_t r = a.row_order != nullptr ? (int64_t)a.row_order[tk] : (int64_t)tk;
-          if (r >= 0 && r < a.n) {
-            row = r;
-            lo = a.indptr[r];
-            m = (int32_t)(a.indptr[r + 1] - lo);
-            total = a.epochs * m;
-            left = total > 0 ? (int64_t)total + PF : 0;
-            fc = fe = fj = ce = cj = 0;
-            load_row<G, E>(p, a.P + r * d, d, gl);
-            if constexpr (BM) {
-              if (total > 0) {  // the row's bitmap, once for its epochs * m walks
-                uint4* bm4 = reinterpret_cast<uint4*>(bm);
-                for (int k = gl; k < (a.bm_words >> 2); k += G) bm4[k] = make_uint4(0u, 0u, 0u, 0u);
-                wave_lds_sync();
-                for (int32_t k = gl; k < m; k += 8 * G) {
-                  int32_t it[8];
-#pragma unroll
-                  for (int q = 0; q < 8; ++q) it[q] = k + q * G < m ? a.items[lo + k + q * G] : -1;
-#pragma unroll
-                  for (int q = 0; q < 8; ++q)
-                    if ((uint32_t)it[q] < (uint32_t)I) atomicOr(&bm[it[q] >> 5], 1u << (it[q] & 31));
-                }
-                wave_lds_sync();
-              }
-            }
-          }
-        }
-      }
-      need = !finished && left == 0;
-    }
+    FOLDIN_NEXT_ROWS(
+        G, m, a.ticket, a.n, a.row_order, a.indptr, a.epochs, PF, (store_row<G, E>(a.P + row * d, p, d, gl);),
+        (fc = fe = fj = ce = cj = 0; load_row<G, E>(p, a.P + row * d, d, gl);
+         if constexpr (BM) { if (total > 0) FOLDIN_BUILD_BITMAP(G, bm, a.bm_words, a.items, I); }));
     if (__all(finished)) break;
 
     const int32_t n_unseen = (I - 1) - m;  // of the row held (m <= I - 1 for a CSR that keeps its contract)
@@ -212,7 +180,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_adaptive(const FoldinAd
           const int32_t i = si[s];
           const int32_t j = real ? dr.item : 0;
           if (cv && gl == 0) {
-            const int64_t t = (int64_t)ce * nnz + (lo - base0) + cj;
+            const int64_t t = FOLDIN_TRIPLE(ce, cj);
             if (a.neg_out != nullptr) a.neg_out[t] = j;
             if (a.factor_out != nullptr) a.factor_out[t] = dr.factor;
             // (a row with nothing unseen: the rank sample_adaptive reports for r = 0)
@@ -242,7 +210,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_adaptive(const FoldinAd
         i = (i >= 1 && i < I) ? i : 0;
         si[s] = i;
         if (valid) {
-          const int64_t t = (int64_t)fe * nnz + (lo - base0) + fj;
+          const int64_t t = FOLDIN_TRIPLE(fe, fj);
           const AdaptiveRandoms rnd = adaptive_randoms(a.seed, a.offset + (uint64_t)t, a.inv_log1mp, (int64_t)n_unseen);
           su[s] = rnd.uf;
           sr[s] = rnd.r;
@@ -250,11 +218,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_adaptive(const FoldinAd
             load_row<G, E>(qi[s], a.Q + (uint32_t)i * (uint32_t)d, d, gl);
             bi[s] = a.bias != nullptr ? a.bias[i] : 0.f;
           }
-          ++fc;
-          if (++fj == m) {
-            fj = 0;
-            ++fe;
-          }
+          FOLDIN_ADVANCE(fc, fe, fj, m);
         }
       }
       left -= left > 0 ? 1 : 0;
@@ -285,20 +249,13 @@ static int fold_in_rows_adaptive_impl(const char* who, const float* Q, const flo
   if (!order || !sigma) return fail(BPR_ERR_INVALID, w + ": snapshot order or sigma is NULL");
 
   hipStream_t stream = (hipStream_t)hip_stream;
-  // the one host read: the first and the last entry of indptr, for the 2^31 bound on the triple counter
-  int64_t ends[2] = {0, 0};
-  BPR_HIP_CHECK(hipMemcpyAsync(&ends[0], indptr, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-  BPR_HIP_CHECK(hipMemcpyAsync(&ends[1], indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-  BPR_HIP_CHECK(hipStreamSynchronize(stream));
-  const int64_t nnz = ends[1] - ends[0];
-  if (ends[0] < 0 || nnz < 0) return fail(BPR_ERR_INVALID, w + ": indptr does not ascend");
-  if (nnz > 0x7FFFFFFF / (int64_t)epochs) return fail(BPR_ERR_UNSUPPORTED, w + ": epochs * nnz must be below 2^31");
+  int64_t nnz = 0;
+  if (int rc = foldin_read_nnz(who, indptr, n, epochs, stream, &nnz)) return rc;
   if (nnz == 0) return BPR_OK;
 
   uint32_t* ticket = nullptr;
   int cus = FOLDIN_CUS;
-  if (int rc = foldin_next_ticket(who, &ticket, &cus)) return rc;
-  BPR_HIP_CHECK(hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream));
+  if (int rc = foldin_begin(who, stream, &ticket, &cus)) return rc;
   const FoldinAdaptivePlan pl = plan_foldin_adaptive(n, I, d, cus, seen_mode);
   FoldinAdaptiveArgs a = {};
   a.Q = Q; a.bias = item_bias; a.I = I; a.d = d; a.order = order; a.sigma = sigma; a.indptr = indptr; a.items = items;

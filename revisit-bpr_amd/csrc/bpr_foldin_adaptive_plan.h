@@ -28,9 +28,7 @@ constexpr int64_t FOLDIN_ADAPTIVE_LDS_CU = 160 * 1024;  // LDS of a CU (CDNA4)
 #define BPR_FOLDIN_ADAPTIVE_PF 4
 #endif
 constexpr int FOLDIN_ADAPTIVE_PF = BPR_FOLDIN_ADAPTIVE_PF;
-constexpr int foldin_adaptive_pf(int E) {
-  return E <= 4 ? FOLDIN_ADAPTIVE_PF : std::max(1, FOLDIN_ADAPTIVE_PF * 4 / E);
-}
+constexpr int foldin_adaptive_pf(int E) { return foldin_pf_at(FOLDIN_ADAPTIVE_PF, E); }
 
 enum { FOLDIN_SEEN_AUTO = 0, FOLDIN_SEEN_CSR = 1, FOLDIN_SEEN_BITMAP = 2 };  // seen_mode (tests force 1 or 2)
 
@@ -61,9 +59,7 @@ inline FoldinAdaptivePlan plan_foldin_adaptive(int64_t n, int64_t I, int d, int 
   p.lds_bytes = p.bitmap ? bytes : 0;
   p.resident = p.bitmap ? (int)std::min<int64_t>(FOLDIN_RESIDENT, FOLDIN_ADAPTIVE_LDS_CU / p.lds_bytes)
                         : FOLDIN_RESIDENT;
-  const int64_t cap = (int64_t)std::max(cus, 1) * p.resident * p.groups_per_block;
-  p.groups = std::min<int64_t>(n, cap);
-  p.grid = (p.groups + p.groups_per_block - 1) / p.groups_per_block;
+  foldin_groups_grid(n, cus, p.resident, p.groups_per_block, &p.groups, &p.grid);
   return p;
 }
 

@@ -24,9 +24,10 @@
 // pipeline at ring slot 0 and drains through 3 PF further steps; slots past the row's end carry "no triple".  The
 // stages of a triple are the same whatever PF is and the updates of a row are applied in triple order by one group,
 // so the result does not depend on PF, on the grid, or on which group takes which row.  PF is BPR_FOLDIN_ITEMS_PF
-// (below).
+// (bpr_foldin_plan.h).
 //
-// Work distribution and wave-uniform control are k_foldin's: rows by atomic ticket, in the caller's `order` when
+// Work distribution and wave-uniform control are the shared skeleton's (FOLDIN_NEXT_ROWS, bpr_foldin_shared.h, with
+// its whole-wave contract and the argument for its termination): rows by atomic ticket, in the caller's `order` when
 // given; the two groups of a G = 32 wave walk different rows in lockstep, every cross-lane step (the DPP sum, the
 // sampler's ballots, the ticket broadcast) runs with the whole wave active and per-group predicates, and a group with
 // nothing to draw searches an empty row.
@@ -36,7 +37,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include <algorithm>
 #include <string>
 
 #include "bpr_device.h"
@@ -44,17 +44,7 @@
 #include "bpr_foldin_shared.h"
 #include "bpr_host.h"
 
-// Triples in flight per stage (E <= 4; halved per doubling of E past 4, as foldin_pf: the rings live in VGPRs).  The
-// default is k_foldin's measured choice; no other depth of THIS kernel has been measured.
-#ifndef BPR_FOLDIN_ITEMS_PF
-#define BPR_FOLDIN_ITEMS_PF BPR_FOLDIN_PF
-#endif
-
 namespace bpr {
-
-constexpr int foldin_items_pf(int E) {
-  return E <= 4 ? BPR_FOLDIN_ITEMS_PF : std::max(1, BPR_FOLDIN_ITEMS_PF * 4 / E);
-}
 
 struct FoldinItemsArgs {
   const float* P;
@@ -112,12 +102,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_items(const FoldinItems
   const int32_t I = (int32_t)a.I, U = (int32_t)a.U;
   const int64_t base0 = a.indptr[0];
   const int64_t nnz = a.indptr[a.m] - base0;
-  bool finished = ((int64_t)blockIdx.x * FOLDIN_BLOCK + threadIdx.x) / G >= a.groups;
-
-  // the row this group holds (the same in every lane of the group)
-  int64_t row = -1, lo = 0;
-  int32_t len = 0, total = 0;  // users of the row, triples of the row (epochs * len < 2^31, checked by the host)
-  int64_t left = 0;            // pipeline steps until the row's last update is applied: total + 3 PF may pass 2^31
+  FOLDIN_ROW_STATE(G, len, a.groups);  // the row this group holds: len users, drained in 3 PF steps
   int32_t fc = 0, fe = 0, fk = 0;  // ids stage: triples fetched, epoch and position of the next one
   float q[E], b = 0.f;
 #pragma unroll
@@ -141,37 +126,10 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_items(const FoldinItems
 
   for (;;) {
     // ---- ring slot 0: groups whose row is done write it back and take the next ticket
-    bool need = !finished && left == 0;
-    while (__any(need)) {
-      if (need && row >= 0) {
-        store_row<G, E>(a.Qn + row * d, q, d, gl);
-        if (a.bn != nullptr && gl == 0) a.bn[row] = b;
-      }
-      uint32_t tk = 0u;
-      if (need && gl == 0) tk = atomicAdd(a.ticket, 1u);
-      tk = group_bcast<G>(tk, 0, lane);
-      if (need) {
-        row = -1;
-        len = total = 0;
-        left = 0;
-        if ((int64_t)tk >= a.m) {
-          finished = true;
-        } else {
-          const int64_t r = a.order != nullptr ? (int64_t)a.order[tk] : (int64_t)tk;
-          if (r >= 0 && r < a.m) {
-            row = r;
-            lo = a.indptr[r];
-            len = (int32_t)(a.indptr[r + 1] - lo);
-            total = a.epochs * len;
-            left = total > 0 ? (int64_t)total + 3 * PF : 0;
-            fc = fe = fk = 0;
-            load_row<G, E>(q, a.Qn + r * d, d, gl);
-            b = a.bn != nullptr ? a.bn[r] : 0.f;
-          }
-        }
-      }
-      need = !finished && left == 0;
-    }
+    FOLDIN_NEXT_ROWS(G, len, a.ticket, a.m, a.order, a.indptr, a.epochs, 3 * PF,
+                     (store_row<G, E>(a.Qn + row * d, q, d, gl); if (a.bn != nullptr && gl == 0) a.bn[row] = b;),
+                     (fc = fe = fk = 0; load_row<G, E>(q, a.Qn + row * d, d, gl);
+                      b = a.bn != nullptr ? a.bn[row] : 0.f;));
     if (__all(finished)) break;
 
 #pragma unroll
@@ -224,7 +182,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_items(const FoldinItems
       // ---- ids: the next triple of the row, if it has one left
       {
         const bool valid = !finished && fc < total;
-        const int64_t t = (int64_t)fe * nnz + (lo - base0) + fk;  // < epochs * nnz < 2^31
+        const int64_t t = FOLDIN_TRIPLE(fe, fk);  // < epochs * nnz < 2^31
         int32_t u = 0, x = 0;
         if (valid) u = a.users[lo + fk];
         // an id outside its table never becomes an address: the triple is skipped
@@ -238,13 +196,7 @@ __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_items(const FoldinItems
         }
         fu[s] = ok ? u : (valid ? BAD_USER : NO_TRIPLE);
         fx[s] = x;
-        if (valid) {
-          ++fc;
-          if (++fk == len) {
-            fk = 0;
-            ++fe;
-          }
-        }
+        if (valid) FOLDIN_ADVANCE(fc, fe, fk, len);
       }
       left -= left > 0 ? 1 : 0;
     }
@@ -266,10 +218,7 @@ extern "C" int bpr_fold_in_item_rows(const float* P, int64_t U, const float* Q, 
   if (U < 1) return fail(BPR_ERR_INVALID, who + ": U must be at least 1");
   if (U * (int64_t)d > 0x7FFFFFFF) return fail(BPR_ERR_UNSUPPORTED, who + ": U * d must be below 2^31");
   if (epochs < 1) return fail(BPR_ERR_INVALID, who + ": epochs must be at least 1");
-  if (sampler == BPR_NEG_ADAPTIVE)
-    return fail(BPR_ERR_UNSUPPORTED, who + ": adaptive negatives are not implemented for item fold-in");
-  if (sampler != BPR_NEG_GIVEN && sampler != BPR_NEG_UNIFORM)
-    return fail(BPR_ERR_INVALID, who + ": unknown sampler " + std::to_string(sampler));
+  if (int rc = foldin_check_sampler(who.c_str(), "item fold-in", sampler)) return rc;
   if (!(lr == lr) || !(alpha_item == alpha_item)) return fail(BPR_ERR_INVALID, who + ": lr or alpha_item is NaN");
   if ((item_bias == nullptr) != (bias_new == nullptr))
     return fail(BPR_ERR_INVALID, who + ": item_bias and bias_new must both be given or both be NULL");
@@ -281,20 +230,13 @@ extern "C" int bpr_fold_in_item_rows(const float* P, int64_t U, const float* Q, 
   if (sampler == BPR_NEG_GIVEN && !neg_in) return fail(BPR_ERR_INVALID, who + ": sampler BPR_NEG_GIVEN needs neg_in");
 
   hipStream_t stream = (hipStream_t)hip_stream;
-  // the one host read: the first and the last entry of indptr, for the 2^31 bound on the triple counter
-  int64_t ends[2] = {0, 0};
-  BPR_HIP_CHECK(hipMemcpyAsync(&ends[0], indptr, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-  BPR_HIP_CHECK(hipMemcpyAsync(&ends[1], indptr + m, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-  BPR_HIP_CHECK(hipStreamSynchronize(stream));
-  const int64_t nnz = ends[1] - ends[0];
-  if (ends[0] < 0 || nnz < 0) return fail(BPR_ERR_INVALID, who + ": indptr does not ascend");
-  if (nnz > 0x7FFFFFFF / (int64_t)epochs) return fail(BPR_ERR_UNSUPPORTED, who + ": epochs * nnz must be below 2^31");
+  int64_t nnz = 0;
+  if (int rc = foldin_read_nnz(who.c_str(), indptr, m, epochs, stream, &nnz)) return rc;
   if (nnz == 0) return BPR_OK;
 
   uint32_t* ticket = nullptr;
   int cus = FOLDIN_CUS;
-  if (int rc = foldin_next_ticket(who.c_str(), &ticket, &cus)) return rc;
-  BPR_HIP_CHECK(hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream));
+  if (int rc = foldin_begin(who.c_str(), stream, &ticket, &cus)) return rc;
   const FoldinPlan p = plan_foldin(m, d, cus);  // one group per row, rows by ticket: k_foldin's layout
   FoldinItemsArgs a = {};
   a.P = P; a.Q = Q; a.bias = item_bias; a.U = U; a.I = I; a.d = d; a.seen_indptr = seen_indptr;

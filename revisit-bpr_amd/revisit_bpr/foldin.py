@@ -32,6 +32,53 @@ def _table(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
     return t.detach().contiguous()
 
 
+def _check_csr(indptr: torch.Tensor, idx: torch.Tensor, idx_name: str, rows_name: str) -> None:
+    if indptr.dtype != torch.int64 or idx.dtype != torch.int32:
+        raise ValueError(f"indptr must be int64 and {idx_name} int32")
+    if indptr.dim() != 1 or indptr.numel() < 1:
+        raise ValueError(f"indptr must have {rows_name}+1 entries")
+
+
+def _rows_csr(indptr: torch.Tensor, idx: torch.Tensor, idx_name: str):
+    """The CSR of a fold-in call (already through `_check_csr`): (indptr, idx) contiguous, the number of rows and
+    nnz — from the one host read of this wrapper, the two ends of `indptr`."""
+    indptr, idx = indptr.contiguous(), idx.reshape(-1).contiguous()
+    n = indptr.numel() - 1
+    first, last = (int(v) for v in indptr[[0, n]].tolist())
+    nnz = last - first
+    if first < 0 or nnz < 0 or last > idx.numel():
+        raise ValueError(f"indptr does not describe rows of `{idx_name}`")
+    return indptr, idx, n, nnz
+
+
+def _check_neg(neg, epochs: int, nnz: int) -> None:
+    if neg is not None:
+        if neg.dtype != torch.int32:
+            raise ValueError("neg must be int32")
+        if neg.numel() != epochs * nnz:
+            raise ValueError(f"neg must have epochs * nnz = {epochs * nnz} entries")
+
+
+def _initial_rows(init, init_std: float, seed: int, n: int, d: int, dev) -> torch.Tensor:
+    """The rows a fold-in starts from: a copy of `init`, else N(0, init_std^2) from a generator seeded by `seed`,
+    else zeros."""
+    if init is not None:
+        return init.detach().clone().contiguous()
+    if init_std:
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        return torch.randn((n, d), generator=gen, device=dev, dtype=torch.float32) * float(init_std)
+    return torch.zeros((n, d), dtype=torch.float32, device=dev)
+
+
+def _neg_buffers(neg, epochs: int, nnz: int, return_neg: bool, dev):
+    """(neg flattened or None, the buffer of negatives used: `neg` itself, a new one to return, or None)."""
+    if neg is not None:
+        neg = neg.reshape(-1).contiguous()
+        return neg, neg
+    return None, (torch.zeros(epochs * nnz, dtype=torch.int32, device=dev) if return_neg else None)
+
+
 ORDER_PAD = 4  # int32 entries that must be readable before and after `order` (include/bprcore.h)
 
 
@@ -117,24 +164,12 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
     I, d = Q.shape
     if item_bias is not None and item_bias.numel() != I:
         raise ValueError("item_bias must have one entry per item row")
-    if indptr.dtype != torch.int64 or items.dtype != torch.int32:
-        raise ValueError("indptr must be int64 and items int32")
-    if indptr.dim() != 1 or indptr.numel() < 1:
-        raise ValueError("indptr must have n+1 entries")
-    indptr, items = indptr.contiguous(), items.reshape(-1).contiguous()
-    n = indptr.numel() - 1
+    _check_csr(indptr, items, "items", "n")
+    indptr, items, n, nnz = _rows_csr(indptr, items, "items")
     dev = Q.device
-    first, last = (int(v) for v in indptr[[0, n]].tolist())
-    nnz = last - first
-    if first < 0 or nnz < 0 or last > items.numel():
-        raise ValueError("indptr does not describe rows of `items`")
     if init is not None and (init.dtype != torch.float32 or tuple(init.shape) != (n, d)):
         raise ValueError("init must be float32 [n, d]")
-    if neg is not None:
-        if neg.dtype != torch.int32:
-            raise ValueError("neg must be int32")
-        if neg.numel() != epochs * nnz:
-            raise ValueError(f"neg must have epochs * nnz = {epochs * nnz} entries")
+    _check_neg(neg, epochs, nnz)
     padded = None
     if snapshot is not None:
         order, sigma = snapshot
@@ -153,19 +188,8 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
     if snapshot is not None and (order.device != Q.device or sigma.device != Q.device):
         raise RuntimeError("fold_in needs every tensor on the device of Q")
     lib = native.load()
-    if init is not None:
-        P_new = init.detach().clone().contiguous()
-    elif init_std:
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(int(seed))
-        P_new = torch.randn((n, d), generator=gen, device=dev, dtype=torch.float32) * float(init_std)
-    else:
-        P_new = torch.zeros((n, d), dtype=torch.float32, device=dev)
-    if neg is not None:
-        neg = neg.reshape(-1).contiguous()
-        used = neg
-    else:
-        used = torch.zeros(epochs * nnz, dtype=torch.int32, device=dev) if return_neg else None
+    P_new = _initial_rows(init, init_std, seed, n, d, dev)
+    neg, used = _neg_buffers(neg, epochs, nnz, return_neg, dev)
     fac = rnk = None
     if return_draws:
         fac = torch.zeros(epochs * nnz, dtype=torch.int32, device=dev)

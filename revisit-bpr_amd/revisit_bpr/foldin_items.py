@@ -17,7 +17,7 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
-from revisit_bpr.foldin import _table, balance_order
+from revisit_bpr.foldin import _check_csr, _check_neg, _initial_rows, _neg_buffers, _rows_csr, _table, balance_order
 
 
 @torch.no_grad()
@@ -57,10 +57,7 @@ def fold_in_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Te
     (U, d), I = P.shape, Q.shape[0]
     if item_bias is not None and item_bias.numel() != I:
         raise ValueError("item_bias must have one entry per item row")
-    if indptr.dtype != torch.int64 or users.dtype != torch.int32:
-        raise ValueError("indptr must be int64 and users int32")
-    if indptr.dim() != 1 or indptr.numel() < 1:
-        raise ValueError("indptr must have m+1 entries")
+    _check_csr(indptr, users, "users", "m")
     if (seen_indptr is None) != (seen_indices is None):
         raise ValueError("seen_indptr and seen_indices must both be given or both be None")
     if seen_indptr is not None:
@@ -69,13 +66,8 @@ def fold_in_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Te
         if seen_indptr.dim() != 1 or seen_indptr.numel() != U + 1:
             raise ValueError("seen_indptr must have U+1 entries")
         seen_indptr, seen_indices = seen_indptr.contiguous(), seen_indices.reshape(-1).contiguous()
-    indptr, users = indptr.contiguous(), users.reshape(-1).contiguous()
-    m = indptr.numel() - 1
+    indptr, users, m, nnz = _rows_csr(indptr, users, "users")
     dev = Q.device
-    first, last = (int(v) for v in indptr[[0, m]].tolist())
-    nnz = last - first
-    if first < 0 or nnz < 0 or last > users.numel():
-        raise ValueError("indptr does not describe rows of `users`")
     if init is not None and (init.dtype != torch.float32 or tuple(init.shape) != (m, d)):
         raise ValueError("init must be float32 [m, d]")
     if init_bias is not None:
@@ -83,11 +75,7 @@ def fold_in_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Te
             raise ValueError("init_bias needs item_bias")
         if init_bias.dtype != torch.float32 or tuple(init_bias.shape) != (m,):
             raise ValueError("init_bias must be float32 [m]")
-    if neg is not None:
-        if neg.dtype != torch.int32:
-            raise ValueError("neg must be int32")
-        if neg.numel() != epochs * nnz:
-            raise ValueError(f"neg must have epochs * nnz = {epochs * nnz} entries")
+    _check_neg(neg, epochs, nnz)
     # (the shapes are checked on any device; the work is not done on any)
     if not (P.is_cuda and Q.is_cuda and indptr.is_cuda and users.is_cuda):
         raise RuntimeError("fold_in_items needs the tables and the audiences on a ROCm device; there is no "
@@ -98,23 +86,12 @@ def fold_in_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Te
     if seen_indices is not None and seen_indices.numel() == 0:
         seen_indptr = seen_indices = None  # (an empty tensor has no address: nothing is seen either way)
     lib = native.load()
-    if init is not None:
-        Q_new = init.detach().clone().contiguous()
-    elif init_std:
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(int(seed))
-        Q_new = torch.randn((m, d), generator=gen, device=dev, dtype=torch.float32) * float(init_std)
-    else:
-        Q_new = torch.zeros((m, d), dtype=torch.float32, device=dev)
+    Q_new = _initial_rows(init, init_std, seed, m, d, dev)
     bias_new = None
     if item_bias is not None:
         bias_new = (init_bias.detach().clone().contiguous() if init_bias is not None
                     else torch.zeros(m, dtype=torch.float32, device=dev))
-    if neg is not None:
-        neg = neg.reshape(-1).contiguous()
-        used = neg
-    else:
-        used = torch.zeros(epochs * nnz, dtype=torch.int32, device=dev) if return_neg else None
+    neg, used = _neg_buffers(neg, epochs, nnz, return_neg, dev)
     if m and nnz:
         order = balance_order(indptr[1:] - indptr[:-1]) if balance else None
         with torch.cuda.device(dev):
