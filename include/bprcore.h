@@ -702,6 +702,53 @@ int bpr_fold_in_item_rows(const float* P, int64_t U, const float* Q, const float
                           float* Q_new /* [m,d] in/out */, float* bias_new /* [m] in/out, or NULL */,
                           void* hip_stream);
 
+/* ---- neighbours: the k rows of a table most similar to each of a list of query rows ("items like this one",
+ * "users like this one"; the reference has no such call).  One fused kernel (csrc/bpr_neighbors.hip) with
+ * bpr_topk_rows' tiling and selection, and no [n, N] buffer anywhere.  Query r is the row X[rows[r]] ([*, d] fp32
+ * row-major; X may be T itself or another table of the same d, e.g. freshly folded-in rows), the table is T [N, d].
+ *
+ * Scores.  dot(x, t) is the fp32 fmaf chain of bpr_topk_rows over the features in its fixed order (per 8 features:
+ * 0, 4, 1, 5, 2, 6, 3, 7, from 0.0f), without a bias.
+ *   BPR_SIM_DOT     s(r, j) = dot(X[rows[r]], T[j]).  With X = P, exclude = NULL and first = 1 the output equals
+ *                   bpr_topk_rows' without a bias and without a seen CSR, bit for bit.
+ *   BPR_SIM_COSINE  ss(v) = dot(v, v): ONE fp32 chain ss = fmaf(v_f, v_f, ss) from 0.0f over the d features in
+ *                   dot's order (per 8 features: 0, 4, 1, 5, 2, 6, 3, 7).
+ *                   rn(v) = 1.0f / sqrt(ss(v)): the IEEE-754 correctly rounded fp32 square root, then the correctly
+ *                   rounded fp32 division (CUDA's __fdiv_rn(1.0f, __fsqrt_rn(ss)); numpy's float32 arithmetic).
+ *                   s(r, j) = (dot(x, t) * rn(t)) * rn(x): two fp32 multiplications in that order.
+ *                   A pre-pass kernel writes rn of the N table rows and the n queries into the workspace on every
+ *                   call; nothing is cached between calls.
+ * Eligibility.  Row j of T is eligible for query r if first <= j < N, j != exclude[r] (exclude NULL or exclude[r] <
+ * 0: no row is left out) and, under cosine, ss(T[j]) > 0 (a NaN fails that comparison, so a row with a NaN is never
+ * returned; so is an all-zero row.  Under BPR_SIM_DOT a zero row is eligible, with score 0).  Under cosine a query with
+ * !(ss > 0) gets a fully padded row.
+ * Output.  ids_out / scores_out [n, k]: the eligible rows sorted by score descending, ties by ascending id; a query
+ * with fewer than k eligible rows ends in id -1 / score -inf.  A NaN score is never better than anything (it can be
+ * returned only where rows run out, in no defined order among NaNs).
+ * The result is a pure function of the inputs: its bits do not depend on n, on a query's place in the list (which may
+ * repeat rows) or on item_slices (0 = the library chooses; s > 1 cuts the table over s workgroups per query tile, for
+ * lists too short to fill the chip, and needs the workspace).  d in [1, 1024], 1 <= k <= 128, item_slices in [0, 64],
+ * N in [1, 2^31), n < 2^31, first >= 0, a known metric: anything else is BPR_ERR_INVALID.  `rows` are not checked
+ * against X.  Arguments are validated before the device is touched; n == 0 is BPR_OK.  Context-free: runs on
+ * `hip_stream` of the current device. */
+#define BPR_SIM_DOT 0
+#define BPR_SIM_COSINE 1
+/* bytes of device workspace bpr_neighbors_rows needs for this shape: the slices' partial results as
+ * bpr_topk_workspace counts them (0 with one slice; with s slices s * n * k * 8; item_slices 0: never less than for a
+ * smaller n), plus (N + n) * 4 under BPR_SIM_COSINE */
+int bpr_neighbors_workspace(int64_t n, int64_t N, int32_t d, int32_t k, int32_t metric, int32_t item_slices,
+                            int64_t* bytes_host);
+/* the slice count a call of this shape runs with (as bpr_topk_slices: passing it back as item_slices makes
+ * bpr_neighbors_workspace answer exactly that call's need) */
+int bpr_neighbors_slices(int64_t n, int64_t N, int32_t d, int32_t k, int32_t item_slices, int32_t* slices_host);
+int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int32_t d,
+                       const int32_t* rows, int64_t n,           /* query r is X[rows[r]] */
+                       const int32_t* exclude /* [n] or NULL */, /* id of T left out of row r; < 0: none */
+                       int32_t first,                            /* ids of T below `first` are never returned */
+                       int32_t metric, int32_t k, int32_t item_slices /* 0 = choose */,
+                       void* workspace, int64_t workspace_bytes,
+                       int32_t* ids_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
+
 /* ---- multi-GPU item-table reconciliation (no reference counterpart: the reference's DDP path is
  * never enabled by a config, experiments/launcher.py:35-73).  The all-reduce itself is RCCL via
  * torch.distributed; these two fused elementwise kernels bracket it (revisit_bpr/distributed.py).

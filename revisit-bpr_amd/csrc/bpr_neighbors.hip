@@ -1,0 +1,493 @@
+// bpr_neighbors.hip — fused neighbour search of libbprcore: the k rows of a table T most similar to each of a list
+// of query rows X[rows[r]], by dot product or cosine, with no [n, N] score matrix anywhere (bpr_neighbors_rows /
+// bpr_neighbors_workspace / bpr_neighbors_slices; the definition is the comment in include/bprcore.h).
+//
+// The kernel has k_topk's structure (bpr_topk.hip, which explains it at length): 256 threads own 64 queries and
+// stream the table past them 128 rows x 32 features at a time through LDS into exact f32 MFMA accumulators
+// (v_mfma_f32_32x32x2_f32: table rows on the A side, queries on the B side, so a lane's 16 results are 16 table
+// rows of ONE query); every query keeps in LDS a threshold tau = its k-th best at the last compaction, a buffer of
+// k + 128 candidates and a count; after a table tile (A) every lane counts its eligible scores that beat tau, (B) a
+// query whose buffer could overflow is compacted by one wave to its k best, sorted, (C) what still beats the
+// tightened tau is appended.  The dot product is k_topk's fmaf chain, bit for bit.
+//
+// What differs from k_topk:
+//   - queries are gathered through `rows` from X, which need not be the table;
+//   - the per-query LDS state carries the excluded id and the query's reciprocal norm instead of a seen row;
+//   - under the cosine metric the reciprocal norms of the table tile travel with the tile's first chunk (global ->
+//     register -> LDS), and the two multiplications are applied to the accumulator before the tau compare;
+//   - eligibility is two integer compares and one float compare on values the lane already holds, so it is part
+//     of (A)'s mask: (C) touches no global memory, where k_topk's (C) runs a binary search in the seen CSR per
+//     candidate.  profiles/similar_probe.txt measures what that is worth.
+//
+// Cosine pre-pass (k_neighbors_norms): one thread per row folds v_f * v_f into ONE fmaf chain from 0 over the
+// features in the dot product's own order (per 8 features 0, 4, 1, 5, 2, 6, 3, 7), so ss(v) == dot(v, v) bit for
+// bit and a row meets its own copy at (ss * rn) * rn, six roundings from 1; rn = 1 / sqrt(ss), both correctly
+// rounded, is stored if ss > 0, the marker -1 otherwise (a zero row, or one with a NaN): such a table row is never
+// returned, such a query gets a padded row.  The norms of the N table rows and the n queries are written on every
+// call.
+// Correct rounding is spelt sqrtf and `/` here, and the Makefile pins -fhip-fp32-correctly-rounded-divide-sqrt for
+// this object: HIP's __fsqrt_rn is the hardware's approximate square root (1 ulp) unless the headers are built
+// with OCML_BASIC_ROUNDED_OPERATIONS, whose __ocml_sqrt_rte_f32 / __ocml_div_rte_f32 the device library of this
+// toolchain does not carry, and its __fdiv_rn is `/`.  tests/test_gpu_similar.py holds the bits to numpy's IEEE
+// float32, so a build that rounds otherwise fails there.
+//
+// Cand, better, compact_row, load4 and the merge kernel are private copies of bpr_topk.hip's (DESIGN 4.10 says why
+// they are not shared); they live in their own namespace.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <string.h>
+
+#include <string>
+
+#include "bpr_host.h"
+#include "bpr_neighbors_plan.h"
+
+namespace bpr {
+namespace nbr {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct Cand {
+  float s;
+  int32_t i;
+};
+
+struct NeighborsArgs {
+  const float* X;
+  const float* T;
+  int64_t N;
+  int d;
+  const int32_t* rows;
+  int64_t n;
+  const int32_t* exclude;  // [n] or nullptr
+  int first;
+  const float* rn_t;  // [N], cosine only
+  const float* rn_x;  // [n], cosine only
+  int k, slices;
+  int64_t tiles;
+  float* out_scores;  // [n, slices, k]
+  int32_t* out_ids;   // [n, slices, k]
+};
+
+// the order of the result: score descending, ties by ascending id (never true for a NaN score)
+__device__ __forceinline__ bool better(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
+
+// One wave: the c <= k + TOPK_TI <= 256 candidates of a query -> its min(c, k) best, sorted, in buf[0 ..); tau and
+// count follow.  Every lane of the wave calls it with the same arguments.
+__device__ __forceinline__ void compact_row(Cand* buf, int c, int k, int lane, Cand* tau, int* cnt) {
+  Cand e[4];
+  int rank[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int idx = lane + 64 * q;
+    e[q] = idx < c ? buf[idx] : Cand{0.0f, 0};
+    rank[q] = 0;
+  }
+  for (int j = 0; j < c; ++j) {
+    const Cand o = buf[j];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) rank[q] += better(o.s, o.i, e[q].s, e[q].i) ? 1 : 0;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (lane + 64 * q < c && rank[q] < k) {
+      buf[rank[q]] = e[q];
+      if (rank[q] == k - 1) *tau = e[q];
+    }
+  }
+  if (lane == 0) *cnt = c < k ? c : k;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <bool VEC>
+__device__ __forceinline__ float4 load4(const float* __restrict__ row, int kk, int d) {
+  if (VEC) return kk < d ? *reinterpret_cast<const float4*>(row + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 v;
+  v.x = kk + 0 < d ? row[kk + 0] : 0.f;
+  v.y = kk + 1 < d ? row[kk + 1] : 0.f;
+  v.z = kk + 2 < d ? row[kk + 2] : 0.f;
+  v.w = kk + 3 < d ? row[kk + 3] : 0.f;
+  return v;
+}
+
+// rn of the N table rows, then of the n queries: one thread per row (the order of the chain: the head of this file;
+// features past d are read as zeros, and fmaf(0, 0, ss) == ss)
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_neighbors_norms(const float* __restrict__ T, int64_t N,
+                                                         const float* __restrict__ X,
+                                                         const int32_t* __restrict__ rows, int64_t n, int d,
+                                                         float* __restrict__ rn_t, float* __restrict__ rn_x) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const float* src;
+  float* dst;
+  if (g < N) {
+    src = T + g * d;
+    dst = rn_t + g;
+  } else if (g - N < n) {
+    src = X + (int64_t)rows[g - N] * d;
+    dst = rn_x + (g - N);
+  } else {
+    return;
+  }
+  float ss = 0.f;
+  for (int f = 0; f < d; f += 8) {
+    const float4 lo = load4<VEC>(src, f, d), hi = load4<VEC>(src, f + 4, d);
+    ss = __fmaf_rn(lo.x, lo.x, ss);
+    ss = __fmaf_rn(hi.x, hi.x, ss);
+    ss = __fmaf_rn(lo.y, lo.y, ss);
+    ss = __fmaf_rn(hi.y, hi.y, ss);
+    ss = __fmaf_rn(lo.z, lo.z, ss);
+    ss = __fmaf_rn(hi.z, hi.z, ss);
+    ss = __fmaf_rn(lo.w, lo.w, ss);
+    ss = __fmaf_rn(hi.w, hi.w, ss);
+  }
+  *dst = ss > 0.f ? 1.0f / sqrtf(ss) : -1.0f;  // (correctly rounded: the head of this file)
+}
+
+// VEC: d % 4 == 0 and 16-byte aligned tables (16-byte global loads); else element loads.  COS: cosine metric.
+template <bool VEC, bool COS>
+__global__ __launch_bounds__(256) void k_neighbors(const NeighborsArgs a) {
+  constexpr int TU = TOPK_TU, TI = TOPK_TI, KC = TOPK_KC, LD = TOPK_LD;
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int cap = a.k + TI;
+  float* const sT = reinterpret_cast<float*>(smem);          // [TI][LD]
+  float* const sX = sT + TI * LD;                            // [TU][LD]
+  float* const sRnT = sX + TU * LD;                          // [TI]
+  Cand* const sBuf = reinterpret_cast<Cand*>(sRnT + TI);     // [TU][cap]
+  Cand* const sTau = sBuf + TU * cap;                        // [TU]
+  int* const sCnt = reinterpret_cast<int*>(sTau + TU);
+  int* const sNeed = sCnt + TU;
+  int* const sRow = sNeed + TU;
+  int* const sExcl = sRow + TU;
+  float* const sRnX = reinterpret_cast<float*>(sExcl + TU);
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+  const int64_t u0 = (int64_t)blockIdx.x * TU;
+  const int slice = blockIdx.y;
+  const int64_t t0 = a.tiles * slice / a.slices, t1 = a.tiles * (slice + 1) / a.slices;
+
+  if (tid < TU) {
+    const int64_t q = u0 + tid;
+    const bool live = q < a.n;
+    const float rx = COS && live ? a.rn_x[q] : 1.0f;
+    sRow[tid] = live ? a.rows[q] : -1;
+    sExcl[tid] = live && a.exclude != nullptr ? a.exclude[q] : -1;
+    sRnX[tid] = rx;
+    sCnt[tid] = 0;
+    sNeed[tid] = 0;
+    // nothing kept yet: everything beats tau; a query past n, or (cosine) without a norm: nothing does
+    sTau[tid] = live && rx >= 0.f ? Cand{-INFINITY, INT_MAX} : Cand{INFINITY, -1};
+  }
+  __syncthreads();
+
+  // the next chunk travels global -> registers while the current one is multiplied, then registers -> LDS
+  float4 treg[4], xreg[2];
+  float rnreg = 0.f;
+  auto fetch = [&](int64_t t, int c) {
+    const int kc = c * KC;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
+      const int64_t j = t * TI + row;
+      treg[m] = j < a.N ? load4<VEC>(a.T + j * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
+      const int u = sRow[row];
+      xreg[m] = u >= 0 ? load4<VEC>(a.X + (int64_t)u * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (COS && c == 0 && tid < TI) {
+      const int64_t j = t * TI + tid;
+      rnreg = j < a.N ? a.rn_t[j] : -1.0f;
+    }
+  };
+  auto stash = [&](int c) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int f = tid + 256 * m;
+      *reinterpret_cast<float4*>(sT + (f >> 3) * LD + 4 * (f & 7)) = treg[m];
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int f = tid + 256 * m;
+      *reinterpret_cast<float4*>(sX + (f >> 3) * LD + 4 * (f & 7)) = xreg[m];
+    }
+    // (read in (A) of this tile only, which a barrier separates from the next tile's first stash)
+    if (COS && c == 0 && tid < TI) sRnT[tid] = rnreg;
+  };
+
+  const int nch = (a.d + KC - 1) / KC;
+  const float* const ta = sT + (32 * w + r) * LD + 4 * h;
+  const float* const xb0 = sX + r * LD + 4 * h;
+  const float* const xb1 = sX + (32 + r) * LD + 4 * h;
+  if (t0 < t1) fetch(t0, 0);
+  for (int64_t t = t0; t < t1; ++t) {
+    f32x16 acc0 = {0.f}, acc1 = {0.f};
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.f;
+    for (int c = 0; c < nch; ++c) {
+      __syncthreads();
+      stash(c);
+      __syncthreads();
+      if (c + 1 < nch) fetch(t, c + 1);
+      else if (t + 1 < t1) fetch(t + 1, 0);
+#pragma unroll
+      for (int blk = 0; blk < KC / 8; ++blk) {
+        const float4 a4 = *reinterpret_cast<const float4*>(ta + 8 * blk);
+        const float4 b0 = *reinterpret_cast<const float4*>(xb0 + 8 * blk);
+        const float4 b1 = *reinterpret_cast<const float4*>(xb1 + 8 * blk);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b0.x, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b1.x, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b0.y, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b1.y, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b0.z, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b1.z, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b0.w, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b1.w, acc1, 0, 0, 0);
+      }
+    }
+
+    // ---- epilogue of the tile: register q of the lane is table row jbase + (q & 3) + 8 (q >> 2) of queries r, 32 + r
+    const int64_t jbase = t * TI + 32 * w + 4 * h;
+    // (A) the eligible scores that beat the query's threshold; under cosine the accumulators become the scores
+    unsigned m0 = 0, m1 = 0;
+    {
+      const Cand tau0 = sTau[r], tau1 = sTau[32 + r];
+      const int ex0 = sExcl[r], ex1 = sExcl[32 + r];
+      const float rx0 = sRnX[r], rx1 = sRnX[32 + r];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int jl = 32 * w + 4 * h + (q & 3) + 8 * (q >> 2);
+        const int64_t j = t * TI + jl;
+        bool ok = j >= a.first && j < a.N;
+        if (COS) {
+          const float rt = sRnT[jl];
+          ok = ok && rt >= 0.f;
+          acc0[q] = __fmul_rn(__fmul_rn(acc0[q], rt), rx0);
+          acc1[q] = __fmul_rn(__fmul_rn(acc1[q], rt), rx1);
+        }
+        if (ok && (int)j != ex0 && better(acc0[q], (int)j, tau0.s, tau0.i)) m0 |= 1u << q;
+        if (ok && (int)j != ex1 && better(acc1[q], (int)j, tau1.s, tau1.i)) m1 |= 1u << q;
+      }
+      if (m0) atomicAdd(&sNeed[r], __popc(m0));
+      if (m1) atomicAdd(&sNeed[32 + r], __popc(m1));
+    }
+    __syncthreads();
+    // (B) queries whose buffer might not take them all: down to the k best (then count <= k, and a tile adds <= TI)
+    for (int row = w; row < TU; row += 4) {
+      const int c = min(sCnt[row], cap);
+      if (c + sNeed[row] > cap) compact_row(sBuf + row * cap, c, a.k, lane, &sTau[row], &sCnt[row]);
+    }
+    __syncthreads();
+    // (C) append what still beats the threshold: no global memory is touched
+    if (tid < TU) sNeed[tid] = 0;
+    if (m0 | m1) {
+      const Cand tau0 = sTau[r], tau1 = sTau[32 + r];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int j = (int)(jbase + (q & 3) + 8 * (q >> 2));
+        if (((m0 >> q) & 1u) && better(acc0[q], j, tau0.s, tau0.i)) {
+          const int pos = atomicAdd(&sCnt[r], 1);
+          if (pos < cap) sBuf[r * cap + pos] = Cand{acc0[q], j};
+        }
+        if (((m1 >> q) & 1u) && better(acc1[q], j, tau1.s, tau1.i)) {
+          const int pos = atomicAdd(&sCnt[32 + r], 1);
+          if (pos < cap) sBuf[(32 + r) * cap + pos] = Cand{acc1[q], j};
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- the slice's result: every query sorted, padded with (-inf, -1)
+  for (int row = w; row < TU; row += 4) {
+    if (u0 + row >= a.n) break;
+    const int c = min(sCnt[row], cap);
+    Cand* const buf = sBuf + row * cap;
+    if (c > 0) compact_row(buf, c, a.k, lane, &sTau[row], &sCnt[row]);
+    const int have = c < a.k ? c : a.k;
+    const int64_t out = ((u0 + row) * a.slices + slice) * a.k;
+    for (int j = lane; j < a.k; j += 64) {
+      const Cand e = j < have ? buf[j] : Cand{-INFINITY, -1};
+      a.out_scores[out + j] = e.s;
+      a.out_ids[out + j] = e.i;
+    }
+  }
+}
+
+// One workgroup per query: S sorted lists of k (padded with id -1 at the end) -> the k best, sorted.
+__global__ __launch_bounds__(256) void k_neighbors_merge(const float* __restrict__ ps, const int32_t* __restrict__ pi,
+                                                         int S, int k, float* __restrict__ out_s,
+                                                         int32_t* __restrict__ out_i) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  Cand* const sE = reinterpret_cast<Cand*>(smem);  // [S][k]
+  int* const sLen = reinterpret_cast<int*>(sE + S * k);
+  const int tid = threadIdx.x;
+  const int64_t row = blockIdx.x;
+  const int64_t base = row * S * k;
+  if (tid < S) sLen[tid] = 0;
+  __syncthreads();
+  for (int e = tid; e < S * k; e += 256) {
+    const Cand c = {ps[base + e], pi[base + e]};
+    sE[e] = c;
+    if (c.i >= 0) atomicAdd(&sLen[e / k], 1);
+  }
+  __syncthreads();
+  int total = 0;
+  for (int s = 0; s < S; ++s) total += sLen[s];
+  for (int e = tid; e < S * k; e += 256) {
+    const int s = e / k, j = e - s * k;
+    if (j >= sLen[s]) continue;
+    const Cand c = sE[e];
+    int rank = j;
+    for (int b = 0; b < S && rank < k; ++b) {
+      if (b == s) continue;
+      const Cand* const L = sE + b * k;
+      int lo = 0, hi = sLen[b];  // entries of list b that come before c
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (better(L[mid].s, L[mid].i, c.s, c.i)) lo = mid + 1; else hi = mid;
+      }
+      rank += lo;
+    }
+    if (rank < k) {
+      out_s[row * k + rank] = c.s;
+      out_i[row * k + rank] = c.i;
+    }
+  }
+  for (int j = (total < k ? total : k) + tid; j < k; j += 256) {
+    out_s[row * k + j] = -INFINITY;
+    out_i[row * k + j] = -1;
+  }
+}
+
+static int check_shape(const char* who, int64_t n, int64_t N, int32_t d, int32_t k, int32_t item_slices) {
+  if (n < 0 || N < 1 || N >= ((int64_t)1 << 31))
+    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be >= 0 and N in [1, 2^31)");
+  if (d < 1 || d > 1024) return fail(BPR_ERR_INVALID, std::string(who) + ": d must be in [1, 1024]");
+  if (k < 1 || k > TOPK_MAX)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": k must be in [1, " + std::to_string(TOPK_MAX) + "]");
+  if (item_slices < 0 || item_slices > TOPK_MAX_SLICES)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": item_slices must be 0 (choose) or in [1, " +
+                                     std::to_string(TOPK_MAX_SLICES) + "]");
+  if (n > 0x7FFFFFFF)  // (the merge kernel's grid is one workgroup per query)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be below 2^31");
+  return BPR_OK;
+}
+
+static int check_metric(const char* who, int32_t metric) {
+  if (metric != NBR_DOT && metric != NBR_COSINE)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": metric must be BPR_SIM_DOT (0) or BPR_SIM_COSINE (1)");
+  return BPR_OK;
+}
+
+template <bool VEC, bool COS>
+static int launch(const NeighborsArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
+  // one workgroup may ask for most of a CU's LDS: past 64 KiB that is a per-function attribute (set on every
+  // call: the process may hold several devices, and the call costs nothing next to a launch)
+  BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_neighbors<VEC, COS>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)neighbors_lds_bytes(TOPK_MAX)));
+  hipLaunchKernelGGL((k_neighbors<VEC, COS>), grid, dim3(256), lds, stream, a);
+  BPR_HIP_CHECK(hipGetLastError());
+  return BPR_OK;
+}
+
+}  // namespace nbr
+}  // namespace bpr
+
+extern "C" int bpr_neighbors_workspace(int64_t n, int64_t N, int32_t d, int32_t k, int32_t metric,
+                                       int32_t item_slices, int64_t* bytes_host) {
+  using namespace bpr;
+  if (bytes_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_neighbors_workspace: bytes_host is NULL");
+  if (int rc = nbr::check_shape("bpr_neighbors_workspace", n, N, d, k, item_slices)) return rc;
+  if (int rc = nbr::check_metric("bpr_neighbors_workspace", metric)) return rc;
+  *bytes_host = neighbors_workspace_bytes(n, N, k, metric, item_slices);
+  return BPR_OK;
+}
+
+extern "C" int bpr_neighbors_slices(int64_t n, int64_t N, int32_t d, int32_t k, int32_t item_slices,
+                                    int32_t* slices_host) {
+  using namespace bpr;
+  if (slices_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_neighbors_slices: slices_host is NULL");
+  if (int rc = nbr::check_shape("bpr_neighbors_slices", n, N, d, k, item_slices)) return rc;
+  *slices_host = plan_neighbors(n, N, k, NBR_DOT, item_slices).t.slices;
+  return BPR_OK;
+}
+
+extern "C" int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int32_t d, const int32_t* rows, int64_t n,
+                                  const int32_t* exclude, int32_t first, int32_t metric, int32_t k,
+                                  int32_t item_slices, void* workspace, int64_t workspace_bytes, int32_t* ids_out,
+                                  float* scores_out, void* hip_stream) {
+  using namespace bpr;
+  using namespace bpr::nbr;
+  if (int rc = check_shape("bpr_neighbors_rows", n, N, d, k, item_slices)) return rc;
+  if (int rc = check_metric("bpr_neighbors_rows", metric)) return rc;
+  if (first < 0) return fail(BPR_ERR_INVALID, "bpr_neighbors_rows: first must be >= 0");
+  if (n > 0 && (!X || !T || !rows || !ids_out || !scores_out))
+    return fail(BPR_ERR_INVALID, "bpr_neighbors_rows: X, T, rows, ids_out or scores_out is NULL");
+  const NeighborsPlan p = plan_neighbors(n, N, k, metric, item_slices);
+  if (p.ws_bytes > 0 && (workspace == nullptr || workspace_bytes < p.ws_bytes))
+    return fail(BPR_ERR_INVALID, "bpr_neighbors_rows: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                     std::to_string(p.ws_bytes) + " needed (bpr_neighbors_workspace)");
+  if (n == 0) return BPR_OK;
+
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const int S = p.t.slices;
+  NeighborsArgs a = {};
+  a.X = X; a.T = T; a.N = N; a.d = d; a.rows = rows; a.n = n; a.exclude = exclude; a.first = first;
+  a.k = k; a.slices = S; a.tiles = p.t.item_tiles;
+  // workspace: the slices' partial scores, their ids, then (cosine) rn of the table rows and of the queries
+  float* part_s = reinterpret_cast<float*>(workspace);
+  int32_t* part_i = reinterpret_cast<int32_t*>(part_s + (S > 1 ? n * (int64_t)S * k : 0));
+  a.out_scores = S > 1 ? part_s : scores_out;
+  a.out_ids = S > 1 ? part_i : ids_out;
+  const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(T)) % 16 == 0;
+  if (metric == NBR_COSINE) {
+    float* rn_t = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + p.partial_bytes);
+    float* rn_x = rn_t + N;
+    a.rn_t = rn_t;
+    a.rn_x = rn_x;
+    const int64_t blocks = (N + n + 255) / 256;  // < 2^24
+    if (vec) hipLaunchKernelGGL(k_neighbors_norms<true>, dim3((unsigned)blocks), dim3(256), 0, stream, T, N, X, rows, n,
+                                (int)d, rn_t, rn_x);
+    else hipLaunchKernelGGL(k_neighbors_norms<false>, dim3((unsigned)blocks), dim3(256), 0, stream, T, N, X, rows, n,
+                            (int)d, rn_t, rn_x);
+    BPR_HIP_CHECK(hipGetLastError());
+  }
+  const dim3 grid((unsigned)p.t.user_tiles, (unsigned)S);
+  int rc;
+  if (metric == NBR_COSINE) rc = vec ? launch<true, true>(a, grid, p.lds, stream) : launch<false, true>(a, grid, p.lds, stream);
+  else rc = vec ? launch<true, false>(a, grid, p.lds, stream) : launch<false, false>(a, grid, p.lds, stream);
+  if (rc != BPR_OK) return rc;
+  if (S > 1) {
+    hipLaunchKernelGGL(k_neighbors_merge, dim3((unsigned)n), dim3(256), p.t.merge_lds, stream, part_s, part_i, S, k,
+                       scores_out, ids_out);
+    BPR_HIP_CHECK(hipGetLastError());
+  }
+  return BPR_OK;
+}
+
+// Test hook, not API (tests/test_neighbors_cpu.py sets its signature): the plan of a shape.  in = {n, N, d, k,
+// metric, item_slices, cus}; out = {slices, query_tiles, table_tiles, tile_queries, tile_rows, cap, lds, lds_limit,
+// merge_lds, partial_bytes, norm_bytes, ws_bytes}; bounds[0 .. slices] = first table row of each slice, then N.
+// Needs no GPU.
+extern "C" int bpr_test_neighbors_plan(const int64_t* in, int64_t* out, int64_t* bounds) {
+  using namespace bpr;
+  if (int rc = nbr::check_shape("bpr_test_neighbors_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3],
+                                (int32_t)in[5]))
+    return rc;
+  if (int rc = nbr::check_metric("bpr_test_neighbors_plan", (int32_t)in[4])) return rc;
+  const NeighborsPlan p = plan_neighbors(in[0], in[1], (int)in[3], (int)in[4], (int)in[5],
+                                         in[6] > 0 ? (int)in[6] : TOPK_CUS);
+  const int64_t v[] = {p.t.slices, p.t.user_tiles, p.t.item_tiles, TOPK_TU, TOPK_TI, p.t.cap, (int64_t)p.lds,
+                       (int64_t)NBR_LDS_LIMIT, (int64_t)p.t.merge_lds, p.partial_bytes, p.norm_bytes, p.ws_bytes};
+  memcpy(out, v, sizeof(v));
+  for (int s = 0; s <= p.t.slices; ++s) bounds[s] = std::min<int64_t>(topk_slice_tile(p.t, s) * TOPK_TI, in[1]);
+  return BPR_OK;
+}

@@ -237,6 +237,26 @@ class Engine:
         return rank_items(self.P, self.Q, self.item_bias, users, tgt_indptr, tgt_items, indptr, indices,
                           item_slices=item_slices)
 
+    def similar_items(self, items: torch.Tensor, k: int, metric: str = "cosine", *, item_slices: int = 0):
+        """The `k` items most similar to each item of `items` by the rows of the bound item table
+        (`bpr_neighbors_rows`, see revisit_bpr/similar.py): (ids [n, k] int32, scores [n, k] float32), sorted by
+        score descending, ties by ascending id, padded with -1 / -inf; never the item itself, never item 0.
+        `metric`: "cosine" or "dot".  The item bias plays no part.  Rows an Adam / momentum / RMSprop optimizer
+        has not replayed yet are compared as they stand: `flush_lazy()` first (`Model.similar_items` does).  A
+        freshly folded-in row is not in the table: `similar.neighbors(Q_new, engine.Q, torch.arange(m), k,
+        first=1)`."""
+        from revisit_bpr.similar import similar_items
+
+        return similar_items(self.Q, items, k, metric, item_slices=item_slices)
+
+    def similar_users(self, users: torch.Tensor, k: int, metric: str = "cosine", *, item_slices: int = 0):
+        """The `k` users most similar to each user of `users` by the rows of the bound user table: as
+        `similar_items`, except that user 0 is a user like any other.  A freshly folded-in row:
+        `similar.neighbors(P_new, engine.P, torch.arange(m), k)`."""
+        from revisit_bpr.similar import similar_users
+
+        return similar_users(self.P, users, k, metric, item_slices=item_slices)
+
     def fold_in(self, indptr: torch.Tensor, items: torch.Tensor, *, epochs: int, lr: Optional[float] = None,
                 sampler: str = "uniform", refresh: bool = True, **kwargs) -> torch.Tensor:
         """User rows for NEW users (the rows of the CSR `indptr` / `items`) learnt against the engine's item

@@ -496,6 +496,31 @@ class Model(torch.nn.Module):
             score += torch.repeat_interleave(ub.detach()[users.reshape(-1).long()], cnt)
         return rank, not_below, score
 
+    def similar_items(self, items: torch.Tensor, k: int, metric: str = "cosine"):
+        """The `k` items most similar to each item of `items` (device tensor of item ids) by their embedding rows:
+        (ids [n, k] int32, scores [n, k] float32) from the engine's fused neighbour kernel
+        (revisit_bpr/similar.py), sorted by score descending, ties by ascending id, padded with -1 / -inf; never
+        the item itself, never item 0.  `metric`: "cosine" or "dot"; biases play no part.  Rows behind the
+        optimizer step are replayed first (`sync()`).  Only the MF scorer has a fused form.  A freshly folded-in
+        row is not in the table: `similar.neighbors(Q_new, Q, torch.arange(m), k, first=1)`."""
+        if not self._fusable():
+            raise NotImplementedError("similar_items needs the MF logits model in float32: other scorers have no "
+                                      "fused neighbour kernel")
+        eng = self.engine()
+        self.sync()
+        return eng.similar_items(items, k, metric)
+
+    def similar_users(self, users: torch.Tensor, k: int, metric: str = "cosine"):
+        """The `k` users most similar to each user of `users` by their embedding rows: as `similar_items`, except
+        that user 0 is a user like any other.  A freshly folded-in row: `similar.neighbors(P_new, P,
+        torch.arange(m), k)`."""
+        if not self._fusable():
+            raise NotImplementedError("similar_users needs the MF logits model in float32: other scorers have no "
+                                      "fused neighbour kernel")
+        eng = self.engine()
+        self.sync()
+        return eng.similar_users(users, k, metric)
+
     def fold_in(self, indptr: torch.Tensor, items: torch.Tensor, *, epochs: int, lr: float, **kwargs) -> torch.Tensor:
         """User rows [n, d] for NEW users (the rows of the CSR `indptr` int64 / `items` int32) learnt against the
         model's frozen item table and item bias by the engine's fold-in kernel (revisit_bpr/foldin.py holds the

@@ -21,6 +21,7 @@ OPT_SGD, OPT_MOMENTUM, OPT_ADAM, OPT_RMSPROP = 0, 1, 2, 3
 MODE_STRICT, MODE_STREAM = 0, 1
 NEG_GIVEN, NEG_UNIFORM, NEG_ADAPTIVE = 0, 1, 2
 SCALARS = 4
+SIM_DOT, SIM_COSINE = 0, 1  # BPR_SIM_DOT, BPR_SIM_COSINE
 REFRESH_INFO_LEN = 8  # BPR_REFRESH_INFO_LEN: int32 entries bpr_adaptive_refresh_info fills
 
 
@@ -119,6 +120,10 @@ SIGNATURES = {
     "bpr_topk_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     "bpr_topk_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
                               c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "bpr_neighbors_workspace": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "bpr_neighbors_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "bpr_neighbors_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32,
+                                   c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "bpr_rank_workspace": (c_int, [c_int64, c_int64, c_int32, c_int32, POINTER(c_int64)]),
     "bpr_rank_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, POINTER(c_int32)]),
     "bpr_rank_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,

@@ -1,0 +1,125 @@
+"""Neighbour search on the HIP engine: the k rows of a table most similar to each of a list of query rows, by
+cosine or by dot product, from one fused kernel (`bpr_neighbors_rows`, csrc/bpr_neighbors.hip) — scores, the
+exclusions and the selection, with no [n, N] score matrix.  `similar_items` / `similar_users` are the usual pair of
+an implicit-feedback library; `neighbors` is what they are made of.  The reference has no such call.
+
+There is no CPU path: tensors must live on a ROCm device.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import torch
+
+from revisit_bpr import native
+from revisit_bpr.recommend import TOPK_MAX, _table
+
+METRICS = {"dot": native.SIM_DOT, "cosine": native.SIM_COSINE}
+
+
+def _metric(metric: str) -> int:
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {sorted(METRICS)}, not {metric!r}")
+    return METRICS[metric]
+
+
+def workspace_bytes(n: int, num_rows: int, d: int, k: int, metric: str = "cosine", item_slices: int = 0) -> int:
+    """`bpr_neighbors_workspace`: bytes of device workspace a call of this shape needs."""
+    out = ctypes.c_int64()
+    native.check(native.load().bpr_neighbors_workspace(n, num_rows, d, k, _metric(metric), item_slices,
+                                                       ctypes.byref(out)))
+    return int(out.value)
+
+
+def slices(n: int, num_rows: int, d: int, k: int, item_slices: int = 0) -> int:
+    """`bpr_neighbors_slices`: the slice count a call of this shape runs with."""
+    out = ctypes.c_int32()
+    native.check(native.load().bpr_neighbors_slices(n, num_rows, d, k, item_slices, ctypes.byref(out)))
+    return int(out.value)
+
+
+def _ids(t: torch.Tensor) -> torch.Tensor:
+    t = t.reshape(-1)
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)
+    return t.contiguous()
+
+
+@torch.no_grad()
+def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, metric: str = "cosine",
+              exclude: Optional[torch.Tensor] = None, first: int = 0, item_slices: int = 0,
+              check_rows: bool = True):
+    """The `k` rows of `T` [N, d] most similar to each query `X[rows[r]]` (`X` [*, d]: `T` itself or another
+    table of the same d), by `metric`: "cosine" (<x, t> / (|x| |t|)) or "dot" (<x, t>, the score of `recommend`
+    without a bias).  Left out of row r: ids of `T` below `first`, the id `exclude[r]` (`exclude` None, or an
+    entry below 0: none) and, under cosine, rows of `T` with a zero (or NaN) norm; a query with such a norm gets a
+    fully padded row.
+
+    Returns (ids [n, k] int32, scores [n, k] float32): rows sorted by score descending, ties by ascending id; a
+    row with fewer than k eligible rows of `T` ends in id -1 / score -inf.  The result does not depend on n, on
+    the order of `rows` or on `item_slices` (0: the library chooses how many workgroups share the table for a
+    query tile); include/bprcore.h defines its bits.  Runs on the current stream.  The kernel reads `X[rows[r]]`
+    unchecked, so `rows` are range-checked against `X` (and `exclude` against `T`) here first, which waits for
+    the device; `check_rows=False` leaves that out (ids known to be valid: a serving loop, a captured graph).
+
+    Rows folded in after training (`fold_in_items`, `fold_in`) are looked at against the catalogue with
+    `neighbors(Q_new, Q, torch.arange(m), k, first=1)`: row r of the result is what the new item r resembles."""
+    k = int(k)
+    if k > TOPK_MAX:
+        raise ValueError(f"k = {k}: neighbors returns at most {TOPK_MAX} ids per query")
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    code = _metric(metric)
+    first = int(first)
+    if first < 0:
+        raise ValueError("first must be at least 0")
+    if not (X.is_cuda and T.is_cuda and rows.is_cuda and (exclude is None or exclude.is_cuda)):
+        raise RuntimeError("neighbors needs the tables and the row list on a ROCm device; there is no CPU path "
+                           "in libbprcore")
+    if any(t is not None and t.device != X.device for t in (T, rows, exclude)):
+        raise RuntimeError("neighbors needs every tensor on the device of X")
+    lib = native.load()
+    same = X is T
+    T = _table(T, "T")
+    X = T if same else _table(X, "X")
+    if X.dim() != 2 or T.dim() != 2 or X.shape[1] != T.shape[1]:
+        raise ValueError("X [*, d] and T [N, d] must share the embedding dim")
+    (N, d), dev = T.shape, X.device
+    rows = _ids(rows)
+    n = rows.numel()
+    if exclude is not None:
+        exclude = _ids(exclude)
+        if exclude.numel() != n:
+            raise ValueError("exclude must have one entry per query")
+    if check_rows and n:
+        if bool(((rows < 0) | (rows >= X.shape[0])).any()):
+            raise ValueError("row id out of range")
+        if exclude is not None and bool((exclude >= N).any()):
+            raise ValueError("exclude id out of range")
+    ids = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    item_slices = slices(n, N, d, k, item_slices)  # the count this call runs with: the workspace is its own need
+    ws_bytes = workspace_bytes(n, N, d, k, metric, item_slices)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    with torch.cuda.device(dev):
+        native.check(lib.bpr_neighbors_rows(
+            X.data_ptr(), T.data_ptr(), N, d, rows.data_ptr(), n,
+            None if exclude is None else exclude.data_ptr(), first, code, k, item_slices,
+            None if ws is None else ws.data_ptr(), ws_bytes, ids.data_ptr(), scores.data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream))
+    return ids, scores
+
+
+def similar_items(Q: torch.Tensor, items: torch.Tensor, k: int, metric: str = "cosine", **kwargs):
+    """The `k` items most similar to each item of `items` by their rows of the item table `Q`: `neighbors(Q, Q,
+    items, k, exclude=items, first=1)` — never the item itself, never the padding item 0.  A freshly folded-in
+    item row is not in `Q`: `neighbors(Q_new, Q, torch.arange(m), k, first=1)`."""
+    return neighbors(Q, Q, items, k, metric=metric, exclude=items, first=1, **kwargs)
+
+
+def similar_users(P: torch.Tensor, users: torch.Tensor, k: int, metric: str = "cosine", **kwargs):
+    """The `k` users most similar to each user of `users` by their rows of the user table `P`: `neighbors(P, P,
+    users, k, exclude=users, first=0)` — never the user itself; user 0 is a user like any other.  A freshly
+    folded-in user row is not in `P`: `neighbors(P_new, P, torch.arange(m), k)`."""
+    return neighbors(P, P, users, k, metric=metric, exclude=users, first=0, **kwargs)
