@@ -749,6 +749,46 @@ int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int32_t d,
                        void* workspace, int64_t workspace_bytes,
                        int32_t* ids_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
 
+/* ---- re-ranking: the k best of a GIVEN candidate list per row, and the score of every candidate ("score this user
+ * on these items": availability filters, second-stage re-ranking, sampled-negative protocols, explicit pairs).  The
+ * reference has no candidate path: it ranks through full logits (example.py:195-230), which this replaces for a
+ * narrowed catalogue.  One fused gather kernel (csrc/bpr_rerank.hip): no [nnz, d] buffer, no sweep of the item table,
+ * no workspace.
+ * Rows.  Row r is user users[r] with the candidates cand_items[cand_indptr[r] .. cand_indptr[r + 1]) (cand_indptr
+ * [n + 1] int64, non-decreasing; unsorted, duplicates allowed, any length including 0), or — cand_indptr NULL — the
+ * ONE list cand_items[0 .. shared_len) for every row.  With a cand_indptr, shared_len is only a hint to the launch
+ * plan: a typical row length (nnz / n), 0 = unknown; it changes no output.
+ * Eligibility.  A candidate is eligible if 0 < id < I and id is not in the user's row of the seen CSR (seen_indptr
+ * [U + 1] int64, seen_indices int32 sorted per row, as bpr_bind_seen_csr; both NULL: nothing is seen).  It is decided
+ * before the item row is read: an ineligible candidate costs no table traffic.
+ * Scores.  s(u, i) = bpr_topk_rows' / bpr_rank_rows' / bpr_neighbors_rows' (dot) score, bit for bit: one fp32 fmaf
+ * chain from 0.0f over the features in the fixed order (per 8 features: 0, 4, 1, 5, 2, 6, 3, 7), then item_bias[i]
+ * as one fp32 add.  Tables are taken to be finite.
+ * Output.  cand_scores_out (may be NULL if k > 0), aligned with the candidates ([n, shared_len] row-major for the
+ * shared list): the score, -inf for an ineligible candidate.  With k > 0, items_out / scores_out [n, k]: the
+ * eligible candidates sorted by score descending, ties by ascending id; an id listed m times is a candidate m times
+ * and may be returned m times, adjacent; a row with fewer than k eligible candidates ends in id -1 / score -inf.
+ * k == 0 writes cand_scores_out only.
+ * The result is a pure function of the inputs: its bits do not depend on n, on a row's place in the call, on the
+ * order of the candidates inside a row (cand_scores_out moves with them) or on `layout` (0 = the library chooses;
+ * 1 = a wave of 64 lanes per row, 2 = a workgroup of 256 threads per row).  A row is never split over workgroups.
+ * d in [1, 1024], 0 <= k <= 128, I in [1, 2^31), n >= 0, shared_len >= 0, layout in [0, 2], k == 0 only with
+ * cand_scores_out, the seen pointers both NULL or both given: anything else is BPR_ERR_INVALID.  users, cand_indptr
+ * and seen_indptr are read unchecked by the kernel; candidate ids are checked.  Arguments are validated before the
+ * device is touched; n == 0 is BPR_OK.  Nothing is read back: the call is asynchronous and can be captured into a
+ * graph.  Context-free: runs on `hip_stream` of the current device. */
+int bpr_rerank_rows(const float* P, const float* Q, const float* item_bias /* or NULL */, int64_t I, int32_t d,
+                    const int32_t* users, int64_t n,
+                    const int64_t* cand_indptr /* [n+1] or NULL */, const int32_t* cand_items, int64_t shared_len,
+                    const int64_t* seen_indptr /* [U+1] or NULL */, const int32_t* seen_indices,
+                    int32_t k, int32_t layout /* 0 = choose */,
+                    float* cand_scores_out /* or NULL */, int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */,
+                    void* hip_stream);
+/* the layout (1 or 2) and the tile (candidates a team stages at a time: 64 or 256) a call of this shape runs with;
+ * row_len is what the call passes as shared_len */
+int bpr_rerank_layout(int64_t n, int32_t d, int32_t k, int64_t row_len, int32_t layout, int32_t* layout_host,
+                      int32_t* tile_host);
+
 /* ---- multi-GPU item-table reconciliation (no reference counterpart: the reference's DDP path is
  * never enabled by a config, experiments/launcher.py:35-73).  The all-reduce itself is RCCL via
  * torch.distributed; these two fused elementwise kernels bracket it (revisit_bpr/distributed.py).

@@ -237,6 +237,32 @@ class Engine:
         return rank_items(self.P, self.Q, self.item_bias, users, tgt_indptr, tgt_items, indptr, indices,
                           item_slices=item_slices)
 
+    def rerank(self, users: torch.Tensor, cand_items: torch.Tensor, k: int,
+               cand_indptr: Optional[torch.Tensor] = None, exclude_seen: bool = True, *,
+               return_scores: bool = False, layout: int = 0):
+        """The `k` best of each row's own candidates from the bound tables (`bpr_rerank_rows`, see
+        revisit_bpr/rerank.py): row r is user `users[r]` with `cand_items[cand_indptr[r]:cand_indptr[r + 1]]`, or
+        with the whole 1-D `cand_items` when there is no `cand_indptr`.  (items [n, k] int32, scores [n, k]
+        float32), sorted by score descending, ties by ascending id, padded with -1 / -inf; `return_scores` adds
+        every candidate's score (-inf: not eligible).  Ids outside 1 .. I-1 are never eligible; exclude_seen also
+        leaves out the user's row of the CSR given to `bind_seen_csr`.  Rows an Adam / momentum / RMSprop
+        optimizer has not replayed yet are scored as they stand: `flush_lazy()` first (`Model.rerank` does)."""
+        from revisit_bpr.rerank import rerank
+
+        indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
+        return rerank(self.P, self.Q, self.item_bias, users, cand_items, k, cand_indptr, indptr, indices,
+                      return_scores=return_scores, layout=layout)
+
+    def score_candidates(self, users: torch.Tensor, cand_items: torch.Tensor,
+                         cand_indptr: Optional[torch.Tensor] = None, exclude_seen: bool = True, *, layout: int = 0):
+        """The score of every candidate of every row (`rerank` with k = 0): float32 aligned with `cand_items`
+        ([n, C] for a shared 1-D list), -inf for a candidate that is not eligible."""
+        from revisit_bpr.rerank import score_candidates
+
+        indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
+        return score_candidates(self.P, self.Q, self.item_bias, users, cand_items, cand_indptr, indptr, indices,
+                                layout=layout)
+
     def similar_items(self, items: torch.Tensor, k: int, metric: str = "cosine", *, item_slices: int = 0):
         """The `k` items most similar to each item of `items` by the rows of the bound item table
         (`bpr_neighbors_rows`, see revisit_bpr/similar.py): (ids [n, k] int32, scores [n, k] float32), sorted by

@@ -496,6 +496,49 @@ class Model(torch.nn.Module):
             score += torch.repeat_interleave(ub.detach()[users.reshape(-1).long()], cnt)
         return rank, not_below, score
 
+    def _cand_user_bias(self, users: torch.Tensor, cand_items: torch.Tensor, cand_indptr):
+        """the user bias of every candidate's row, shaped like cand_scores"""
+        ub = self.logits_model._user_bias.detach()[users.reshape(-1).long()]
+        if cand_indptr is None:
+            return ub.unsqueeze(1)  # [n, 1] against [n, C]
+        return torch.repeat_interleave(ub, cand_indptr[1:] - cand_indptr[:-1])
+
+    def rerank(self, users: torch.Tensor, cand_items: torch.Tensor, k: int, cand_indptr=None,
+               exclude_seen: bool = True, return_scores: bool = False):
+        """The `k` best of each row's own candidates (row r: user `users[r]` with
+        `cand_items[cand_indptr[r]:cand_indptr[r + 1]]`, or the whole 1-D `cand_items` without a `cand_indptr`):
+        (items [n, k] int32, scores [n, k] float32) from the engine's fused re-ranking kernel
+        (revisit_bpr/rerank.py), sorted by score descending, ties by ascending id, padded with -1 / -inf;
+        `return_scores` adds every candidate's score (-inf: not eligible).  Ids outside 1 .. I-1 and —
+        exclude_seen — the items of the CSR given to `bind_seen_csr` are not eligible.  Rows behind the optimizer
+        step are replayed first (`sync()`).  A user bias is added to the returned scores (it does not change a
+        row's order).  Only the MF scorer has a fused form."""
+        if not self._fusable():
+            raise NotImplementedError("rerank needs the MF logits model in float32: other scorers have no fused "
+                                      "re-ranking kernel")
+        eng = self.engine()
+        self.sync()
+        out = eng.rerank(users, cand_items, k, cand_indptr, exclude_seen=exclude_seen, return_scores=return_scores)
+        if self.logits_model._user_bias is not None:
+            out[1].add_(self.logits_model._user_bias.detach()[users.reshape(-1).long()].unsqueeze(1))
+            if return_scores:
+                out[2].add_(self._cand_user_bias(users, cand_items, cand_indptr))
+        return out
+
+    def score_candidates(self, users: torch.Tensor, cand_items: torch.Tensor, cand_indptr=None,
+                         exclude_seen: bool = True):
+        """The score of every candidate of every row (`rerank` with k = 0): float32 aligned with `cand_items`
+        ([n, C] for a shared 1-D list), -inf for a candidate that is not eligible; the user bias included."""
+        if not self._fusable():
+            raise NotImplementedError("score_candidates needs the MF logits model in float32: other scorers have no "
+                                      "fused re-ranking kernel")
+        eng = self.engine()
+        self.sync()
+        score = eng.score_candidates(users, cand_items, cand_indptr, exclude_seen=exclude_seen)
+        if self.logits_model._user_bias is not None:
+            score.add_(self._cand_user_bias(users, cand_items, cand_indptr))
+        return score
+
     def similar_items(self, items: torch.Tensor, k: int, metric: str = "cosine"):
         """The `k` items most similar to each item of `items` (device tensor of item ids) by their embedding rows:
         (ids [n, k] int32, scores [n, k] float32) from the engine's fused neighbour kernel
