@@ -702,6 +702,53 @@ int bpr_fold_in_item_rows(const float* P, int64_t U, const float* Q, const float
                           float* Q_new /* [m,d] in/out */, float* bias_new /* [m] in/out, or NULL */,
                           void* hip_stream);
 
+/* bpr_fold_in_item_rows in BOTH roles (csrc/bpr_foldin_items_roles.hip): besides being the positive of its audience's
+ * triples, a new item is the NEGATIVE of neg_role (R >= 0) training interactions per epoch — triples (u, i, new) where
+ * (u, i) is a training interaction of a user outside the item's audience, the triples that would have drawn it in joint
+ * training with uniform negatives (about T / I per epoch for every item, whence one R for all rows).  Every argument it
+ * shares with bpr_fold_in_item_rows means what it means there; so do the CSR contract, `order`, the limits, "validated
+ * before the device is touched", the one host read, the ticket words, m == 0 and what is never written — to which
+ * train_users / train_items (int32 [T], T < 2^31, as the trainers take them; never written) are added.
+ * STEP ORDER.  Row r of length L takes `epochs` passes of L + R sequential steps.  Step s in [0, L + R) of a pass is a
+ * negative-role step iff floor((s + 1) R / (L + R)) > floor(s R / (L + R)) (64-bit integers); rho = floor(s R / (L + R))
+ * negative-role steps precede it, and a positive-role step has position k = s - rho.  A row of length 0 takes R
+ * negative-role steps per epoch when R > 0 and keeps its initial values when R = 0.
+ * POSITIVE-ROLE STEP (e, k): exactly bpr_fold_in_item_rows' step — its triple index t, counter offset + t, neg_in /
+ * neg_out entry t, skip rule and update.  With R = 0 the call returns bpr_fold_in_item_rows' bits for Q_new, bias_new
+ * and neg_out.
+ * NEGATIVE-ROLE STEP (e, rho), with g = (e * m + r) * R + rho:
+ *     attempts       a = 0 .. 15, in order: w_a = word a & 3 of the Philox4x32-10 block with counter words (lo32(c),
+ *                    hi32(c), a >> 2, 2), c = offset + g, under the key (lo32(seed), hi32(seed)).  Counter word 3 = 2
+ *                    separates the stream from the uniform sampler's (0: candidates and rank pick) and the adaptive
+ *                    sampler's (1).  tau = (uint64) w_a * T >> 32, u = train_users[tau], i = train_items[tau]; the
+ *                    attempt is accepted iff 0 <= u < U, 1 <= i < I and u is not in row r's audience.
+ *     interaction    that of the first accepted attempt; role_out[g] = its tau.  None accepted (a row whose audience is
+ *                    nearly everyone): the step is skipped, role_out[g] = -1, q and b unchanged.
+ *     update, fp32   x = <p_u, q_i - q> (+ b_i - b),  w = sigma(-x),  q <- q - lr (w p_u + alpha_item q),
+ *                    b <- b - lr w
+ * Both updates form x as bpr_fold_in_item_rows does: per lane an fmaf chain from 0.0f over its elements of p_u times the
+ * difference, the group's sum of the lanes, then the bias difference added; w = 1 / (1 + exp(x)).
+ * role_out [epochs * m * R] int32 or NULL; the entries of rows that `order` passes over are not written.  The result is
+ * a pure function of these definitions: the bits of Q_new, bias_new, neg_out and role_out do not depend on `order`, on
+ * the launch or on the kernel's prefetch depth; a row's bits depend on m and r only through g.
+ * neg_role < 0, or neg_role > 0 with train_users or train_items NULL or T < 1: BPR_ERR_INVALID (neg_role = 0 accepts NULL
+ * arrays).  epochs * m * neg_role, and epochs * (nnz + m * neg_role) (the kernel's 32-bit step counters), must be below
+ * 2^31: BPR_ERR_UNSUPPORTED. */
+int bpr_fold_in_item_rows_roles(const float* P, int64_t U, const float* Q, const float* item_bias /* or NULL */,
+                                int64_t I, int32_t d,
+                                const int64_t* seen_indptr /* [U+1] or NULL */, const int32_t* seen_indices,
+                                const int64_t* indptr /* [m+1] */, const int32_t* users, int64_t m,
+                                const int32_t* order /* [m] or NULL */,
+                                int32_t epochs, float lr, float alpha_item,
+                                int32_t sampler /* BPR_NEG_GIVEN | BPR_NEG_UNIFORM */,
+                                const int32_t* neg_in /* [epochs*nnz], GIVEN */,
+                                int32_t* neg_out /* [epochs*nnz] or NULL */,
+                                uint64_t seed, uint64_t offset,
+                                const int32_t* train_users /* [T] */, const int32_t* train_items /* [T] */, int64_t T,
+                                int32_t neg_role /* R */, int32_t* role_out /* [epochs*m*R] or NULL */,
+                                float* Q_new /* [m,d] in/out */, float* bias_new /* [m] in/out, or NULL */,
+                                void* hip_stream);
+
 /* ---- neighbours: the k rows of a table most similar to each of a list of query rows ("items like this one",
  * "users like this one"; the reference has no such call).  One fused kernel (csrc/bpr_neighbors.hip) with
  * bpr_topk_rows' tiling and selection, and no [n, N] buffer anywhere.  Query r is the row X[rows[r]] ([*, d] fp32

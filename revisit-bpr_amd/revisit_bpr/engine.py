@@ -327,7 +327,9 @@ class Engine:
         `torch.cat((engine.item_bias, bias_new))` go straight into `recommend`, `rank_items` and `evaluate_*`.
         `reg_item` defaults to the item alpha of `set_reg`, `lr` to the learning rate of `set_optimizer`.
         `exclude_seen`: sampled negatives are unseen by the triple's user according to the CSR given to
-        `bind_seen_csr` (False, or none bound: any item but 0).  Both tables are made whole first: the hot block an
+        `bind_seen_csr` (False, or none bound: any item but 0).  `neg_role`, `train_users`, `train_items` and
+        `return_roles` (the item's second role, as the negative of training interactions outside its audience) go
+        through unchanged.  Both tables are made whole first: the hot block an
         asynchronous cut left is folded and rows a lazy optimizer has not replayed yet are flushed."""
         from revisit_bpr import foldin_items
 

@@ -586,7 +586,8 @@ class Model(torch.nn.Module):
         """Item rows [m, d] (and biases [m], when the model has an item bias: a pair) for NEW items (the rows of the
         CSR `indptr` int64 / `users` int32: who interacted with each) learnt against the model's frozen user table,
         item table and item bias by the engine's item fold-in kernel (revisit_bpr/foldin_items.py holds the
-        keywords); `reg_item` defaults to the model's item regularisation.  The model is not changed: the rows are
+        keywords, `neg_role` / `train_users` / `train_items` / `return_roles` among them); `reg_item` defaults to the
+        model's item regularisation.  The model is not changed: the rows are
         returned, and `torch.cat` of the item table (bias) with them goes straight into
         `revisit_bpr.recommend.recommend`, `rank_items` or `evaluate_*`, where the new items have the ids I, I + 1,
         ...  Rows behind the optimizer step are replayed first (`sync()`).  Only the MF scorer has a fused form; a

@@ -141,6 +141,10 @@ SIGNATURES = {
     "bpr_fold_in_item_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_float, c_float, c_int32,
                                       c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "bpr_fold_in_item_rows_roles": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_float, c_float, c_int32,
+                                            c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_int64,
+                                            c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bpr_set_hot_lds": (c_int, [c_void_p, c_int32, c_int32]),
     "bpr_stream_lds_rows": (c_int, [c_void_p]),
     "bpr_item_fold_delta": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64,

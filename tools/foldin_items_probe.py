@@ -16,7 +16,14 @@ jointly with everything else and beside untrained rows (the floor); and, second 
 interactions, which charges a new item for the warm targets it displaces.  Folded-in items get no updates in the
 negative role; this table is how far that matters.
 
-Usage: python tools/foldin_items_probe.py [--reps 5] [--skip-study] [--skip-timing] [--out profiles/foldin_items_probe.txt]"""
+With `--neg-role auto` (or N) both questions are asked of the second role (`fold_in_items(neg_role=...)`,
+csrc/bpr_foldin_items_roles.hip): (i) times the same two lists with R negative-role steps per row and epoch against
+R = 0 through the single-role entry, alternating in one process, and reports microseconds per sequential step of the
+longest row on both sides (the training interactions are the seen CSR's); (ii) adds the rows folded in with R to the
+table, beside R = 0, at 5 / 20 / 60 epochs.  The output then goes to profiles/foldin_items_roles_probe.txt.
+
+Usage: python tools/foldin_items_probe.py [--reps 5] [--skip-study] [--skip-timing] [--neg-role {0,auto,N}]
+       [--out profiles/foldin_items_probe.txt]"""
 import argparse
 import sys
 from pathlib import Path
@@ -35,8 +42,12 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--skip-study", action="store_true")
 ap.add_argument("--skip-timing", action="store_true")
-ap.add_argument("--out", type=str, default=str(ROOT / "profiles" / "foldin_items_probe.txt"))
+ap.add_argument("--neg-role", type=str, default="0", help="0 (single role), auto, or a count per row and epoch")
+ap.add_argument("--out", type=str, default=None)
 opt = ap.parse_args()
+NEG_ROLE = "auto" if opt.neg_role == "auto" else int(opt.neg_role)
+if opt.out is None:
+    opt.out = str(ROOT / "profiles" / ("foldin_items_roles_probe.txt" if NEG_ROLE != 0 else "foldin_items_probe.txt"))
 dev = torch.device("cuda")
 lines = []
 
@@ -64,6 +75,49 @@ def timed(fn):
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b)
+
+
+def timing_roles():
+    """R negative-role steps against none (the single-role entry), alternating, on the lists of `timing`."""
+    m, epochs = 2_000, 5
+    say(f"(i) one fold_in_items call, {m} new items, {epochs} epochs, sampled negatives, item bias, lr 0.05, reg_item "
+        f"0.01, balance on; neg_role {NEG_ROLE} against 0 (bpr_fold_in_item_rows), alternating in one process; ms: "
+        f"median  min .. max of {opt.reps}; us/step: per sequential step of the longest row, epochs * (L + R) of them")
+    say(f"{'shape':34s} {'nnz':>9s} {'longest':>7s} {'R':>6s} {'T':>10s} | {'ms, R = 0':>28s} {'us/step':>7s} | "
+        f"{'ms, R':>28s} {'us/step':>7s} | {'ratio':>6s} {'(L+R)/L':>7s}")
+    for name, U, I, d, mean_seen, median, sigma in (("ML-20M U=138493 I=20109 d=128", 138_493, 20_109, 128, 144, 40.0, 2.0),
+                                                    ("MSD U=571355 I=41140 d=256", 571_355, 41_140, 256, 59, 20.0, 1.5)):
+        g = torch.Generator(device=dev).manual_seed(1)
+        P = (torch.rand(U, d, device=dev, generator=g) - 0.5) / d
+        Q = (torch.rand(I, d, device=dev, generator=g) - 0.5) / d
+        b = (torch.rand(I, device=dev, generator=g) - 0.5) / d
+        seen_cnt = torch.randint(1, 2 * mean_seen, (U,), device=dev, generator=g)
+        seen_indptr, seen_indices = strided_csr(seen_cnt, I, 1, g)
+        train_users = torch.repeat_interleave(torch.arange(U, device=dev, dtype=torch.int32), seen_cnt)
+        lens = torch.clamp(torch.round(median * torch.exp(sigma * torch.randn(m, device=dev, generator=g))), 1, U // 4)
+        indptr, users = strided_csr(lens.long(), U, 0, g)
+        nnz, longest, T = int(indptr[-1]), int(lens.max()), train_users.numel()
+        R = max(1, round(T / (I - 1))) if NEG_ROLE == "auto" else NEG_ROLE
+        kw = dict(epochs=epochs, lr=0.05, reg_item=0.01, init_std=0.01, seed=3, seen_indptr=seen_indptr,
+                  seen_indices=seen_indices)
+        calls = {0: lambda: fold_in_items(P, Q, b, indptr, users, **kw),
+                 R: lambda: fold_in_items(P, Q, b, indptr, users, neg_role=R, train_users=train_users,
+                                          train_items=seen_indices, **kw)}
+        ms = {0: [], R: []}
+        for side in (0, R):
+            calls[side]()  # warm-up
+        for _ in range(opt.reps):
+            for side in (0, R):
+                ms[side].append(timed(calls[side]))
+        med = {}
+        cells = []
+        for side in (0, R):
+            v = sorted(ms[side])
+            med[side] = v[len(v) // 2]
+            cells.append(f"{med[side]:10.3f}  {v[0]:7.3f} .. {v[-1]:7.3f} {1e3 * med[side] / (epochs * (longest + side)):7.3f}")
+        say(f"{name:34s} {nnz:9d} {longest:7d} {R:6d} {T:10d} | {cells[0]} | {cells[1]} | {med[R] / med[0]:6.3f} "
+            f"{(longest + R) / longest:7.3f}")
+        del P, Q, b, seen_indptr, seen_indices, indptr, users, train_users
 
 
 def timing():
@@ -176,6 +230,13 @@ def study():
         Qn = fold_in_items(Pw, Qw, None, t(c_indptr), t(c_users), epochs=fe, lr=lr, reg_item=reg, init_std=0.1, seed=8,
                            seen_indptr=t(w_indptr), seen_indices=t(w_indices))
         say(f"  folded in against the tables trained without them, {fe:2d} epochs   {ndcg(Pw, torch.cat((Qw, Qn)))}")
+        if NEG_ROLE != 0:
+            Qn, roles = fold_in_items(Pw, Qw, None, t(c_indptr), t(c_users), epochs=fe, lr=lr, reg_item=reg, init_std=0.1,
+                                      seed=8, seen_indptr=t(w_indptr), seen_indices=t(w_indices), neg_role=NEG_ROLE,
+                                      train_users=t(w_users), train_items=t(w_indices), return_roles=True)
+            per = roles.numel() // (fe * len(cold))
+            say(f"  the same with neg_role {NEG_ROLE} (R = {per}, {int((roles < 0).sum())} steps skipped), {fe:2d} epochs"
+                f"   {ndcg(Pw, torch.cat((Qw, Qn)))}")
     g = torch.Generator(device=dev).manual_seed(8)
     Qn = torch.randn(len(cold), d, device=dev, generator=g) * 0.1
     say(f"  untrained rows (N(0, 0.1^2)) beside those tables           {ndcg(Pw, torch.cat((Qw, Qn)))}")
@@ -183,7 +244,7 @@ def study():
 
 say(f"device {torch.cuda.get_device_name(0)}")
 if not opt.skip_timing:
-    timing()
+    timing_roles() if NEG_ROLE != 0 else timing()
 if not opt.skip_study:
     study()
 Path(opt.out).parent.mkdir(parents=True, exist_ok=True)
