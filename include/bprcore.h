@@ -836,6 +836,54 @@ int bpr_rerank_rows(const float* P, const float* Q, const float* item_bias /* or
 int bpr_rerank_layout(int64_t n, int32_t d, int32_t k, int64_t row_len, int32_t layout, int32_t* layout_host,
                       int32_t* tile_host);
 
+/* ---- diversified top-k: greedy maximal marginal relevance (MMR) over a pool of candidates per row — "the k best,
+ * but not k copies of one thing".  The reference has no such pass: it ranks through full logits (example.py:195-230).
+ * The input is what bpr_topk_rows / bpr_rerank_rows return ([n, C] ids and scores, -1 / -inf padding); the output has
+ * the same form.  One fused kernel (csrc/bpr_diversify.hip): a workgroup per row keeps the row's C x C similarities in
+ * LDS; no [n, C, d] gather, no [n, C, C] matrix, no workspace.
+ * Rows.  Row r has the C candidates cand_items[r, 0 .. C) (int32) with relevances cand_scores[r, 0 .. C) (fp32),
+ * row-major, 1 <= C <= 128; the item table is Q [I, d] fp32 row-major.
+ * Eligibility.  A candidate is eligible if 0 < id < I and its relevance is finite (this drops the -1 / -inf padding,
+ * id 0 and a NaN relevance).  It is decided before the item row is read: an ineligible candidate costs no table
+ * traffic.  An id listed m times is m candidates.
+ * Similarity.  dot(a, b) is bpr_topk_rows' chain on the two item rows: ONE fp32 accumulator from +0.0f, one fmaf per
+ * feature in the fixed order (per 8 features: 0, 4, 1, 5, 2, 6, 3, 7), every chunk of 32 features run to its end over
+ * zeros past d — the bits bpr_rerank_rows' cand_scores_out holds for P = Q, user a, candidate b, no bias.
+ *   BPR_SIM_DOT     sim(a, b) = dot(a, b).
+ *   BPR_SIM_COSINE  sim(a, b) = dot(a, b) * (rn(a) * rn(b)): two fp32 multiplications in THAT association, with
+ *                   rn(v) = 1.0f / sqrt(dot(v, v)), the correctly rounded fp32 square root and division (as
+ *                   bpr_neighbors_rows' rn).  A row with !(dot(v, v) > 0) has similarity 0 to everything.  This is
+ *                   NOT bpr_neighbors_rows' (dot * rn(t)) * rn(x): here sim(a, b) and sim(b, a) are the same bits.
+ * Relevance.  BPR_SCALE_NONE: rel' = rel.  BPR_SCALE_MINMAX: rel' = (rel - lo) / (hi - lo) with lo / hi the smallest /
+ * largest relevance of the row's eligible candidates: fp32 subtraction, subtraction, correctly rounded division;
+ * hi == lo: rel' = 0.  The scores returned are always the ORIGINAL relevances.
+ * Objective.  oml = 1.0f - lam (fp32); m(c) = the largest sim(c, s) over the candidates s picked so far (after the
+ * first pick it is that similarity, negative or not; 0.0f while nothing is picked);
+ *   v(c) = (lam * rel'(c)) - (oml * m(c)): three separately rounded fp32 operations, no fma.
+ * Each step picks the unpicked eligible candidate with the largest v; ties go to the larger original relevance, then
+ * the smaller id, then the smaller position: the output is a function of the multiset of (id, relevance) pairs of the
+ * row.  A NaN v (tables are taken to be finite; an overflowing dot can make one) counts, and is reported, as -inf.
+ * Output.  items_out / scores_out [n, k] in pick order, and — mmr_out may be NULL — the v each pick won with; a row
+ * with fewer than k eligible candidates ends in id -1 / score -inf / mmr -inf.
+ * The result is a pure function of the inputs: its bits do not depend on n, on a row's place in the call, on the order
+ * of the candidates inside a row or on `layout` (0 = the library chooses; 1 = a workgroup of 256 threads per row, the
+ * only layout today).  1 <= C <= 128, 0 <= k <= 128, d in [1, 1024], I in [1, 2^31), n >= 0, 0 <= lam <= 1 (a NaN is
+ * refused), a known metric and scale, layout in [0, 1]: anything else is BPR_ERR_INVALID.  Arguments are validated
+ * before the device is touched; n == 0 and k == 0 are BPR_OK without tables.  Nothing is read back: the call is
+ * asynchronous and can be captured into a graph.  Context-free: runs on `hip_stream` of the current device. */
+#define BPR_SCALE_NONE 0
+#define BPR_SCALE_MINMAX 1
+int bpr_diversify_rows(const float* Q, int64_t I, int32_t d,
+                       const int32_t* cand_items /* [n,C] */, const float* cand_scores /* [n,C] */, int64_t n,
+                       int32_t C, int32_t k, float lam, int32_t metric /* BPR_SIM_* */, int32_t scale /* BPR_SCALE_* */,
+                       int32_t layout /* 0 = choose */,
+                       int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, float* mmr_out /* [n,k] or NULL */,
+                       void* hip_stream);
+/* what a call of this shape runs with: the layout (1), the pool padded to a multiple of 32 and the bytes of LDS a
+ * workgroup holds (they depend on C only: 9,344 / 22,784 / 40,448 / 62,336 at C <= 32 / 64 / 96 / 128) */
+int bpr_diversify_layout(int64_t n, int32_t C, int32_t k, int32_t layout, int32_t* layout_host, int32_t* cpad_host,
+                         int64_t* lds_host);
+
 /* ---- multi-GPU item-table reconciliation (no reference counterpart: the reference's DDP path is
  * never enabled by a config, experiments/launcher.py:35-73).  The all-reduce itself is RCCL via
  * torch.distributed; these two fused elementwise kernels bracket it (revisit_bpr/distributed.py).

@@ -283,6 +283,28 @@ class Engine:
 
         return similar_users(self.P, users, k, metric, item_slices=item_slices)
 
+    def diversify(self, cand_items: torch.Tensor, cand_scores: torch.Tensor, k: int, *, lam: float = 0.7,
+                  metric: str = "cosine", scale: str = "none", return_mmr: bool = False, layout: int = 0):
+        """Greedy MMR over each row's pool of candidates by the rows of the bound item table
+        (`bpr_diversify_rows`, see revisit_bpr/diversify.py): `cand_items` / `cand_scores` [n, C] as `recommend` /
+        `rerank` return them, C <= 128; (items [n, k] int32, scores [n, k] float32) in pick order, padded with
+        -1 / -inf; `return_mmr` adds the objective each pick won with.  Rows an Adam / momentum / RMSprop optimizer
+        has not replayed yet are compared as they stand: `flush_lazy()` first (`Model.diversify` does)."""
+        from revisit_bpr.diversify import diversify
+
+        return diversify(self.Q, cand_items, cand_scores, k, lam=lam, metric=metric, scale=scale,
+                         return_mmr=return_mmr, layout=layout)
+
+    def recommend_diverse(self, users: torch.Tensor, k: int, *, pool: int = 100, lam: float = 0.7,
+                          metric: str = "cosine", scale: str = "minmax", exclude_seen: bool = True):
+        """`recommend(pool)` followed by `diversify(k)` on the bound tables (revisit_bpr/diversify.py): the `k`
+        picks of greedy MMR from every user's `pool` best items.  lam = 1 is `recommend(k)` bit for bit."""
+        from revisit_bpr.diversify import recommend_diverse
+
+        indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
+        return recommend_diverse(self.P, self.Q, self.item_bias, users, k, pool=pool, lam=lam, metric=metric,
+                                 scale=scale, seen_indptr=indptr, seen_indices=indices)
+
     def fold_in(self, indptr: torch.Tensor, items: torch.Tensor, *, epochs: int, lr: Optional[float] = None,
                 sampler: str = "uniform", refresh: bool = True, **kwargs) -> torch.Tensor:
         """User rows for NEW users (the rows of the CSR `indptr` / `items`) learnt against the engine's item

@@ -564,6 +564,38 @@ class Model(torch.nn.Module):
         self.sync()
         return eng.similar_users(users, k, metric)
 
+    def diversify(self, cand_items: torch.Tensor, cand_scores: torch.Tensor, k: int, *, lam: float = 0.7,
+                  metric: str = "cosine", scale: str = "none", return_mmr: bool = False):
+        """Greedy MMR over each row's pool of candidates (`cand_items` / `cand_scores` [n, C] as `recommend` /
+        `rerank` return them, C <= 128) by the item embedding rows: (items [n, k] int32, scores [n, k] float32) in
+        pick order from the engine's fused kernel (revisit_bpr/diversify.py), padded with -1 / -inf; `return_mmr`
+        adds the objective each pick won with.  Rows behind the optimizer step are replayed first (`sync()`).  Only
+        the MF scorer has a fused form."""
+        if not self._fusable():
+            raise NotImplementedError("diversify needs the MF logits model in float32: other scorers have no fused "
+                                      "diversification kernel")
+        eng = self.engine()
+        self.sync()
+        return eng.diversify(cand_items, cand_scores, k, lam=lam, metric=metric, scale=scale, return_mmr=return_mmr)
+
+    def recommend_diverse(self, users: torch.Tensor, k: int, *, pool: int = 100, lam: float = 0.7,
+                          metric: str = "cosine", scale: str = "minmax", exclude_seen: bool = True):
+        """`recommend(pool)` followed by `diversify(k)`: the `k` picks of greedy MMR from every user's `pool` best
+        items.  A user bias is added to the returned scores after the picks are made (it shifts a whole row and
+        plays no part in the choice).  Rows behind the optimizer step are replayed first (`sync()`).  Only the MF
+        scorer has a fused form."""
+        if not self._fusable():
+            raise NotImplementedError("recommend_diverse needs the MF logits model in float32: other scorers have "
+                                      "no fused top-K kernel")
+        eng = self.engine()
+        self.sync()
+        items, scores = eng.recommend_diverse(users, k, pool=pool, lam=lam, metric=metric, scale=scale,
+                                              exclude_seen=exclude_seen)
+        ub = self.logits_model._user_bias
+        if ub is not None:
+            scores += ub.detach()[users.reshape(-1).long()].unsqueeze(1)
+        return items, scores
+
     def fold_in(self, indptr: torch.Tensor, items: torch.Tensor, *, epochs: int, lr: float, **kwargs) -> torch.Tensor:
         """User rows [n, d] for NEW users (the rows of the CSR `indptr` int64 / `items` int32) learnt against the
         model's frozen item table and item bias by the engine's fold-in kernel (revisit_bpr/foldin.py holds the

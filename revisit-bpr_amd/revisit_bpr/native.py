@@ -127,6 +127,10 @@ SIGNATURES = {
     "bpr_rerank_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                 c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bpr_rerank_layout": (c_int, [c_int64, c_int32, c_int32, c_int64, c_int32, POINTER(c_int32), POINTER(c_int32)]),
+    "bpr_diversify_rows": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float,
+                                   c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bpr_diversify_layout": (c_int, [c_int64, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32),
+                                     POINTER(c_int64)]),
     "bpr_rank_workspace": (c_int, [c_int64, c_int64, c_int32, c_int32, POINTER(c_int64)]),
     "bpr_rank_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, POINTER(c_int32)]),
     "bpr_rank_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
