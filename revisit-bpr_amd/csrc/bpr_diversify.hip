@@ -20,8 +20,8 @@
 //       every thread then reads its similarity to the winner: a row of a tile (contiguous) or a column of one
 //       (stride 33), 32 lanes on 32 banks either way.
 //
-// Numerics.  dot(a, b) is k_topk's chain bit for bit (one fp32 accumulator from +0, per 8 features 0, 4, 1, 5, 2, 6,
-// 3, 7, every chunk of 32 run to its end over staged zeros): it IS that MFMA sequence, with item rows on both sides.
+// Numerics.  dot(a, b) is k_topk's chain bit for bit (one fp32 accumulator from +0, every chunk of 32 run to its end
+// over staged zeros): it IS that MFMA sequence (mfma_block1, bpr_topk_shared.h), with item rows on both sides.
 // fp32 multiplication commutes, so G[a][b] and G[b][a] are the same bits and half the matrix suffices.  Cosine is
 // dot * (rn(a) * rn(b)) — the product of the two norms first, so that it is symmetric too; rn = 1 / sqrt(dot(v, v)),
 // correctly rounded: spelt sqrtf and `/`, with -fhip-fp32-correctly-rounded-divide-sqrt pinned for this object by the
@@ -31,7 +31,7 @@
 //
 // Order.  The key's last field is the candidate's position among the row's eligible candidates, which only ever
 // separates copies of one (v, relevance, id): the OUTPUT is a function of the multiset of (id, relevance) pairs.
-// The small helpers (load4) are private copies, as in bpr_rerank.hip ("Not shared").
+// load4 and the chain are bpr_topk_shared.h's.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -41,11 +41,10 @@
 
 #include "bpr_diversify_plan.h"
 #include "bpr_host.h"
+#include "bpr_topk_shared.h"
 
 namespace bpr {
 namespace dv {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct Key {
   float v;      // the objective (a NaN counts, and is reported, as -inf)
@@ -77,17 +76,6 @@ __device__ __forceinline__ bool better(const Key& a, const Key& b) {
   if (a.rel != b.rel) return a.rel > b.rel;
   if (a.id != b.id) return a.id < b.id;
   return a.pos < b.pos;
-}
-
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float* __restrict__ row, int kk, int d) {
-  if (VEC) return kk < d ? *reinterpret_cast<const float4*>(row + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 v;
-  v.x = kk + 0 < d ? row[kk + 0] : 0.f;
-  v.y = kk + 1 < d ? row[kk + 1] : 0.f;
-  v.z = kk + 2 < d ? row[kk + 2] : 0.f;
-  v.w = kk + 3 < d ? row[kk + 3] : 0.f;
-  return v;
 }
 
 // VEC: d % 4 == 0 and a 16-byte aligned item table (16-byte global loads); else element loads.
@@ -186,7 +174,7 @@ __global__ __launch_bounds__(DIVERSIFY_THREADS) void k_diversify(const DivArgs a
       for (int c = 0; c < nch; ++c) {
         __syncthreads();  // the chunk before is read
 #pragma unroll
-        for (int m = 0; m < NF; ++m) {
+        for (int m = 0; m < NF; ++m) {  // (BPR_STASH_CHUNK's loop, for the tiles the row fills only)
           const int f = tid + DIVERSIFY_THREADS * m;
           if ((f >> 3) < Ep) *reinterpret_cast<float4*>(sQ + (f >> 3) * LD + 4 * (f & 7)) = qreg[m];
         }
@@ -199,10 +187,7 @@ __global__ __launch_bounds__(DIVERSIFY_THREADS) void k_diversify(const DivArgs a
             if (!own[s]) continue;  // (wave-uniform)
             const float4 a4 = *reinterpret_cast<const float4*>(sQ + aoff[s] + 8 * blk);
             const float4 b4 = *reinterpret_cast<const float4*>(sQ + boff[s] + 8 * blk);
-            acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc[s], 0, 0, 0);
-            acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc[s], 0, 0, 0);
-            acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc[s], 0, 0, 0);
-            acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc[s], 0, 0, 0);
+            mfma_block1(a4, b4, acc[s]);
           }
         }
       }

@@ -8,7 +8,8 @@
 // rows of ONE query); every query keeps in LDS a threshold tau = its k-th best at the last compaction, a buffer of
 // k + 128 candidates and a count; after a table tile (A) every lane counts its eligible scores that beat tau, (B) a
 // query whose buffer could overflow is compacted by one wave to its k best, sorted, (C) what still beats the
-// tightened tau is appended.  The dot product is k_topk's fmaf chain, bit for bit.
+// tightened tau is appended.  The dot product is k_topk's fmaf chain, bit for bit: staging, the chain, Cand, better,
+// compact_row and step (B) are the same code (bpr_topk_shared.h), and the slices are merged by k_topk_merge.
 //
 // What differs from k_topk:
 //   - queries are gathered through `rows` from X, which need not be the table;
@@ -20,7 +21,7 @@
 //     candidate.  profiles/similar_probe.txt measures what that is worth.
 //
 // Cosine pre-pass (k_neighbors_norms): one thread per row folds v_f * v_f into ONE fmaf chain from 0 over the
-// features in the dot product's own order (per 8 features 0, 4, 1, 5, 2, 6, 3, 7), so ss(v) == dot(v, v) bit for
+// features in the dot product's own order (fma_chain8, bpr_topk_shared.h), so ss(v) == dot(v, v) bit for
 // bit and a row meets its own copy at (ss * rn) * rn, six roundings from 1; rn = 1 / sqrt(ss), both correctly
 // rounded, is stored if ss > 0, the marker -1 otherwise (a zero row, or one with a NaN): such a table row is never
 // returned, such a query gets a padded row.  The norms of the N table rows and the n queries are written on every
@@ -30,9 +31,6 @@
 // with OCML_BASIC_ROUNDED_OPERATIONS, whose __ocml_sqrt_rte_f32 / __ocml_div_rte_f32 the device library of this
 // toolchain does not carry, and its __fdiv_rn is `/`.  tests/test_gpu_similar.py holds the bits to numpy's IEEE
 // float32, so a build that rounds otherwise fails there.
-//
-// Cand, better, compact_row, load4 and the merge kernel are private copies of bpr_topk.hip's (DESIGN 4.10 says why
-// they are not shared); they live in their own namespace.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -42,16 +40,10 @@
 
 #include "bpr_host.h"
 #include "bpr_neighbors_plan.h"
+#include "bpr_topk_shared.h"
 
 namespace bpr {
 namespace nbr {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Cand {
-  float s;
-  int32_t i;
-};
 
 struct NeighborsArgs {
   const float* X;
@@ -70,51 +62,7 @@ struct NeighborsArgs {
   int32_t* out_ids;   // [n, slices, k]
 };
 
-// the order of the result: score descending, ties by ascending id (never true for a NaN score)
-__device__ __forceinline__ bool better(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
-
-// One wave: the c <= k + TOPK_TI <= 256 candidates of a query -> its min(c, k) best, sorted, in buf[0 ..); tau and
-// count follow.  Every lane of the wave calls it with the same arguments.
-__device__ __forceinline__ void compact_row(Cand* buf, int c, int k, int lane, Cand* tau, int* cnt) {
-  Cand e[4];
-  int rank[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int idx = lane + 64 * q;
-    e[q] = idx < c ? buf[idx] : Cand{0.0f, 0};
-    rank[q] = 0;
-  }
-  for (int j = 0; j < c; ++j) {
-    const Cand o = buf[j];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) rank[q] += better(o.s, o.i, e[q].s, e[q].i) ? 1 : 0;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (lane + 64 * q < c && rank[q] < k) {
-      buf[rank[q]] = e[q];
-      if (rank[q] == k - 1) *tau = e[q];
-    }
-  }
-  if (lane == 0) *cnt = c < k ? c : k;
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float* __restrict__ row, int kk, int d) {
-  if (VEC) return kk < d ? *reinterpret_cast<const float4*>(row + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 v;
-  v.x = kk + 0 < d ? row[kk + 0] : 0.f;
-  v.y = kk + 1 < d ? row[kk + 1] : 0.f;
-  v.z = kk + 2 < d ? row[kk + 2] : 0.f;
-  v.w = kk + 3 < d ? row[kk + 3] : 0.f;
-  return v;
-}
-
-// rn of the N table rows, then of the n queries: one thread per row (the order of the chain: the head of this file;
+// rn of the N table rows, then of the n queries: one thread per row (the order of the chain: bpr_topk_shared.h;
 // features past d are read as zeros, and fmaf(0, 0, ss) == ss)
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_neighbors_norms(const float* __restrict__ T, int64_t N,
@@ -136,14 +84,7 @@ __global__ __launch_bounds__(256) void k_neighbors_norms(const float* __restrict
   float ss = 0.f;
   for (int f = 0; f < d; f += 8) {
     const float4 lo = load4<VEC>(src, f, d), hi = load4<VEC>(src, f + 4, d);
-    ss = __fmaf_rn(lo.x, lo.x, ss);
-    ss = __fmaf_rn(hi.x, hi.x, ss);
-    ss = __fmaf_rn(lo.y, lo.y, ss);
-    ss = __fmaf_rn(hi.y, hi.y, ss);
-    ss = __fmaf_rn(lo.z, lo.z, ss);
-    ss = __fmaf_rn(hi.z, hi.z, ss);
-    ss = __fmaf_rn(lo.w, lo.w, ss);
-    ss = __fmaf_rn(hi.w, hi.w, ss);
+    ss = fma_chain8(lo, hi, lo, hi, ss);
   }
   *dst = ss > 0.f ? 1.0f / sqrtf(ss) : -1.0f;  // (correctly rounded: the head of this file)
 }
@@ -207,16 +148,8 @@ __global__ __launch_bounds__(256) void k_neighbors(const NeighborsArgs a) {
     }
   };
   auto stash = [&](int c) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int f = tid + 256 * m;
-      *reinterpret_cast<float4*>(sT + (f >> 3) * LD + 4 * (f & 7)) = treg[m];
-    }
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int f = tid + 256 * m;
-      *reinterpret_cast<float4*>(sX + (f >> 3) * LD + 4 * (f & 7)) = xreg[m];
-    }
+    BPR_STASH_CHUNK(sT, treg, 4, tid, 256);
+    BPR_STASH_CHUNK(sX, xreg, 2, tid, 256);
     // (read in (A) of this tile only, which a barrier separates from the next tile's first stash)
     if (COS && c == 0 && tid < TI) sRnT[tid] = rnreg;
   };
@@ -236,20 +169,7 @@ __global__ __launch_bounds__(256) void k_neighbors(const NeighborsArgs a) {
       __syncthreads();
       if (c + 1 < nch) fetch(t, c + 1);
       else if (t + 1 < t1) fetch(t + 1, 0);
-#pragma unroll
-      for (int blk = 0; blk < KC / 8; ++blk) {
-        const float4 a4 = *reinterpret_cast<const float4*>(ta + 8 * blk);
-        const float4 b0 = *reinterpret_cast<const float4*>(xb0 + 8 * blk);
-        const float4 b1 = *reinterpret_cast<const float4*>(xb1 + 8 * blk);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b0.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b1.x, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b0.y, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b1.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b0.z, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b1.z, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b0.w, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b1.w, acc1, 0, 0, 0);
-      }
+      mfma_chunk2(ta, xb0, xb1, acc0, acc1);
     }
 
     // ---- epilogue of the tile: register q of the lane is table row jbase + (q & 3) + 8 (q >> 2) of queries r, 32 + r
@@ -278,11 +198,8 @@ __global__ __launch_bounds__(256) void k_neighbors(const NeighborsArgs a) {
       if (m1) atomicAdd(&sNeed[32 + r], __popc(m1));
     }
     __syncthreads();
-    // (B) queries whose buffer might not take them all: down to the k best (then count <= k, and a tile adds <= TI)
-    for (int row = w; row < TU; row += 4) {
-      const int c = min(sCnt[row], cap);
-      if (c + sNeed[row] > cap) compact_row(sBuf + row * cap, c, a.k, lane, &sTau[row], &sCnt[row]);
-    }
+    // (B) queries whose buffer might not take them all are compacted, which tightens tau
+    compact_overflowing_rows(sBuf, sCnt, sNeed, sTau, cap, a.k, w, lane);
     __syncthreads();
     // (C) append what still beats the threshold: no global memory is touched
     if (tid < TU) sNeed[tid] = 0;
@@ -320,66 +237,6 @@ __global__ __launch_bounds__(256) void k_neighbors(const NeighborsArgs a) {
   }
 }
 
-// One workgroup per query: S sorted lists of k (padded with id -1 at the end) -> the k best, sorted.
-__global__ __launch_bounds__(256) void k_neighbors_merge(const float* __restrict__ ps, const int32_t* __restrict__ pi,
-                                                         int S, int k, float* __restrict__ out_s,
-                                                         int32_t* __restrict__ out_i) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  Cand* const sE = reinterpret_cast<Cand*>(smem);  // [S][k]
-  int* const sLen = reinterpret_cast<int*>(sE + S * k);
-  const int tid = threadIdx.x;
-  const int64_t row = blockIdx.x;
-  const int64_t base = row * S * k;
-  if (tid < S) sLen[tid] = 0;
-  __syncthreads();
-  for (int e = tid; e < S * k; e += 256) {
-    const Cand c = {ps[base + e], pi[base + e]};
-    sE[e] = c;
-    if (c.i >= 0) atomicAdd(&sLen[e / k], 1);
-  }
-  __syncthreads();
-  int total = 0;
-  for (int s = 0; s < S; ++s) total += sLen[s];
-  for (int e = tid; e < S * k; e += 256) {
-    const int s = e / k, j = e - s * k;
-    if (j >= sLen[s]) continue;
-    const Cand c = sE[e];
-    int rank = j;
-    for (int b = 0; b < S && rank < k; ++b) {
-      if (b == s) continue;
-      const Cand* const L = sE + b * k;
-      int lo = 0, hi = sLen[b];  // entries of list b that come before c
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (better(L[mid].s, L[mid].i, c.s, c.i)) lo = mid + 1; else hi = mid;
-      }
-      rank += lo;
-    }
-    if (rank < k) {
-      out_s[row * k + rank] = c.s;
-      out_i[row * k + rank] = c.i;
-    }
-  }
-  for (int j = (total < k ? total : k) + tid; j < k; j += 256) {
-    out_s[row * k + j] = -INFINITY;
-    out_i[row * k + j] = -1;
-  }
-}
-
-static int check_shape(const char* who, int64_t n, int64_t N, int32_t d, int32_t k, int32_t item_slices) {
-  if (n < 0 || N < 1 || N >= ((int64_t)1 << 31))
-    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be >= 0 and N in [1, 2^31)");
-  if (d < 1 || d > 1024) return fail(BPR_ERR_INVALID, std::string(who) + ": d must be in [1, 1024]");
-  if (k < 1 || k > TOPK_MAX)
-    return fail(BPR_ERR_INVALID, std::string(who) + ": k must be in [1, " + std::to_string(TOPK_MAX) + "]");
-  if (item_slices < 0 || item_slices > TOPK_MAX_SLICES)
-    return fail(BPR_ERR_INVALID, std::string(who) + ": item_slices must be 0 (choose) or in [1, " +
-                                     std::to_string(TOPK_MAX_SLICES) + "]");
-  if (n > 0x7FFFFFFF)  // (the merge kernel's grid is one workgroup per query)
-    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be below 2^31");
-  return BPR_OK;
-}
-
 static int check_metric(const char* who, int32_t metric) {
   if (metric != NBR_DOT && metric != NBR_COSINE)
     return fail(BPR_ERR_INVALID, std::string(who) + ": metric must be BPR_SIM_DOT (0) or BPR_SIM_COSINE (1)");
@@ -405,7 +262,7 @@ extern "C" int bpr_neighbors_workspace(int64_t n, int64_t N, int32_t d, int32_t 
                                        int32_t item_slices, int64_t* bytes_host) {
   using namespace bpr;
   if (bytes_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_neighbors_workspace: bytes_host is NULL");
-  if (int rc = nbr::check_shape("bpr_neighbors_workspace", n, N, d, k, item_slices)) return rc;
+  if (int rc = check_topk_shape("bpr_neighbors_workspace", n, N, d, k, item_slices, "N")) return rc;
   if (int rc = nbr::check_metric("bpr_neighbors_workspace", metric)) return rc;
   *bytes_host = neighbors_workspace_bytes(n, N, k, metric, item_slices);
   return BPR_OK;
@@ -415,7 +272,7 @@ extern "C" int bpr_neighbors_slices(int64_t n, int64_t N, int32_t d, int32_t k, 
                                     int32_t* slices_host) {
   using namespace bpr;
   if (slices_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_neighbors_slices: slices_host is NULL");
-  if (int rc = nbr::check_shape("bpr_neighbors_slices", n, N, d, k, item_slices)) return rc;
+  if (int rc = check_topk_shape("bpr_neighbors_slices", n, N, d, k, item_slices, "N")) return rc;
   *slices_host = plan_neighbors(n, N, k, NBR_DOT, item_slices).t.slices;
   return BPR_OK;
 }
@@ -426,7 +283,7 @@ extern "C" int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int
                                   float* scores_out, void* hip_stream) {
   using namespace bpr;
   using namespace bpr::nbr;
-  if (int rc = check_shape("bpr_neighbors_rows", n, N, d, k, item_slices)) return rc;
+  if (int rc = check_topk_shape("bpr_neighbors_rows", n, N, d, k, item_slices, "N")) return rc;
   if (int rc = check_metric("bpr_neighbors_rows", metric)) return rc;
   if (first < 0) return fail(BPR_ERR_INVALID, "bpr_neighbors_rows: first must be >= 0");
   if (n > 0 && (!X || !T || !rows || !ids_out || !scores_out))
@@ -465,11 +322,7 @@ extern "C" int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int
   if (metric == NBR_COSINE) rc = vec ? launch<true, true>(a, grid, p.lds, stream) : launch<false, true>(a, grid, p.lds, stream);
   else rc = vec ? launch<true, false>(a, grid, p.lds, stream) : launch<false, false>(a, grid, p.lds, stream);
   if (rc != BPR_OK) return rc;
-  if (S > 1) {
-    hipLaunchKernelGGL(k_neighbors_merge, dim3((unsigned)n), dim3(256), p.t.merge_lds, stream, part_s, part_i, S, k,
-                       scores_out, ids_out);
-    BPR_HIP_CHECK(hipGetLastError());
-  }
+  if (S > 1) return launch_topk_merge(part_s, part_i, n, S, k, p.t.merge_lds, scores_out, ids_out, stream);
   return BPR_OK;
 }
 
@@ -479,8 +332,8 @@ extern "C" int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int
 // Needs no GPU.
 extern "C" int bpr_test_neighbors_plan(const int64_t* in, int64_t* out, int64_t* bounds) {
   using namespace bpr;
-  if (int rc = nbr::check_shape("bpr_test_neighbors_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3],
-                                (int32_t)in[5]))
+  if (int rc = check_topk_shape("bpr_test_neighbors_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3],
+                                (int32_t)in[5], "N"))
     return rc;
   if (int rc = nbr::check_metric("bpr_test_neighbors_plan", (int32_t)in[4])) return rc;
   const NeighborsPlan p = plan_neighbors(in[0], in[1], (int)in[3], (int)in[4], (int)in[5],

@@ -18,7 +18,7 @@
 //      rank = not_below = -1 here; an eligible one gets its score and 0 / 0.  One launch whatever the slice count,
 //      so that every slice sees the same bits.
 //   2. Ranking (k_rank<.., false>): every row's live targets (eligible, score not NaN) are sorted in LDS by the
-//      result order (rank by counting, as compact_row of bpr_topk.hip; duplicates of an id are ordered by their
+//      result order (rank by counting, as compact_row of bpr_topk_shared.h; duplicates of an id are ordered by their
 //      place in the list).  Every streamed eligible score finds by a branch-free binary search the first target it
 //      comes before and bumps that bin (runs of one bin are counted privately, as k_auc_rows does); a score equal
 //      to that of the targets just in front of its place walks them and bumps their "tied after" counter.  A prefix
@@ -31,9 +31,9 @@
 // by one binary search at the slice's first tile, and per item tile sets the bits of the entries that fall into the
 // tile in a 128-bit mask per row in LDS.  CSR traffic: one read of each row's seen list per slice.
 //
-// Numerics: the "Numerics" paragraph of bpr_topk.hip word for word — one accumulator carried through every feature
-// chunk, per 8 features the order 0, 4, 1, 5, 2, 6, 3, 7, zeros past d, the bias one fp32 add afterwards — so a
-// score's bits are k_topk's for the same pair, wherever the pair falls.
+// Numerics: k_topk's — the same staging and the same chain (bpr_topk_shared.h), one accumulator carried through
+// every feature chunk, zeros past d, the bias one fp32 add afterwards — so a score's bits are k_topk's for the same
+// pair, wherever the pair falls.
 //
 // Not measured against the composition until tools/rank_probe.py has run on the chip (profiles/rank_probe.txt).
 #include <hip/hip_runtime.h>
@@ -46,15 +46,11 @@
 
 #include "bpr_host.h"
 #include "bpr_rank_plan.h"
+#include "bpr_topk_shared.h"
 
 namespace bpr {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct RCand {
-  float s;
-  int32_t i;
-};
+static_assert(RANK_KC == TOPK_KC && RANK_LD == TOPK_LD, "k_rank stages k_topk's chunks (bpr_topk_shared.h)");
 
 struct RankArgs {
   const float* P;
@@ -76,9 +72,6 @@ struct RankArgs {
   int32_t* ws;  // slices > 1: [3][n][RANK_TMAX]
 };
 
-// the order of the result (bpr_topk.hip): score descending, ties by ascending item id; never true for a NaN score
-__device__ __forceinline__ bool rbetter(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
-
 __device__ __forceinline__ int lower_bound_i32(const int32_t* __restrict__ v, int len, int64_t x) {
   int lo = 0, hi = len;
   while (lo < hi) {
@@ -88,31 +81,20 @@ __device__ __forceinline__ int lower_bound_i32(const int32_t* __restrict__ v, in
   return lo;
 }
 
-template <bool VEC>
-__device__ __forceinline__ float4 rload4(const float* __restrict__ row, int kk, int d) {
-  if (VEC) return kk < d ? *reinterpret_cast<const float4*>(row + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 v;
-  v.x = kk + 0 < d ? row[kk + 0] : 0.f;
-  v.y = kk + 1 < d ? row[kk + 1] : 0.f;
-  v.z = kk + 2 < d ? row[kk + 2] : 0.f;
-  v.w = kk + 3 < d ? row[kk + 3] : 0.f;
-  return v;
-}
-
 // One wave: the T <= RANK_TMAX targets of a row -> its live ones sorted into L, their places in the list into perm,
 // the row's counters zeroed, *cnt = how many are live.  Every lane of the wave calls it with the same arguments.
-__device__ __forceinline__ void sort_row(const RankArgs& a, int64_t tlo, int T, int lane, RCand* L, uint16_t* perm,
+__device__ __forceinline__ void sort_row(const RankArgs& a, int64_t tlo, int T, int lane, Cand* L, uint16_t* perm,
                                          int* ht, int* cnt) {
-  RCand* const tmp = reinterpret_cast<RCand*>(ht);  // (staged through the counters' LDS: 2 T <= RANK_HT ints)
-  RCand e[2];
+  Cand* const tmp = reinterpret_cast<Cand*>(ht);  // (staged through the counters' LDS: 2 T <= RANK_HT ints)
+  Cand e[2];
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int p = lane + 64 * q;
-    e[q] = RCand{0.f, -1};
+    e[q] = Cand{0.f, -1};
     if (p < T) {
       const float s = a.score[tlo + p];
       const bool live = a.rank[tlo + p] == 0 && s == s;
-      e[q] = RCand{s, live ? a.titems[tlo + p] : -1};
+      e[q] = Cand{s, live ? a.titems[tlo + p] : -1};
       tmp[p] = e[q];
     }
   }
@@ -120,11 +102,11 @@ __device__ __forceinline__ void sort_row(const RankArgs& a, int64_t tlo, int T, 
   __builtin_amdgcn_wave_barrier();
   int pos[2] = {0, 0};
   for (int j = 0; j < T; ++j) {
-    const RCand o = tmp[j];
+    const Cand o = tmp[j];
     if (o.i < 0) continue;
 #pragma unroll
     for (int q = 0; q < 2; ++q)
-      pos[q] += (rbetter(o.s, o.i, e[q].s, e[q].i) || (o.s == e[q].s && o.i == e[q].i && j < lane + 64 * q)) ? 1 : 0;
+      pos[q] += (better(o.s, o.i, e[q].s, e[q].i) || (o.s == e[q].s && o.i == e[q].i && j < lane + 64 * q)) ? 1 : 0;
   }
   const int live = __popcll(__ballot(e[0].i >= 0)) + __popcll(__ballot(e[1].i >= 0));
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -158,7 +140,7 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
   int* const sT = sSeenLen + TR;
   int* const sOwner = sT + TR;                                   // PRE: [TI]
   uint32_t* const sMask = reinterpret_cast<uint32_t*>(sT + TR);  // ranking: [TR][4], bit set = seen
-  RCand* const sL = reinterpret_cast<RCand*>(sMask + TR * 4);    // [TR][TM]
+  Cand* const sL = reinterpret_cast<Cand*>(sMask + TR * 4);    // [TR][TM]
   int* const sHT = reinterpret_cast<int*>(sL + TR * TM);         // [TR][HT]
   uint16_t* const sPerm = reinterpret_cast<uint16_t*>(sHT + TR * HT);  // [TR][TM]
 
@@ -243,26 +225,18 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
     for (int m = 0; m < 4; ++m) {
       const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
       const int64_t item = item_of(t, row);
-      qreg[m] = item >= 0 ? rload4<VEC>(a.Q + item * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
+      qreg[m] = item >= 0 ? load4<VEC>(a.Q + item * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
       const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
       const int u = sUser[row];
-      preg[m] = u >= 0 ? rload4<VEC>(a.P + (int64_t)u * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
+      preg[m] = u >= 0 ? load4<VEC>(a.P + (int64_t)u * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   };
   auto stash = [&]() {
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int f = tid + 256 * m;
-      *reinterpret_cast<float4*>(sQ + (f >> 3) * LD + 4 * (f & 7)) = qreg[m];
-    }
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int f = tid + 256 * m;
-      *reinterpret_cast<float4*>(sP + (f >> 3) * LD + 4 * (f & 7)) = preg[m];
-    }
+    BPR_STASH_CHUNK(sQ, qreg, 4, tid, 256);
+    BPR_STASH_CHUNK(sP, preg, 2, tid, 256);
   };
 
   const int nch = (a.d + KC - 1) / KC;
@@ -305,20 +279,7 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
       }
       if (c + 1 < nch) fetch(t, c + 1);
       else if (t + 1 < t1) fetch(t + 1, 0);
-#pragma unroll
-      for (int blk = 0; blk < KC / 8; ++blk) {
-        const float4 a4 = *reinterpret_cast<const float4*>(qa + 8 * blk);
-        const float4 b0 = *reinterpret_cast<const float4*>(pb0 + 8 * blk);
-        const float4 b1 = *reinterpret_cast<const float4*>(pb1 + 8 * blk);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b0.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b1.x, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b0.y, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b1.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b0.z, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b1.z, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b0.w, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b1.w, acc1, 0, 0, 0);
-      }
+      mfma_chunk2(qa, pb0, pb1, acc0, acc1);
     }
     __syncthreads();  // the tile's owners / seen masks are complete
 
@@ -349,8 +310,8 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
       const int64_t ibase = t * TI + lbase;
       const uint32_t seen0 = sMask[r * 4 + w], seen1 = sMask[(32 + r) * 4 + w];
       const int T0 = sT[r], T1 = sT[32 + r];
-      const RCand* const L0 = sL + r * TM;
-      const RCand* const L1 = sL + (32 + r) * TM;
+      const Cand* const L0 = sL + r * TM;
+      const Cand* const L1 = sL + (32 + r) * TM;
       float s0[16], s1[16];
       int p0[16], p1[16];
 #pragma unroll
@@ -368,12 +329,12 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
           const int item = (int)(ibase + (q & 3) + 8 * (q >> 2));
           const int c0 = p0[q] + step, c1 = p1[q] + step;
           if (c0 <= T0) {
-            const RCand e = L0[c0 - 1];
-            if (!rbetter(s0[q], item, e.s, e.i)) p0[q] = c0;
+            const Cand e = L0[c0 - 1];
+            if (!better(s0[q], item, e.s, e.i)) p0[q] = c0;
           }
           if (c1 <= T1) {
-            const RCand e = L1[c1 - 1];
-            if (!rbetter(s1[q], item, e.s, e.i)) p1[q] = c1;
+            const Cand e = L1[c1 - 1];
+            if (!better(s1[q], item, e.s, e.i)) p1[q] = c1;
           }
         }
       }

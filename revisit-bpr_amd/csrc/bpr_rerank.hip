@@ -20,16 +20,15 @@
 //       it, (B) compact the buffer of k + tile entries when they might not fit, (C) append what beats the tightened
 //       tau.  Nothing is dropped whatever the data.
 //
-// Numerics.  s(u, i) is bpr_topk_rows' score bit for bit: one fp32 accumulator from +0 through one fmaf chain over
-// the features in k_topk's order (per 8 features: 0, 4, 1, 5, 2, 6, 3, 7 — what v_mfma_f32_32x32x2_f32 computes
-// there, a k-ordered fmaf chain), every chunk of 32 run to its end with zeros staged past d on both sides, then
-// the bias as one fp32 add.  k_neighbors_norms (bpr_neighbors.hip) reproduces the MFMA chain the same way.
+// Numerics.  s(u, i) is bpr_topk_rows' score bit for bit: one fp32 accumulator from +0 through k_topk's chain in
+// one thread (fma_chain8, bpr_topk_shared.h, which states the order), every chunk of 32 run to its end with zeros
+// staged past d on both sides, then the bias as one fp32 add.
 //
 // Order.  Duplicates make (score desc, id asc) a preorder, and rank counting needs distinct ranks, so the order here
 // has a third key: the candidate's position in its list.  Two entries that differ only in position are the same
 // (score, id) pair to the caller, so the OUTPUT is a function of the multiset of candidates alone: not of their
 // order, of the row's place, of the team or of the grid.  Because of the third key Cand, better and compact_row are
-// copies of bpr_topk.hip's, adapted, not shared with it: a shared header would have had to change k_topk's own.
+// this file's own (DESIGN 4.10 records why compact_row is not the shared one); the rest is bpr_topk_shared.h's.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -39,6 +38,7 @@
 
 #include "bpr_host.h"
 #include "bpr_rerank_plan.h"
+#include "bpr_topk_shared.h"
 
 namespace bpr {
 namespace rr {
@@ -73,15 +73,6 @@ __device__ __forceinline__ bool better(const Cand& a, const Cand& b) {
   return a.s > b.s || (a.s == b.s && (a.i < b.i || (a.i == b.i && a.p < b.p)));
 }
 
-__device__ __forceinline__ bool in_sorted(const int32_t* __restrict__ v, int64_t len, int item) {
-  int64_t lo = 0, hi = len;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (v[mid] < item) lo = mid + 1; else hi = mid;
-  }
-  return lo < len && v[lo] == item;
-}
-
 // One wave: the c <= 64 * QN candidates of a row -> its min(c, k) best, sorted, in buf[0 ..); tau and count follow
 // (k >= 1).  Every lane of the wave calls it with the same arguments.
 template <int QN>
@@ -111,17 +102,6 @@ __device__ __forceinline__ void compact_row(Cand* buf, int c, int k, int lane, C
   if (lane == 0) *cnt = c < k ? c : k;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
-}
-
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float* __restrict__ row, int kk, int d) {
-  if (VEC) return kk < d ? *reinterpret_cast<const float4*>(row + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 v;
-  v.x = kk + 0 < d ? row[kk + 0] : 0.f;
-  v.y = kk + 1 < d ? row[kk + 1] : 0.f;
-  v.z = kk + 2 < d ? row[kk + 2] : 0.f;
-  v.w = kk + 3 < d ? row[kk + 3] : 0.f;
-  return v;
 }
 
 // the team's barrier: the workgroup's, or (a wave is its own team, and the waves of a workgroup walk rows of
@@ -209,11 +189,7 @@ __global__ __launch_bounds__(RERANK_THREADS) void k_rerank(const RerankArgs a, c
       float acc = 0.f;
       const float* const q = sQ + tid * LD;
       for (int c = 0; c < nch; ++c) {
-#pragma unroll
-        for (int m = 0; m < NF; ++m) {
-          const int f = tid + TEAM * m;
-          *reinterpret_cast<float4*>(sQ + (f >> 3) * LD + 4 * (f & 7)) = qreg[m];
-        }
+        BPR_STASH_CHUNK(sQ, qreg, NF, tid, TEAM);
         team_sync<TEAM>();
         if (c + 1 < nch) fetch(c + 1);
         const float* const p = sP + c * KC;
@@ -223,14 +199,7 @@ __global__ __launch_bounds__(RERANK_THREADS) void k_rerank(const RerankArgs a, c
           const float4 q1 = *reinterpret_cast<const float4*>(q + 8 * blk + 4);
           const float4 p0 = *reinterpret_cast<const float4*>(p + 8 * blk);
           const float4 p1 = *reinterpret_cast<const float4*>(p + 8 * blk + 4);
-          acc = __fmaf_rn(q0.x, p0.x, acc);
-          acc = __fmaf_rn(q1.x, p1.x, acc);
-          acc = __fmaf_rn(q0.y, p0.y, acc);
-          acc = __fmaf_rn(q1.y, p1.y, acc);
-          acc = __fmaf_rn(q0.z, p0.z, acc);
-          acc = __fmaf_rn(q1.z, p1.z, acc);
-          acc = __fmaf_rn(q0.w, p0.w, acc);
-          acc = __fmaf_rn(q1.w, p1.w, acc);
+          acc = fma_chain8(q0, q1, p0, p1, acc);
         }
         team_sync<TEAM>();  // the chunk is read: the next one may be written over it
       }

@@ -23,14 +23,15 @@
 // orders it by a strict total order: the output is a pure function of the inputs.
 //
 // Numerics.  An accumulator is carried through every feature chunk, so s(u, i) is one fmaf chain over the
-// features in a fixed order (per 8 features: 0, 4, 1, 5, 2, 6, 3, 7 — a lane half reads 4 consecutive features
-// with one 16-byte LDS read), the same wherever (u, i) falls in a tile, a slice or the user list; features past d
-// are staged as zeros on both sides.  The bias is one fp32 add after the chain.
+// features in a fixed order (bpr_topk_shared.h states it, and why it is a contract), the same wherever (u, i) falls
+// in a tile, a slice or the user list; features past d are staged as zeros on both sides.  The bias is one fp32 add
+// after the chain.
 //
 // Item slices.  Few users (a serving call, a small evaluation) do not fill the chip: the item tiles are then cut
 // into slices, grid = user tiles x slices, each slice writes its sorted top-k to the workspace and k_topk_merge
 // merges a row's slices (each entry's rank = its index + binary searches in the other slices).  Layout and sizes:
-// bpr_topk_plan.h.
+// bpr_topk_plan.h.  What the other serving kernels use as well — staging, the chain, Cand / better / compact_row —
+// is bpr_topk_shared.h; its two host functions (check_topk_shape, launch_topk_merge) are defined here.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -40,15 +41,9 @@
 
 #include "bpr_host.h"
 #include "bpr_topk_plan.h"
+#include "bpr_topk_shared.h"
 
 namespace bpr {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Cand {
-  float s;
-  int32_t i;
-};
 
 struct TopkArgs {
   const float* P;
@@ -65,59 +60,6 @@ struct TopkArgs {
   float* out_scores;   // [n, slices, k]
   int32_t* out_items;  // [n, slices, k]
 };
-
-// the order of the result: score descending, ties by ascending item id (never true for a NaN score)
-__device__ __forceinline__ bool better(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
-
-__device__ __forceinline__ bool in_sorted(const int32_t* __restrict__ v, int len, int item) {
-  int lo = 0, hi = len;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (v[mid] < item) lo = mid + 1; else hi = mid;
-  }
-  return lo < len && v[lo] == item;
-}
-
-// One wave: the c <= k + TOPK_TI <= 256 candidates of a row -> its min(c, k) best, sorted, in buf[0 ..); tau and
-// count follow.  Every lane of the wave calls it with the same arguments.
-__device__ __forceinline__ void compact_row(Cand* buf, int c, int k, int lane, Cand* tau, int* cnt) {
-  Cand e[4];
-  int rank[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int idx = lane + 64 * q;
-    e[q] = idx < c ? buf[idx] : Cand{0.0f, 0};
-    rank[q] = 0;
-  }
-  for (int j = 0; j < c; ++j) {
-    const Cand o = buf[j];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) rank[q] += better(o.s, o.i, e[q].s, e[q].i) ? 1 : 0;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (lane + 64 * q < c && rank[q] < k) {
-      buf[rank[q]] = e[q];
-      if (rank[q] == k - 1) *tau = e[q];
-    }
-  }
-  if (lane == 0) *cnt = c < k ? c : k;
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float* __restrict__ row, int kk, int d) {
-  if (VEC) return kk < d ? *reinterpret_cast<const float4*>(row + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 v;
-  v.x = kk + 0 < d ? row[kk + 0] : 0.f;
-  v.y = kk + 1 < d ? row[kk + 1] : 0.f;
-  v.z = kk + 2 < d ? row[kk + 2] : 0.f;
-  v.w = kk + 3 < d ? row[kk + 3] : 0.f;
-  return v;
-}
 
 // VEC: d % 4 == 0 and 16-byte aligned tables (16-byte global loads); else element loads.
 template <bool VEC>
@@ -178,16 +120,8 @@ __global__ __launch_bounds__(256) void k_topk(const TopkArgs a) {
     }
   };
   auto stash = [&]() {
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int f = tid + 256 * m;
-      *reinterpret_cast<float4*>(sQ + (f >> 3) * LD + 4 * (f & 7)) = qreg[m];
-    }
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int f = tid + 256 * m;
-      *reinterpret_cast<float4*>(sP + (f >> 3) * LD + 4 * (f & 7)) = preg[m];
-    }
+    BPR_STASH_CHUNK(sQ, qreg, 4, tid, 256);
+    BPR_STASH_CHUNK(sP, preg, 2, tid, 256);
   };
 
   const int nch = (a.d + KC - 1) / KC;
@@ -205,20 +139,7 @@ __global__ __launch_bounds__(256) void k_topk(const TopkArgs a) {
       __syncthreads();
       if (c + 1 < nch) fetch(t, c + 1);
       else if (t + 1 < t1) fetch(t + 1, 0);
-#pragma unroll
-      for (int blk = 0; blk < KC / 8; ++blk) {
-        const float4 a4 = *reinterpret_cast<const float4*>(qa + 8 * blk);
-        const float4 b0 = *reinterpret_cast<const float4*>(pb0 + 8 * blk);
-        const float4 b1 = *reinterpret_cast<const float4*>(pb1 + 8 * blk);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b0.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b1.x, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b0.y, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b1.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b0.z, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b1.z, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b0.w, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b1.w, acc1, 0, 0, 0);
-      }
+      mfma_chunk2(qa, pb0, pb1, acc0, acc1);
     }
 
     // ---- epilogue of the item tile: register q of the lane is item ibase + (q & 3) + 8 (q >> 2) of users r, 32 + r
@@ -247,11 +168,8 @@ __global__ __launch_bounds__(256) void k_topk(const TopkArgs a) {
       if (m1) atomicAdd(&sNeed[32 + r], __popc(m1));
     }
     __syncthreads();
-    // (B) rows whose buffer might not take them all: down to the k best (then count <= k, and a tile adds <= TI)
-    for (int row = w; row < TU; row += 4) {
-      const int c = min(sCnt[row], cap);
-      if (c + sNeed[row] > cap) compact_row(sBuf + row * cap, c, a.k, lane, &sTau[row], &sCnt[row]);
-    }
+    // (B) rows whose buffer might not take them all are compacted, which tightens tau
+    compact_overflowing_rows(sBuf, sCnt, sNeed, sTau, cap, a.k, w, lane);
     __syncthreads();
     // (C) append what still beats the threshold and the user has not seen
     if (tid < TU) sNeed[tid] = 0;
@@ -343,9 +261,10 @@ __global__ __launch_bounds__(256) void k_topk_merge(const float* __restrict__ ps
   }
 }
 
-static int check_shape(const char* who, int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices) {
-  if (n < 0 || I < 1 || I >= ((int64_t)1 << 31))
-    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be >= 0 and I in [1, 2^31)");
+int check_topk_shape(const char* who, int64_t n, int64_t rows, int32_t d, int32_t k, int32_t item_slices,
+                     const char* rows_name) {
+  if (n < 0 || rows < 1 || rows >= ((int64_t)1 << 31))
+    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be >= 0 and " + rows_name + " in [1, 2^31)");
   if (d < 1 || d > 1024) return fail(BPR_ERR_INVALID, std::string(who) + ": d must be in [1, 1024]");
   if (k < 1 || k > TOPK_MAX)
     return fail(BPR_ERR_INVALID, std::string(who) + ": k must be in [1, " + std::to_string(TOPK_MAX) + "]");
@@ -357,13 +276,32 @@ static int check_shape(const char* who, int64_t n, int64_t I, int32_t d, int32_t
   return BPR_OK;
 }
 
+int launch_topk_merge(const float* part_s, const int32_t* part_i, int64_t n, int S, int k, size_t merge_lds,
+                      float* out_s, int32_t* out_i, hipStream_t stream) {
+  hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)n), dim3(256), merge_lds, stream, part_s, part_i, S, k, out_s,
+                     out_i);
+  BPR_HIP_CHECK(hipGetLastError());
+  return BPR_OK;
+}
+
+template <bool VEC>
+static int launch(const TopkArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
+  // one workgroup may ask for most of a CU's LDS: past 64 KiB that is a per-function attribute (set on every
+  // call: the process may hold several devices, and the call costs nothing next to a launch)
+  BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk<VEC>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)topk_lds_bytes(TOPK_MAX)));
+  hipLaunchKernelGGL(k_topk<VEC>, grid, dim3(256), lds, stream, a);
+  BPR_HIP_CHECK(hipGetLastError());
+  return BPR_OK;
+}
+
 }  // namespace bpr
 
 extern "C" int bpr_topk_workspace(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices,
                                   int64_t* bytes_host) {
   using namespace bpr;
   if (bytes_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_topk_workspace: bytes_host is NULL");
-  if (int rc = check_shape("bpr_topk_workspace", n, I, d, k, item_slices)) return rc;
+  if (int rc = check_topk_shape("bpr_topk_workspace", n, I, d, k, item_slices, "I")) return rc;
   *bytes_host = topk_workspace_bytes(n, I, k, item_slices);
   return BPR_OK;
 }
@@ -371,7 +309,7 @@ extern "C" int bpr_topk_workspace(int64_t n, int64_t I, int32_t d, int32_t k, in
 extern "C" int bpr_topk_slices(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices, int32_t* slices_host) {
   using namespace bpr;
   if (slices_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_topk_slices: slices_host is NULL");
-  if (int rc = check_shape("bpr_topk_slices", n, I, d, k, item_slices)) return rc;
+  if (int rc = check_topk_shape("bpr_topk_slices", n, I, d, k, item_slices, "I")) return rc;
   *slices_host = plan_topk(n, I, k, item_slices).slices;
   return BPR_OK;
 }
@@ -381,7 +319,7 @@ extern "C" int bpr_topk_rows(const float* P, const float* Q, const float* item_b
                              int32_t k, int32_t item_slices, void* workspace, int64_t workspace_bytes,
                              int32_t* items_out, float* scores_out, void* hip_stream) {
   using namespace bpr;
-  if (int rc = check_shape("bpr_topk_rows", n, I, d, k, item_slices)) return rc;
+  if (int rc = check_topk_shape("bpr_topk_rows", n, I, d, k, item_slices, "I")) return rc;
   if (n > 0 && (!P || !Q || !users || !items_out || !scores_out))
     return fail(BPR_ERR_INVALID, "bpr_topk_rows: P, Q, users, items_out or scores_out is NULL");
   const TopkPlan p = plan_topk(n, I, k, item_slices);
@@ -400,24 +338,9 @@ extern "C" int bpr_topk_rows(const float* P, const float* Q, const float* item_b
   a.out_items = p.slices > 1 ? part_i : items_out;
   const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Q)) % 16 == 0;
   const dim3 grid((unsigned)p.user_tiles, (unsigned)p.slices);
-  // one workgroup may ask for most of a CU's LDS: past 64 KiB that is a per-function attribute (set on every
-  // call: the process may hold several devices, and the call costs nothing next to a launch)
-  const int lds_max = (int)topk_lds_bytes(TOPK_MAX);
-  if (vec) {
-    BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    hipLaunchKernelGGL(k_topk<true>, grid, dim3(256), p.lds, stream, a);
-  } else {
-    BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    hipLaunchKernelGGL(k_topk<false>, grid, dim3(256), p.lds, stream, a);
-  }
-  BPR_HIP_CHECK(hipGetLastError());
-  if (p.slices > 1) {
-    hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)n), dim3(256), p.merge_lds, stream, part_s, part_i, p.slices, k,
-                       scores_out, items_out);
-    BPR_HIP_CHECK(hipGetLastError());
-  }
+  if (int rc = vec ? launch<true>(a, grid, p.lds, stream) : launch<false>(a, grid, p.lds, stream)) return rc;
+  if (p.slices > 1)
+    return launch_topk_merge(part_s, part_i, n, p.slices, k, p.merge_lds, scores_out, items_out, stream);
   return BPR_OK;
 }
 
@@ -426,7 +349,8 @@ extern "C" int bpr_topk_rows(const float* P, const float* Q, const float* item_b
 // bounds[0 .. slices] = first item of each slice, then I.  Needs no GPU.
 extern "C" int bpr_test_topk_plan(const int64_t* in, int64_t* out, int64_t* bounds) {
   using namespace bpr;
-  if (int rc = check_shape("bpr_test_topk_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3], (int32_t)in[4]))
+  if (int rc = check_topk_shape("bpr_test_topk_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3], (int32_t)in[4],
+                                "I"))
     return rc;
   const TopkPlan p = plan_topk(in[0], in[1], (int)in[3], (int)in[4], in[5] > 0 ? (int)in[5] : TOPK_CUS);
   const int64_t v[] = {p.slices, p.user_tiles, p.item_tiles, TOPK_TU, TOPK_TI, p.cap, (int64_t)p.lds,
