@@ -565,6 +565,33 @@ int bpr_topk_rows(const float* P, const float* Q, const float* item_bias /* or N
                   void* workspace, int64_t workspace_bytes,
                   int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
 
+/* ---- deep retrieval: bpr_topk_rows for 1 <= k <= 1024, the first stage of a two-stage recommender (candidates for
+ * bpr_rerank_rows, a downstream ranker or a business-rule filter).  Its own fused kernel (csrc/bpr_retrieve.hip):
+ * the rows' candidate buffers live in the device workspace and are compacted by a sort in LDS, and a bounded number
+ * of persistent workgroups walks the user tiles, so the workspace does not grow with n beyond the slices' partial
+ * results.  Semantics are bpr_topk_rows' word for word: s(u, i) is the same fp32 fmaf chain plus one bias add (the
+ * same bits), item 0 and the user's seen row are left out, rows are sorted by score descending, ties by ascending
+ * id, a short row ends in item -1 / score -inf, a NaN score never enters, and the result is a pure function of the
+ * inputs (not of n, of a row's place in the list, of repeated users, of item_slices).  For k <= 128 it returns what
+ * bpr_topk_rows returns, bit for bit.  d in [1, 1024], item_slices in [0, 64] (0 = the library chooses; a count
+ * above 8192 / k or above the item tiles is reduced, not refused: bpr_retrieve_slices reports the count that runs),
+ * n < 2^31.  The workspace (8-byte aligned) is needed whenever n > 0.  User ids are not checked.  Arguments are
+ * validated before the device is touched; n == 0 is BPR_OK.  Context-free: runs on `hip_stream` of the current
+ * device. */
+/* bytes of device workspace bpr_retrieve_rows needs for this shape: the persistent workgroups' candidate blocks
+ * (constant in n once n passes their reach) plus, with s > 1 slices, s * n * k * 8 of partial results; item_slices
+ * 0: never less than for a smaller n */
+int bpr_retrieve_workspace(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices, int64_t* bytes_host);
+/* the slice count a call of this shape runs with; passing it back as item_slices makes bpr_retrieve_workspace
+ * answer exactly that call's need */
+int bpr_retrieve_slices(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices, int32_t* slices_host);
+int bpr_retrieve_rows(const float* P, const float* Q, const float* item_bias /* or NULL */, int64_t I, int32_t d,
+                      const int32_t* users, int64_t n,
+                      const int64_t* seen_indptr /* or NULL */, const int32_t* seen_indices,
+                      int32_t k, int32_t item_slices /* 0 = choose */,
+                      void* workspace, int64_t workspace_bytes,
+                      int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
+
 /* ---- ranking of held-out items: where each target of a row stands among the user's eligible items (the reference
  * measures through full logits: example.py:195-230 and experiments/bpr/exp.py:369-374, an argsort of I scores per
  * metric object; metrics/auc.py:70-130; metrics/map.py; the user-metrics.jsonl saver of experiments/options.py:319-351).

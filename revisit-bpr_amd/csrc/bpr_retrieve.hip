@@ -1,0 +1,393 @@
+// bpr_retrieve.hip — the deep first stage of libbprcore: the k <= 1,024 best unseen items of a list of users, fused
+// scoring + selection with no [n, I] score matrix (bpr_retrieve_rows / bpr_retrieve_workspace / bpr_retrieve_slices).
+//
+// k_topk (bpr_topk.hip) stops at k = 128 because its 64 rows keep k + 128 candidates each in LDS.  k_retrieve is the
+// same tile loop — 64 users x 128 items x 32 features at a time through LDS into exact f32 MFMA accumulators, the
+// chain of bpr_topk_shared.h, so a score has bpr_topk_rows' bits — with the rows' candidate buffers in device memory:
+// a workgroup owns one block of 64 x cap (score, id) pairs of the workspace (cap: bpr_retrieve_plan.h, a power of two
+// >= 2 k), and LDS holds the staged operands, the rows' meta data and a scratch of 4 x cap pairs.
+//
+// Selection.  Per row: a threshold tau = (score, id) — its k-th best at the last compaction — a count, and `need`.
+// After an item tile: (A) every lane counts its scores that beat tau; (B) a row whose buffer might not take them
+// (count + need > cap) is compacted by one wave: buffer -> scratch, bitonic sort by `better`, the k best and the new
+// tau back; (C) scores that beat the current tau are appended (atomic slot in LDS, the pair to device memory, every
+// store behind `pos < cap`).  compact_row's rank by counting is quadratic — no option at 2,048 entries; the network
+// is n log^2 n, 64 lanes wide.  `better` is a strict total order on what a buffer holds (ids are distinct), so the
+// sorted row does not depend on the order the appends took their slots in: the output is a pure function of the
+// inputs.  Seen items: (C) appends WITHOUT looking at the user's seen row; the compaction does, for what was
+// appended since the last one (`checked` entries at the front are known to be unseen), every lane its own binary
+// search — the tile loop never touches the CSR.  tau is then the k-th best of unseen items only, so it is the bound
+// it would be had the seen items never entered, and a seen item costs a slot until the next compaction, no more.
+//
+// Barriers.  The buffer is device memory written by some lanes of the workgroup and read by others.  (C) of a tile
+// and (B) of a later one are separated by the __syncthreads of the chunk loop and the one after (A); (B)'s write-back
+// and (C) by the one after (B): __syncthreads orders the workgroup's device-memory accesses as well as its LDS
+// accesses (a workgroup's waves share a CU and its vector cache).  Inside a compaction the wave alone touches its
+// scratch and its row; the network's stages are separated by wave barriers and wavefront fences.
+//
+// Persistent grid.  plan_retrieve bounds the workgroups (as many as stay resident, from TOPK_CUS); workgroup b
+// walks the (user tile, slice) pairs b, b + grid, ... and reuses its block, so the workspace is grid blocks plus the
+// slices' partial results whatever n is.  Item slices, their partial results and the merge are k_topk's
+// (launch_topk_merge), with slices x k <= 8,192.
+//
+// Measured (profiles/retrieve_probe.txt, ML-20M shape, d = 128; the composition is P[users] Q^T, the seen scatter and
+// torch.topk(k) per 4,096 users).  All 138,493 users: k = 128 31.5 ms against 58.8 (and against k_topk's 99.6: the
+// tile loop without the CSR searches is what that kernel's header asks for), k = 256 45.9 against 60.1 — and then it
+// LOSES: k = 512 74.4 against 60.4, k = 1,024 204.2 against 61.2.  4,096 users (64 user tiles x 4 slices): it loses
+// at every k, 3.1 / 4.8 / 7.5 / 11.4 ms against 1.8 - 1.9.  Suspected reasons, not measured apart: the sort — a
+// compaction at cap = 2,048 is 66 stages of 16 LDS compare-exchanges per lane, run by ONE wave while the row's other
+// lanes wait at the barrier, and with a random table a row sees about k ln(I / k) candidates after the fill, one
+// compaction per cap - k of them and one more at the end; the composition's cost barely moves with k.  At 4,096
+// users one workgroup per CU leaves the MFMA pipe idle during every epilogue, the merge is a second launch, and the
+// composition is a single GEMM there.  Next steps: sort the small strides in registers (DPP / shuffles) instead of
+// through LDS, merge the k sorted survivors with the sorted tail instead of sorting all of it again, and give the
+// compaction to all 4 waves of the row's workgroup.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <string.h>
+
+#include <string>
+
+#include "bpr_host.h"
+#include "bpr_retrieve_plan.h"
+#include "bpr_topk_shared.h"
+
+namespace bpr {
+
+struct RetrieveArgs {
+  const float* P;
+  const float* Q;
+  const float* bias;
+  int64_t I;
+  int d;
+  const int32_t* users;
+  int64_t n;
+  const int64_t* indptr;
+  const int32_t* indices;
+  int k, slices, cap;
+  int64_t item_tiles, units;
+  Cand* bufs;          // [grid][TOPK_TU][cap]
+  float* out_scores;   // [n, slices, k]
+  int32_t* out_items;  // [n, slices, k]
+};
+
+// One wave: the c <= cap candidates of a row in device memory -> scratch (LDS, [cap]), the entries from `checked`
+// on that are in the sorted seen row dropped, sorted by `better`.  Returns how many are left; they are scratch[0 ..).
+// What is dropped or past c is the sentinel (-inf, INT_MAX), which every candidate beats (ids are below INT_MAX) and
+// which therefore sorts last.  Every lane of the wave calls it with the same arguments.
+__device__ __forceinline__ int sort_row(const Cand* buf, int c, int checked, const int32_t* __restrict__ seen,
+                                        int seen_len, Cand* scratch, int lane) {
+  int n2 = 64;  // (a power of two >= c, and at least one entry per lane)
+  while (n2 < c) n2 <<= 1;
+  int dropped = 0;
+  for (int idx = lane; idx < n2; idx += 64) {
+    Cand e = {-INFINITY, INT_MAX};
+    if (idx < c) {
+      e = buf[idx];
+      if (idx >= checked && in_sorted(seen, seen_len, e.i)) {
+        e = Cand{-INFINITY, INT_MAX};
+        ++dropped;
+      }
+    }
+    scratch[idx] = e;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) dropped += __shfl_xor(dropped, off, 64);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  // the bitonic network over n2 entries: pair t of a stage is (i, i + stride), i = t with a 0 bit put in at `stride`
+  for (int size = 2; size <= n2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = lane; t < (n2 >> 1); t += 64) {
+        const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+        const Cand x = scratch[i], y = scratch[j];
+        const bool first = (i & size) == 0;  // best first in this block of the stage, or best last
+        if (first ? better(y.s, y.i, x.s, x.i) : better(x.s, x.i, y.s, y.i)) {
+          scratch[i] = y;
+          scratch[j] = x;
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  return c - dropped;
+}
+
+// VEC: d % 4 == 0 and 16-byte aligned tables (16-byte global loads); else element loads.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_retrieve(const RetrieveArgs a) {
+  constexpr int TU = TOPK_TU, TI = TOPK_TI, KC = TOPK_KC, LD = TOPK_LD;
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int cap = a.cap;
+  float* const sQ = reinterpret_cast<float*>(smem);               // [TI][LD]
+  float* const sP = sQ + TI * LD;                                 // [TU][LD]
+  Cand* const sScratch = reinterpret_cast<Cand*>(sP + TU * LD);   // [4][cap]
+  Cand* const sTau = sScratch + 4 * cap;                          // [TU]
+  int64_t* const sSeenLo = reinterpret_cast<int64_t*>(sTau + TU);
+  int* const sCnt = reinterpret_cast<int*>(sSeenLo + TU);
+  int* const sNeed = sCnt + TU;
+  int* const sUser = sNeed + TU;
+  int* const sSeenLen = sUser + TU;
+  int* const sChecked = sSeenLen + TU;
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+  Cand* const gBuf = a.bufs + (int64_t)blockIdx.x * TU * cap;  // this workgroup's block: [TU][cap]
+  Cand* const scratch = sScratch + w * cap;
+  const int nch = (a.d + KC - 1) / KC;
+  const float* const qa = sQ + (32 * w + r) * LD + 4 * h;
+  const float* const pb0 = sP + r * LD + 4 * h;
+  const float* const pb1 = sP + (32 + r) * LD + 4 * h;
+  const bool has_bias = a.bias != nullptr;
+
+  for (int64_t unit = blockIdx.x; unit < a.units; unit += gridDim.x) {
+    const int64_t u0 = unit / a.slices * TU;
+    const int slice = (int)(unit % a.slices);
+    const int64_t t0 = a.item_tiles * slice / a.slices, t1 = a.item_tiles * (slice + 1) / a.slices;
+
+    if (tid < TU) {
+      const int64_t row = u0 + tid;
+      const bool live = row < a.n;
+      const int u = live ? a.users[row] : -1;
+      int64_t lo = 0;
+      int len = 0;
+      if (live && a.indptr != nullptr && a.indices != nullptr) {
+        lo = a.indptr[u];
+        len = (int)(a.indptr[u + 1] - lo);
+      }
+      sUser[tid] = u;
+      sSeenLo[tid] = lo;
+      sSeenLen[tid] = len;
+      sCnt[tid] = 0;
+      sNeed[tid] = 0;
+      sChecked[tid] = 0;
+      // nothing kept yet: everything beats tau; a row past n: nothing does
+      sTau[tid] = live ? Cand{-INFINITY, INT_MAX} : Cand{INFINITY, -1};
+    }
+    __syncthreads();
+
+    // the next chunk travels global -> registers while the current one is multiplied, then registers -> LDS
+    float4 qreg[4], preg[2];
+    auto fetch = [&](int64_t t, int c) {
+      const int kc = c * KC;
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
+        const int64_t item = t * TI + row;
+        qreg[m] = item < a.I ? load4<VEC>(a.Q + item * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
+        const int u = sUser[row];
+        preg[m] = u >= 0 ? load4<VEC>(a.P + (int64_t)u * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    };
+    auto stash = [&]() {
+      BPR_STASH_CHUNK(sQ, qreg, 4, tid, 256);
+      BPR_STASH_CHUNK(sP, preg, 2, tid, 256);
+    };
+    // one wave: row's buffer -> its scratch, unseen and sorted; returns how many
+    auto sorted_row = [&](int row) {
+      return sort_row(gBuf + (int64_t)row * cap, min(sCnt[row], cap), sChecked[row], a.indices + sSeenLo[row],
+                      sSeenLen[row], scratch, lane);
+    };
+
+    if (t0 < t1) fetch(t0, 0);
+    for (int64_t t = t0; t < t1; ++t) {
+      f32x16 acc0 = {0.f}, acc1 = {0.f};
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.f;
+      for (int c = 0; c < nch; ++c) {
+        __syncthreads();
+        stash();
+        __syncthreads();
+        if (c + 1 < nch) fetch(t, c + 1);
+        else if (t + 1 < t1) fetch(t + 1, 0);
+        mfma_chunk2(qa, pb0, pb1, acc0, acc1);
+      }
+
+      // ---- epilogue of the item tile: register q of the lane is item ibase + (q & 3) + 8 (q >> 2) of users r, 32 + r
+      const int64_t ibase = t * TI + 32 * w + 4 * h;
+      float bv[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int64_t item = ibase + (q & 3) + 8 * (q >> 2);
+        bv[q] = has_bias && item < a.I ? a.bias[item] : 0.f;
+      }
+      // (A) how many scores beat the row's threshold
+      unsigned m0 = 0, m1 = 0;
+      {
+        const Cand tau0 = sTau[r], tau1 = sTau[32 + r];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int64_t item = ibase + (q & 3) + 8 * (q >> 2);
+          const bool ok = item > 0 && item < a.I;
+          const float s0 = has_bias ? acc0[q] + bv[q] : acc0[q];
+          const float s1 = has_bias ? acc1[q] + bv[q] : acc1[q];
+          if (ok && better(s0, (int)item, tau0.s, tau0.i)) m0 |= 1u << q;
+          if (ok && better(s1, (int)item, tau1.s, tau1.i)) m1 |= 1u << q;
+        }
+        if (m0) atomicAdd(&sNeed[r], __popc(m0));
+        if (m1) atomicAdd(&sNeed[32 + r], __popc(m1));
+      }
+      __syncthreads();  // (the appends of the tiles before are behind this barrier too)
+      // (B) rows whose buffer might not take them all: down to the k best unseen, which tightens tau
+      for (int row = w; row < TU; row += 4) {
+        const int c = min(sCnt[row], cap);
+        if (c + sNeed[row] <= cap) continue;
+        const int left = sorted_row(row);
+        const int keep = left < a.k ? left : a.k;
+        Cand* const buf = gBuf + (int64_t)row * cap;
+        for (int j = lane; j < keep; j += 64) buf[j] = scratch[j];
+        if (lane == 0) {
+          if (left >= a.k) sTau[row] = scratch[a.k - 1];
+          sCnt[row] = keep;
+          sChecked[row] = keep;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();  // (the scratch is free for the wave's next row)
+      }
+      __syncthreads();
+      // (C) append what still beats the threshold; whether the user has seen it is the compaction's question
+      if (tid < TU) sNeed[tid] = 0;
+      if (m0 | m1) {
+        const Cand tau0 = sTau[r], tau1 = sTau[32 + r];
+        Cand* const buf0 = gBuf + (int64_t)r * cap;
+        Cand* const buf1 = gBuf + (int64_t)(32 + r) * cap;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int item = (int)(ibase + (q & 3) + 8 * (q >> 2));
+          if ((m0 >> q) & 1u) {
+            const float s0 = has_bias ? acc0[q] + bv[q] : acc0[q];
+            if (better(s0, item, tau0.s, tau0.i)) {
+              const int pos = atomicAdd(&sCnt[r], 1);
+              if (pos < cap) buf0[pos] = Cand{s0, item};
+            }
+          }
+          if ((m1 >> q) & 1u) {
+            const float s1 = has_bias ? acc1[q] + bv[q] : acc1[q];
+            if (better(s1, item, tau1.s, tau1.i)) {
+              const int pos = atomicAdd(&sCnt[32 + r], 1);
+              if (pos < cap) buf1[pos] = Cand{s1, item};
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+
+    // ---- the unit's result: every row unseen and sorted, straight from the scratch, padded with (-inf, -1)
+    for (int row = w; row < TU; row += 4) {
+      if (u0 + row >= a.n) break;
+      const int left = sorted_row(row);
+      const int have = left < a.k ? left : a.k;
+      const int64_t out = ((u0 + row) * a.slices + slice) * a.k;
+      for (int j = lane; j < a.k; j += 64) {
+        const Cand e = j < have ? scratch[j] : Cand{-INFINITY, -1};
+        a.out_scores[out + j] = e.s;
+        a.out_items[out + j] = e.i;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();  // (the next unit resets the rows' meta data and reuses the block)
+  }
+}
+
+static int check_retrieve_shape(const char* who, int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices) {
+  if (n < 0 || I < 1 || I >= ((int64_t)1 << 31))
+    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be >= 0 and I in [1, 2^31)");
+  if (d < 1 || d > 1024) return fail(BPR_ERR_INVALID, std::string(who) + ": d must be in [1, 1024]");
+  if (k < 1 || k > RETRIEVE_MAX)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": k must be in [1, " + std::to_string(RETRIEVE_MAX) + "]");
+  if (item_slices < 0 || item_slices > TOPK_MAX_SLICES)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": item_slices must be 0 (choose) or in [1, " +
+                                     std::to_string(TOPK_MAX_SLICES) + "]");
+  if (n > 0x7FFFFFFF)  // (the merge kernel's grid is one workgroup per row)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be below 2^31");
+  return BPR_OK;
+}
+
+template <bool VEC>
+static int launch(const RetrieveArgs& a, const RetrievePlan& p, hipStream_t stream) {
+  // past 64 KiB the dynamic LDS of a workgroup is a per-function attribute (set on every call, as k_topk's)
+  BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_retrieve<VEC>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)retrieve_lds_bytes(RETRIEVE_MAX)));
+  hipLaunchKernelGGL(k_retrieve<VEC>, dim3((unsigned)p.grid), dim3(256), p.lds, stream, a);
+  BPR_HIP_CHECK(hipGetLastError());
+  return BPR_OK;
+}
+
+}  // namespace bpr
+
+extern "C" int bpr_retrieve_workspace(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices,
+                                      int64_t* bytes_host) {
+  using namespace bpr;
+  if (bytes_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_retrieve_workspace: bytes_host is NULL");
+  if (int rc = check_retrieve_shape("bpr_retrieve_workspace", n, I, d, k, item_slices)) return rc;
+  *bytes_host = retrieve_workspace_bytes(n, I, k, item_slices);
+  return BPR_OK;
+}
+
+extern "C" int bpr_retrieve_slices(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices,
+                                   int32_t* slices_host) {
+  using namespace bpr;
+  if (slices_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_retrieve_slices: slices_host is NULL");
+  if (int rc = check_retrieve_shape("bpr_retrieve_slices", n, I, d, k, item_slices)) return rc;
+  *slices_host = plan_retrieve(n, I, k, item_slices).slices;
+  return BPR_OK;
+}
+
+extern "C" int bpr_retrieve_rows(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                                 const int32_t* users, int64_t n, const int64_t* seen_indptr,
+                                 const int32_t* seen_indices, int32_t k, int32_t item_slices, void* workspace,
+                                 int64_t workspace_bytes, int32_t* items_out, float* scores_out, void* hip_stream) {
+  using namespace bpr;
+  if (int rc = check_retrieve_shape("bpr_retrieve_rows", n, I, d, k, item_slices)) return rc;
+  if (n > 0 && (!P || !Q || !users || !items_out || !scores_out))
+    return fail(BPR_ERR_INVALID, "bpr_retrieve_rows: P, Q, users, items_out or scores_out is NULL");
+  const RetrievePlan p = plan_retrieve(n, I, k, item_slices);
+  if (p.ws_bytes > 0 && (workspace == nullptr || workspace_bytes < p.ws_bytes))
+    return fail(BPR_ERR_INVALID, "bpr_retrieve_rows: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                     std::to_string(p.ws_bytes) + " needed (bpr_retrieve_workspace)");
+  if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
+    return fail(BPR_ERR_INVALID, "bpr_retrieve_rows: workspace must be 8-byte aligned");
+  if (n == 0) return BPR_OK;
+
+  hipStream_t stream = (hipStream_t)hip_stream;
+  RetrieveArgs a = {};
+  a.P = P; a.Q = Q; a.bias = item_bias; a.I = I; a.d = d; a.users = users; a.n = n;
+  a.indptr = seen_indptr; a.indices = seen_indices; a.k = k; a.slices = p.slices; a.cap = p.cap;
+  a.item_tiles = p.item_tiles; a.units = p.units;
+  float* part_s = reinterpret_cast<float*>(workspace);
+  int32_t* part_i = reinterpret_cast<int32_t*>(part_s + (p.slices > 1 ? n * (int64_t)p.slices * k : 0));
+  a.bufs = reinterpret_cast<Cand*>(reinterpret_cast<unsigned char*>(workspace) + p.part_bytes);
+  a.out_scores = p.slices > 1 ? part_s : scores_out;
+  a.out_items = p.slices > 1 ? part_i : items_out;
+  const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Q)) % 16 == 0;
+  if (int rc = vec ? launch<true>(a, p, stream) : launch<false>(a, p, stream)) return rc;
+  if (p.slices > 1)
+    return launch_topk_merge(part_s, part_i, n, p.slices, k, p.merge_lds, scores_out, items_out, stream);
+  return BPR_OK;
+}
+
+// Test hook, not API (tests/test_retrieve_cpu.py sets its signature): the plan of a shape.  in = {n, I, d, k,
+// item_slices, cus}; out = {slices, user_tiles, item_tiles, tile_users, tile_items, cap, lds, merge_lds, ws_bytes,
+// units, grid, grid_max, part_bytes, buf_bytes}; bounds[0 .. slices] = first item of each slice, then I.  No GPU.
+extern "C" int bpr_test_retrieve_plan(const int64_t* in, int64_t* out, int64_t* bounds) {
+  using namespace bpr;
+  if (int rc = check_retrieve_shape("bpr_test_retrieve_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3],
+                                    (int32_t)in[4]))
+    return rc;
+  const int cus = in[5] > 0 ? (int)in[5] : TOPK_CUS;
+  const RetrievePlan p = plan_retrieve(in[0], in[1], (int)in[3], (int)in[4], cus);
+  const int64_t v[] = {p.slices, p.user_tiles, p.item_tiles, TOPK_TU, TOPK_TI, p.cap, (int64_t)p.lds,
+                       (int64_t)p.merge_lds, p.ws_bytes, p.units, p.grid, retrieve_grid_max((int)in[3], cus),
+                       p.part_bytes, p.buf_bytes};
+  memcpy(out, v, sizeof(v));
+  for (int s = 0; s <= p.slices; ++s) bounds[s] = std::min<int64_t>(retrieve_slice_tile(p, s) * TOPK_TI, in[1]);
+  return BPR_OK;
+}

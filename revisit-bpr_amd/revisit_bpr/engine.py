@@ -224,6 +224,16 @@ class Engine:
         indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
         return recommend(self.P, self.Q, self.item_bias, users, k, indptr, indices, item_slices=item_slices)
 
+    def retrieve(self, users: torch.Tensor, k: int, exclude_seen: bool = True, *, item_slices: int = 0):
+        """`recommend` for `k` up to 1,024, the first stage of a two-stage recommender (`bpr_retrieve_rows`, see
+        revisit_bpr/retrieve.py): the same scores, exclusions, order and padding, from the kernel that keeps its
+        candidates in device memory.  As `recommend`, rows an optimizer has not replayed yet are scored as they
+        stand: `flush_lazy()` first (`Model.retrieve` does)."""
+        from revisit_bpr.retrieve import retrieve
+
+        indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
+        return retrieve(self.P, self.Q, self.item_bias, users, k, indptr, indices, item_slices=item_slices)
+
     def rank_items(self, users: torch.Tensor, tgt_indptr: torch.Tensor, tgt_items: torch.Tensor,
                    exclude_seen: bool = True, *, item_slices: int = 0):
         """(rank, not_below, score) of every target of every row (row r: user `users[r]`, targets

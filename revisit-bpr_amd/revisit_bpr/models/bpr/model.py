@@ -476,6 +476,22 @@ class Model(torch.nn.Module):
             scores += ub.detach()[users.reshape(-1).long()].unsqueeze(1)
         return items, scores
 
+    def retrieve(self, users: torch.Tensor, k: int, exclude_seen: bool = True):
+        """`recommend` for `k` up to 1,024 (revisit_bpr/retrieve.py): candidates for `rerank`, `diversify` or a
+        ranker of the caller's, with `recommend`'s scores, exclusions, order and padding.  Rows behind the
+        optimizer step are replayed first (`sync()`).  A user bias is added to the returned scores (it does not
+        change a user's order).  Only the MF scorer has a fused form."""
+        if not self._fusable():
+            raise NotImplementedError("retrieve needs the MF logits model in float32: other scorers have no "
+                                      "fused top-K kernel")
+        eng = self.engine()
+        self.sync()
+        items, scores = eng.retrieve(users, k, exclude_seen=exclude_seen)
+        ub = self.logits_model._user_bias
+        if ub is not None:
+            scores += ub.detach()[users.reshape(-1).long()].unsqueeze(1)
+        return items, scores
+
     def rank_items(self, users: torch.Tensor, tgt_indptr: torch.Tensor, tgt_items: torch.Tensor,
                    exclude_seen: bool = True):
         """(rank, not_below, score), aligned with `tgt_items`, of every target of every row (row r: user
