@@ -545,7 +545,10 @@ int bpr_auc_rows(const float* scores, int64_t n, int64_t I, const int64_t* pos_i
  * kernel (csrc/bpr_topk.hip): s(u, i) = <P[u], Q[i]> (+ item_bias[i]) in fp32 over all I items, item 0 and the
  * items of the user's seen row (the CSR of bpr_bind_seen_csr: int64 [U+1], int32 sorted per row; NULL = only item 0)
  * left out, and no [n, I] buffer anywhere.  items_out / scores_out [n, k]: rows sorted by score descending, ties by
- * ascending item id; a row with fewer than k eligible items ends in item -1 / score -inf.  The result is a pure
+ * ascending item id; a row with fewer than k eligible items ends in item -1 / score -inf.  A NaN score (a NaN in a
+ * row, 0 * inf, inf - inf) is never returned, so such a row may end in padding although items are left; +inf and -inf
+ * scores are ordered like any other, and a real item scoring -inf keeps its id (tests/test_gpu_chain.py holds all of
+ * this, and the score's bits, to tests/chain_model.py).  The result is a pure
  * function of the inputs: its bits do not depend on n, on a user's place in the list (which may repeat users) or on
  * item_slices (0 = the library chooses; s > 1 cuts the item range over s workgroups per user tile, for lists too
  * short to fill the chip, and needs the workspace).  d in [1, 1024], 1 <= k <= 128 (more: BPR_ERR_INVALID),
@@ -571,7 +574,8 @@ int bpr_topk_rows(const float* P, const float* Q, const float* item_bias /* or N
  * of persistent workgroups walks the user tiles, so the workspace does not grow with n beyond the slices' partial
  * results.  Semantics are bpr_topk_rows' word for word: s(u, i) is the same fp32 fmaf chain plus one bias add (the
  * same bits), item 0 and the user's seen row are left out, rows are sorted by score descending, ties by ascending
- * id, a short row ends in item -1 / score -inf, a NaN score never enters, and the result is a pure function of the
+ * id, a short row ends in item -1 / score -inf, a NaN score is never returned (the row may then end in padding), +-inf
+ * scores are ordered like any other, a real item scoring -inf keeps its id, and the result is a pure function of the
  * inputs (not of n, of a row's place in the list, of repeated users, of item_slices).  For k <= 128 it returns what
  * bpr_topk_rows returns, bit for bit.  d in [1, 1024], item_slices in [0, 64] (0 = the library chooses; a count
  * above 8192 / k or above the item tiles is reduced, not refused: bpr_retrieve_slices reports the count that runs),
@@ -797,8 +801,10 @@ int bpr_fold_in_item_rows_roles(const float* P, int64_t U, const float* Q, const
  * returned; so is an all-zero row.  Under BPR_SIM_DOT a zero row is eligible, with score 0).  Under cosine a query with
  * !(ss > 0) gets a fully padded row.
  * Output.  ids_out / scores_out [n, k]: the eligible rows sorted by score descending, ties by ascending id; a query
- * with fewer than k eligible rows ends in id -1 / score -inf.  A NaN score is never better than anything (it can be
- * returned only where rows run out, in no defined order among NaNs).
+ * with fewer than k eligible rows ends in id -1 / score -inf.  A NaN score is never better than anything, the initial
+ * threshold included: it is never returned, and the row may end in padding although rows of T are left.  +inf and
+ * -inf scores are ordered like any other, and a real row scoring -inf keeps its id.  Under cosine an ss that
+ * overflowed is +inf > 0: rn = +0, the row stays eligible and its scores are +-0 or (inf * 0) NaN.
  * The result is a pure function of the inputs: its bits do not depend on n, on a query's place in the list (which may
  * repeat rows) or on item_slices (0 = the library chooses; s > 1 cuts the table over s workgroups per query tile, for
  * lists too short to fill the chip, and needs the workspace).  d in [1, 1024], 1 <= k <= 128, item_slices in [0, 64],
@@ -837,7 +843,9 @@ int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int32_t d,
  * before the item row is read: an ineligible candidate costs no table traffic.
  * Scores.  s(u, i) = bpr_topk_rows' / bpr_rank_rows' / bpr_neighbors_rows' (dot) score, bit for bit: one fp32 fmaf
  * chain from 0.0f over the features in the fixed order (per 8 features: 0, 4, 1, 5, 2, 6, 3, 7), then item_bias[i]
- * as one fp32 add.  Tables are taken to be finite.
+ * as one fp32 add.  A table that is not finite gives IEEE's infinities and NaNs: cand_scores_out holds them as they
+ * are; in items_out a NaN score is never returned (the row may end in padding), +-inf scores are ordered like any
+ * other and a real candidate scoring -inf keeps its id.
  * Output.  cand_scores_out (may be NULL if k > 0), aligned with the candidates ([n, shared_len] row-major for the
  * shared list): the score, -inf for an ineligible candidate.  With k > 0, items_out / scores_out [n, k]: the
  * eligible candidates sorted by score descending, ties by ascending id; an id listed m times is a candidate m times

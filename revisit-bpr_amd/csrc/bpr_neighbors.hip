@@ -24,8 +24,9 @@
 // features in the dot product's own order (fma_chain8, bpr_topk_shared.h), so ss(v) == dot(v, v) bit for
 // bit and a row meets its own copy at (ss * rn) * rn, six roundings from 1; rn = 1 / sqrt(ss), both correctly
 // rounded, is stored if ss > 0, the marker -1 otherwise (a zero row, or one with a NaN): such a table row is never
-// returned, such a query gets a padded row.  The norms of the N table rows and the n queries are written on every
-// call.
+// returned, such a query gets a padded row.  An ss that overflowed is +inf > 0: rn = +0, the row stays eligible and
+// its scores are +-0 or (inf * 0) NaN, which is never returned (tests/test_gpu_chain.py, class d).  The norms of the N
+// table rows and the n queries are written on every call.
 // Correct rounding is spelt sqrtf and `/` here, and the Makefile pins -fhip-fp32-correctly-rounded-divide-sqrt for
 // this object: HIP's __fsqrt_rn is the hardware's approximate square root (1 ulp) unless the headers are built
 // with OCML_BASIC_ROUNDED_OPERATIONS, whose __ocml_sqrt_rte_f32 / __ocml_div_rte_f32 the device library of this

@@ -56,6 +56,14 @@ __device__ __forceinline__ void stash_piece(float* s, const float4 v, int f) {
 // to each other bit for bit (rerank against bpr_topk_rows and bpr_rank_rows, the cosine norms against the dot
 // product, diversify's Gram matrix against the scores), so a score's bits are the same wherever the pair falls —
 // in a tile, a slice, a list, or another kernel.  Whoever changes the order changes it here, for all of them.
+// The host statement of the contract is tests/chain_model.py (numpy, a correctly rounded fma, held to exact rational
+// arithmetic by tests/test_chain_model_cpu.py); tests/test_gpu_chain.py holds every kernel's scores to its bits, so
+// a change here that moves all kernels together is still seen.  That includes the values at the edge: subnormal
+// products and sums are kept, by the MFMA as by fmaf (measured on gfx950: IEEE, bit for bit); a negative product that
+// underflows onto the zero accumulator is -0 and the staged zeros after it make +0 of it (which is why a chunk is run
+// to its end); 0 * inf over a staged zero is NaN, a NaN score is never `better` than anything and so never enters a
+// buffer, and +-inf scores are ordered like any other — a real item at -inf beats the padding (-inf, -1) and
+// k_retrieve's sort sentinel (-inf, INT_MAX) by its id.
 
 // 8 features of one 32 x 32 tile: a, b are the lane's 4 staged features of its A-side and B-side row
 __device__ __forceinline__ void mfma_block1(const float4 a, const float4 b, f32x16& acc) {

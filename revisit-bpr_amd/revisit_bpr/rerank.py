@@ -44,7 +44,11 @@ def rerank(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor], 
     id, an id listed m times returned up to m times, adjacent; a row with fewer than k eligible candidates ends in
     item -1 / score -inf.  `return_scores=True` adds cand_scores (float32, aligned with `cand_items`; [n, C] for
     the shared list): every candidate's score, -inf for an ineligible one.  A score is the bits `recommend` and
-    `rank_items` return for the pair.  The result does not depend on n, on the order of the rows, on the order of
+    `rank_items` return for the pair.
+    A NaN score (a NaN in a row, 0 * inf, inf - inf) is never returned, so such a row may end in padding although
+    candidates are left, and cand_scores holds it as it is; +inf and -inf scores are ordered like any other, and a
+    real item scoring -inf keeps its id: only the padding is item -1 (tests/test_gpu_chain.py).
+    The result does not depend on n, on the order of the rows, on the order of
     the candidates inside a row or on `layout` (0: the library chooses; LAYOUT_WAVE, LAYOUT_WG).  Runs on the
     current stream.  The kernel reads P[user], the user's CSR row and `cand_indptr` unchecked, so they are checked
     here first, which waits for the device; `check_users=False` leaves that out.

@@ -42,7 +42,10 @@ def retrieve(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor]
     user's row of the seen CSR (int64 [U+1], int32 sorted per row; None: only item 0) left out.
 
     Returns (items [n, k] int32, scores [n, k] float32): rows sorted by score descending, ties by ascending item
-    id; a row with fewer than k eligible items ends in item -1 / score -inf.  The result does not depend on n, on
+    id; a row with fewer than k eligible items ends in item -1 / score -inf.
+    A NaN score (a NaN in a row, 0 * inf, inf - inf) is never returned, so such a row may end in padding although
+    items are left; +inf and -inf scores are ordered like any other, and a real item scoring -inf keeps its id: only
+    the padding is item -1 (tests/test_gpu_chain.py).  The result does not depend on n, on
     the order of `users` or on `item_slices` (0: the library chooses how many workgroups share the item range of
     a user tile), and its first 128 columns are `recommend`'s.  Runs on the current stream.  The kernel reads
     P[user] and the user's CSR row unchecked, so the ids are range-checked here first, which waits for the device;

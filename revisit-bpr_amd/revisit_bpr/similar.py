@@ -57,7 +57,11 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
     fully padded row.
 
     Returns (ids [n, k] int32, scores [n, k] float32): rows sorted by score descending, ties by ascending id; a
-    row with fewer than k eligible rows of `T` ends in id -1 / score -inf.  The result does not depend on n, on
+    row with fewer than k eligible rows of `T` ends in id -1 / score -inf.
+    A NaN score (a NaN in a row, 0 * inf, inf - inf) is never returned, so such a row may end in padding although
+    rows of `T` are left; +inf and -inf scores are ordered like any other, and a real row scoring -inf keeps its id:
+    only the padding is id -1.  Under cosine a row whose sum of squares overflows has the norm factor +0: it stays
+    eligible, with scores +-0 or NaN (tests/test_gpu_chain.py).  The result does not depend on n, on
     the order of `rows` or on `item_slices` (0: the library chooses how many workgroups share the table for a
     query tile); include/bprcore.h defines its bits.  Runs on the current stream.  The kernel reads `X[rows[r]]`
     unchecked, so `rows` are range-checked against `X` (and `exclude` against `T`) here first, which waits for
@@ -113,13 +117,15 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
 
 def similar_items(Q: torch.Tensor, items: torch.Tensor, k: int, metric: str = "cosine", **kwargs):
     """The `k` items most similar to each item of `items` by their rows of the item table `Q`: `neighbors(Q, Q,
-    items, k, exclude=items, first=1)` — never the item itself, never the padding item 0.  A freshly folded-in
+    items, k, exclude=items, first=1)` — never the item itself, never the padding item 0, never a NaN score
+    (`neighbors` says what +-inf scores do).  A freshly folded-in
     item row is not in `Q`: `neighbors(Q_new, Q, torch.arange(m), k, first=1)`."""
     return neighbors(Q, Q, items, k, metric=metric, exclude=items, first=1, **kwargs)
 
 
 def similar_users(P: torch.Tensor, users: torch.Tensor, k: int, metric: str = "cosine", **kwargs):
     """The `k` users most similar to each user of `users` by their rows of the user table `P`: `neighbors(P, P,
-    users, k, exclude=users, first=0)` — never the user itself; user 0 is a user like any other.  A freshly
+    users, k, exclude=users, first=0)` — never the user itself, never a NaN score (`neighbors` says what +-inf scores
+    do); user 0 is a user like any other.  A freshly
     folded-in user row is not in `P`: `neighbors(P_new, P, torch.arange(m), k)`."""
     return neighbors(P, P, users, k, metric=metric, exclude=users, first=0, **kwargs)

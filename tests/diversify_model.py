@@ -3,26 +3,17 @@ the code under test.  `sim_matrix` restates the similarity in float32 steps, `di
 the tie rule, the rows of a call advancing together a step at a time."""
 import numpy as np
 
+from chain_model import chain_scores
+
 F = np.float32
 
 
 def chain_dot(A, B):
     """dot(a, b) for every pair of rows of A [m, d] and B [p, d]: one float32 accumulator from +0, one fused
     multiply-add per feature in k_topk's order (per 8 features 0, 4, 1, 5, 2, 6, 3, 7), every chunk of 32 run to its
-    end over zeros.  The fma is a float64 product (exact: 24 + 24 bits) and a float64 add rounded to float32: on
-    integer-valued tables every step is exact and so is this; on float tables the double rounding can differ from a
-    true fma in the last bit, rarely (the GPU tests hold float tables to the kernel's own scores or to a bound)."""
-    A, B = np.asarray(A, F), np.asarray(B, F)
-    d = A.shape[1]
-    dpad = -(-d // 32) * 32
-    A64 = np.zeros((A.shape[0], dpad))
-    B64 = np.zeros((B.shape[0], dpad))
-    A64[:, :d], B64[:, :d] = A, B
-    acc = np.zeros((A.shape[0], B.shape[0]), F)
-    for f8 in range(0, dpad, 8):
-        for j in (0, 4, 1, 5, 2, 6, 3, 7):
-            acc = (np.outer(A64[:, f8 + j], B64[:, f8 + j]) + acc.astype(np.float64)).astype(F)
-    return acc
+    end over zeros.  There is one host model of that chain, tests/chain_model.py, whose fma is correctly rounded
+    (tests/test_chain_model_cpu.py holds it to exact rational arithmetic); this is it."""
+    return chain_scores(A, B)
 
 
 def sim_matrix(Q, metric):
