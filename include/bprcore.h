@@ -596,6 +596,48 @@ int bpr_retrieve_rows(const float* P, const float* Q, const float* item_bias /* 
                       void* workspace, int64_t workspace_bytes,
                       int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
 
+/* ---- sampling: k unseen items per user drawn WITHOUT replacement from softmax(s(u, .) / temperature) over the
+ * user's eligible items (the Plackett-Luce model) — exploration, and logs that off-policy evaluation can use.  The
+ * reference's sampler goes through the [n, I] score matrix and a multinomial; here one fused kernel
+ * (csrc/bpr_sample.hip) with bpr_topk_rows' tiling, selection and slices, by the Gumbel-top-k identity: the k largest
+ * keys, in descending order, are the k draws in the order drawn.
+ * Eligibility and scores are bpr_topk_rows': item 0 and the user's seen row are out; s(u, i) is the same fp32 fmaf
+ * chain plus one bias add, the same bits.
+ * The draw (csrc/bpr_sample_shared.h; tests/sample_model.py states it in numpy).  Row r has the 64-bit id
+ * draw_ids[r] (NULL: the user id).  Item i's 32 random bits are word i & 3 of philox4x32_10 with counter
+ * (i >> 2, lo32(draw_id), hi32(draw_id), 3) and key (lo32(seed), hi32(seed)); u = ((bits >> 9) + 0.5f) * 2^-23, exact
+ * in fp32 and strictly inside (0, 1); g = -log(-log(u)) with the header's logarithm, a fixed sequence of fp32
+ * operations (within 5.34e-7 of float64 for every u); key = fmaf(s, inv_temp, g), inv_temp = 1.0f / temperature in
+ * fp32.  Items and keys are therefore a pure function of (tables, user, draw_id, seed, temperature): not of n, of a
+ * row's place in the list, of item_slices.  The same user twice with one draw_id is the same row twice; give rows
+ * distinct draw_ids (a request counter) for independent draws.
+ * items_out [n, k]: the draws in order (key descending, ties by ascending id); scores_out [n, k]: their unperturbed
+ * scores s(u, i), bpr_rerank_rows' cand_scores bits; keys_out [n, k] or NULL.  A row with fewer than k eligible
+ * items ends in item -1 / score -inf / key -inf.  A NaN score gives a NaN key and is never returned; a +-inf score
+ * gives a +-inf key, ordered like any other (+inf is drawn first).
+ * log_z_out [n] or NULL: log sum_i exp(s(u, i) * inv_temp) over the row's eligible items whose score is not NaN, the
+ * normaliser a propensity needs; -inf for a row with nothing eligible, +inf with an eligible +inf score.  Accumulated
+ * online in fp32 with the fast exp / log: held to a tolerance, not to bits, and its bits may depend on item_slices
+ * (the slices' sums are combined in slice order); for a fixed slice count they depend on nothing else.
+ * d in [1, 1024], 1 <= k <= 128, temperature finite and > 0 with 1.0f / temperature finite (else BPR_ERR_INVALID),
+ * item_slices in [0, 64], n < 2^31.  The workspace is 8-byte aligned.  User ids are not checked.  Arguments are
+ * validated before the device is touched; n == 0 is BPR_OK.  Context-free: runs on `hip_stream` of the current
+ * device. */
+/* bytes of device workspace bpr_sample_rows needs for this shape: bpr_topk_workspace's partial results, plus
+ * 8 bytes per row and slice (with one slice too) when log_z is wanted; item_slices 0: never less than for a
+ * smaller n */
+int bpr_sample_workspace(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices, int32_t want_log_z,
+                         int64_t* bytes_host);
+/* the slice count a call of this shape runs with (as bpr_topk_slices) */
+int bpr_sample_slices(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices, int32_t* slices_host);
+int bpr_sample_rows(const float* P, const float* Q, const float* item_bias /* or NULL */, int64_t I, int32_t d,
+                    const int32_t* users, int64_t n, const int64_t* draw_ids /* [n] or NULL = the user id */,
+                    const int64_t* seen_indptr /* or NULL */, const int32_t* seen_indices,
+                    int32_t k, float temperature, uint64_t seed, int32_t item_slices /* 0 = choose */,
+                    void* workspace, int64_t workspace_bytes,
+                    int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, float* keys_out /* [n,k] or NULL */,
+                    float* log_z_out /* [n] or NULL */, void* hip_stream);
+
 /* ---- ranking of held-out items: where each target of a row stands among the user's eligible items (the reference
  * measures through full logits: example.py:195-230 and experiments/bpr/exp.py:369-374, an argsort of I scores per
  * metric object; metrics/auc.py:70-130; metrics/map.py; the user-metrics.jsonl saver of experiments/options.py:319-351).

@@ -224,6 +224,18 @@ class Engine:
         indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
         return recommend(self.P, self.Q, self.item_bias, users, k, indptr, indices, item_slices=item_slices)
 
+    def sample_items(self, users: torch.Tensor, k: int, exclude_seen: bool = True, **kw):
+        """`k` items per user drawn without replacement from softmax(score / temperature) over the user's
+        eligible items, in draw order, from the bound tables (`bpr_sample_rows`, see revisit_bpr/sample.py, which
+        takes the keywords: temperature, seed, draw_ids, return_keys, return_log_z, item_slices, check_users):
+        (items [n, k] int32, scores [n, k] float32[, keys][, log_z]), padded with -1 / -inf.  Eligibility is
+        `recommend`'s.  Rows an optimizer has not replayed yet are scored as they stand: `flush_lazy()` first
+        (`Model.sample_items` does)."""
+        from revisit_bpr.sample import sample_items
+
+        indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
+        return sample_items(self.P, self.Q, self.item_bias, users, k, indptr, indices, **kw)
+
     def retrieve(self, users: torch.Tensor, k: int, exclude_seen: bool = True, *, item_slices: int = 0):
         """`recommend` for `k` up to 1,024, the first stage of a two-stage recommender (`bpr_retrieve_rows`, see
         revisit_bpr/retrieve.py): the same scores, exclusions, order and padding, from the kernel that keeps its

@@ -476,6 +476,33 @@ class Model(torch.nn.Module):
             scores += ub.detach()[users.reshape(-1).long()].unsqueeze(1)
         return items, scores
 
+    def sample_items(self, users: torch.Tensor, k: int, exclude_seen: bool = True, **kw):
+        """`k` items per user drawn without replacement from softmax(score / temperature) over the user's
+        eligible items (the Plackett-Luce model), in draw order, from the engine's fused sampling kernel
+        (revisit_bpr/sample.py, which takes the keywords: temperature, seed, draw_ids, return_keys, return_log_z,
+        item_slices, check_users): (items [n, k] int32, scores [n, k] float32[, keys][, log_z]), padded with
+        -1 / -inf; eligibility is `recommend`'s.  Rows behind the optimizer step are replayed first (`sync()`).
+        A user bias shifts a whole row and so changes no probability: it is added to the returned scores, and
+        divided by the temperature to the keys and to log_z, so that `log_propensity` holds as it stands.  Only
+        the MF scorer has a fused form."""
+        if not self._fusable():
+            raise NotImplementedError("sample_items needs the MF logits model in float32: other scorers have no "
+                                      "fused sampling kernel")
+        eng = self.engine()
+        self.sync()
+        out = list(eng.sample_items(users, k, exclude_seen=exclude_seen, **kw))
+        ub = self.logits_model._user_bias
+        if ub is not None:
+            b = ub.detach()[users.reshape(-1).long()].reshape(-1)
+            out[1] += b.unsqueeze(1)
+            rest = 2
+            if kw.get("return_keys", False):
+                out[rest] += (b / float(kw.get("temperature", 1.0))).unsqueeze(1)
+                rest += 1
+            if kw.get("return_log_z", False):
+                out[rest] += b / float(kw.get("temperature", 1.0))
+        return tuple(out)
+
     def retrieve(self, users: torch.Tensor, k: int, exclude_seen: bool = True):
         """`recommend` for `k` up to 1,024 (revisit_bpr/retrieve.py): candidates for `rerank`, `diversify` or a
         ranker of the caller's, with `recommend`'s scores, exclusions, order and padding.  Rows behind the
