@@ -534,9 +534,19 @@ int bpr_set_sampler_iter(bpr_ctx* ctx, int64_t iteration);
  * RocAucManySlow (revisit_bpr/metrics/auc.py:70-130: every (positive, negative) pair of a row; 1 of the 14 metrics of
  * its ML-20M / MSD configs) without the [B, I, I] comparison or a sort per row: scores [n, I] fp32 row-major (masked
  * entries carry their mask value and count as negatives, as in the reference's eval loop), positives of row r =
- * pos_items[pos_indptr[r] .. pos_indptr[r + 1]); auc_out[r] = sum over the positives of #{negatives scored strictly
- * below} / (T (I - T)); NaN for a row without positives (0 / 0, as the metric classes) or with more than 4,096.
- * Context-free: runs on `hip_stream`. */
+ * pos_items[pos_indptr[r] .. pos_indptr[r + 1]) (pos_indptr [n + 1] int64, need not start at 0).
+ * THE CONTRACT, for one row with scores s[0 .. I) and the set Pos of its listed ids:
+ *   wins = #{(p, n) : p in Pos, n not in Pos, s[p] > s[n]} with IEEE '>': false whenever either side is NaN (a NaN
+ *          positive wins nothing, a NaN negative is beaten by nothing and still counts in I - T), -0 == +0,
+ *          subnormals compare by value, +-inf are ordinary values;
+ *   T = |Pos|;  auc_out[r] = (float)((double)wins / ((double)T * (double)(I - T)));
+ *   NaN when T == 0 or T == I (0 / 0, as the metric classes) and when T > 4,096 ("not computed": the caller's
+ *   sort-based path takes the row).  The result is a function of the row alone, not of the order of its ids.
+ * PRECONDITIONS, which the kernel cannot check without a fault path: every id lies in [0, I) (another id reads out of
+ * bounds), and the ids of a row are unique (a repeated id would count as two positives and win twice;
+ * evaluation.evaluate_topk removes repeats before the call).
+ * Held bit for bit to an all-pairs count by tests/test_gpu_auc.py (tests/auc_model.py).  Context-free: runs on
+ * `hip_stream`. */
 int bpr_auc_rows(const float* scores, int64_t n, int64_t I, const int64_t* pos_indptr, const int32_t* pos_items,
                  float* auc_out, void* hip_stream);
 

@@ -8,7 +8,24 @@
 // per row: the T positive scores are ranked in LDS (counting, T^2 / 256 per thread: T is tens), every score of the
 // row finds the number of positives <= it by binary search in LDS and bumps one bin of a (T + 1)-bin histogram; a
 // prefix sum of the bins gives "scores strictly below positive p", minus the positives among them.  One pass over
-// the scores, bit-for-bit the counts of the sort-based form.
+// the scores.
+//
+// THE CONTRACT (include/bprcore.h at bpr_auc_rows; held bit for bit by tests/test_gpu_auc.py against
+// tests/auc_model.py).  For a row with scores s[0 .. I) and the SET Pos of its listed ids:
+//   wins = #{(p, n) : p in Pos, n not in Pos, s[p] > s[n]}   with IEEE '>': false whenever either side is NaN,
+//                                                            -0 == +0, subnormals by value, +-inf ordinary values
+//   T = |Pos|;  result = float32(float64(wins) / (float64(T) * float64(I - T)))
+//   NaN for T == 0, for T == I (0 / 0) and for T > 4096 ("not computed": the caller's sort-based path takes the row).
+// Preconditions that the kernel cannot check without a fault path: ids in [0, I), and unique within a row (a
+// repeated id would be counted as two positives; evaluation.evaluate_topk removes repeats before the call).
+//
+// Where NaN goes.  The positives are ranked by a TOTAL order: non-NaN scores by value (ties by list index), every
+// NaN above +inf (among themselves by list index).  So the ranks are a permutation of 0 .. T - 1 whatever the
+// scores hold — every s_sorted slot that a later phase reads is written in this launch —, the K non-NaN positives
+// fill s_sorted[0 .. K) in ascending order and the NaN positives sit behind them, where the upper-bound search of a
+// non-NaN score never goes right of them (NaN <= x is false) and where the final sum stops: a NaN positive wins
+// nothing.  A NaN score of the row is not binned at all: it is below no positive, so it is nobody's win, but it
+// stays in I - T: a NaN negative is a pair that is lost.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -27,20 +44,25 @@ __global__ __launch_bounds__(256) void k_auc_rows(const float* __restrict__ scor
   const int64_t p0 = pos_indptr[row];
   const int T = (int)(pos_indptr[row + 1] - p0);
   const float* __restrict__ s = scores + row * I;
-  if (T <= 0 || T > AUC_T_MAX) {  // no positives: 0 / 0 as the metric classes; too many: NaN marks "not computed"
-    if (threadIdx.x == 0) auc[row] = nanf("");
+  if (T <= 0 || T > AUC_T_MAX || (int64_t)T >= I) {  // no positives or no negatives: 0 / 0 as the metric classes;
+    if (threadIdx.x == 0) auc[row] = nanf("");        // too many: NaN marks "not computed"
     return;
   }
-  // rank the positives' scores (ascending, ties by index): sorted[rank] = score  (staged through the bins' LDS)
+  // rank the positives' scores (ascending, NaN last, ties by index): sorted[rank] = score  (staged through the
+  // bins' LDS).  The order is total, so every slot 0 .. T - 1 of s_sorted is written
   float* const s_pos = reinterpret_cast<float*>(s_hist);
   for (int p = threadIdx.x; p < T; p += blockDim.x) s_pos[p] = s[pos_items[p0 + p]];
   __syncthreads();
   for (int p = threadIdx.x; p < T; p += blockDim.x) {
     const float sp = s_pos[p];
+    const bool p_nan = sp != sp;
     int rank = 0;
     for (int q = 0; q < T; ++q) {
       const float sq = s_pos[q];
-      rank += (sq < sp || (sq == sp && q < p)) ? 1 : 0;
+      const bool q_nan = sq != sq;
+      const bool before = p_nan ? !q_nan : sq < sp;           // (sq < sp is false for a NaN sq)
+      const bool equal = p_nan ? q_nan : sq == sp;
+      rank += (before || (equal && q < p)) ? 1 : 0;
     }
     s_sorted[rank] = sp;
   }
@@ -51,6 +73,7 @@ __global__ __launch_bounds__(256) void k_auc_rows(const float* __restrict__ scor
   uint32_t run_bin = 0xFFFFFFFFu, run_cnt = 0u;
   for (int64_t j = threadIdx.x; j < I; j += blockDim.x) {
     const float sj = s[j];
+    if (sj != sj) continue;  // NaN: below no positive (see the header)
     int lo = 0, hi = T;  // upper bound: first index with sorted > sj
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
@@ -73,6 +96,7 @@ __global__ __launch_bounds__(256) void k_auc_rows(const float* __restrict__ scor
     uint64_t below = 0;
     int first_equal = 0;
     for (int p = 0; p < T; ++p) {
+      if (s_sorted[p] != s_sorted[p]) break;  // the NaN positives, behind the others: no wins
       below += s_hist[p];
       if (p > 0 && s_sorted[p] != s_sorted[p - 1]) first_equal = p;
       wins += (double)(below - (uint64_t)first_equal);

@@ -66,23 +66,43 @@ def evaluate_topk(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: torch
     ROC-AUC of the reference's RocAucMany (metrics/auc.py:70-130: all positive / negative pairs of a
     row) from the same block of scores: on a ROCm device `bpr_auc_rows` (csrc/bpr_eval.hip, r6: one pass over the
     scores, the positives ranked in LDS), else by rank sums after one sort per block — instead of the [B, I, I]
-    comparison."""
+    comparison.  For `auc` a user's targets are a SET: a target counts once however often the eval CSR lists it, on
+    either device (the kernel wants unique ids: the repeats are dropped from a sorted key list before the block loop,
+    one pass over the targets, not over the scores); a pair with a NaN score on either side is not a win.  `n_pos` of
+    recall and ndcg stays the listed count (tests/rank_model.py)."""
     from revisit_bpr.metrics.auc import RocAucManySlow
 
     auc_metric = RocAucManySlow() if auc else None
     auc_sum = torch.zeros((), device=P.device, dtype=torch.float32)
     lib = None
+    dev = P.device
+    I = Q.shape[0]
+    E = eval_users.numel()
     if auc and P.is_cuda:  # r6: bpr_auc_rows — one pass over the scores instead of a sort per row
         from revisit_bpr import native
 
         lib = native.load()
-    dev = P.device
-    I = Q.shape[0]
+        # the targets of the whole call as sorted keys (row * I + item), as evaluate_fused builds them, the first of
+        # every run of equal keys kept: the CSR the kernel reads (u_ptr [E + 1] from 0, u_items), every id once per
+        # row.  No device-to-host copy but the first one: the kept keys are scattered to their places, the repeats
+        # to a spare slot behind them
+        first, last = (int(v) for v in eval_indptr[[0, E]].tolist())
+        total = last - first
+        ptr0 = (eval_indptr[:E + 1] - first).long()
+        keys = torch.repeat_interleave(torch.arange(E, device=dev), ptr0[1:] - ptr0[:-1], output_size=total) * I
+        keys = torch.sort(keys + eval_items[first:last].long()).values
+        keep = torch.ones(total, device=dev, dtype=torch.bool)
+        keep[1:] = keys[1:] != keys[:-1]
+        kept_before = torch.zeros(total + 1, device=dev, dtype=torch.int64)
+        kept_before[1:] = torch.cumsum(keep, 0)
+        u_ptr = kept_before[ptr0]
+        u_cnt = u_ptr[1:] - u_ptr[:-1]
+        u_items = torch.empty(total + 1, device=dev, dtype=torch.int32)
+        u_items.scatter_(0, torch.where(keep, kept_before[:-1], total), (keys % I).to(torch.int32))
     kmax = min(max(ks), I)
     disc = 1.0 / torch.log2(torch.arange(kmax, dtype=torch.float, device=dev) + 2.0)
     sums = {f"{m}@{k}": torch.zeros((), device=dev, dtype=torch.float64)
             for k in ks for m in ("ndcg", "recall", "precision")}
-    E = eval_users.numel()
     for lo in range(0, E, block):
         hi = min(lo + block, E)
         users = eval_users[lo:hi].long()
@@ -109,12 +129,11 @@ def evaluate_topk(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: torch
         if auc_metric is not None and lib is None:
             auc_metric(logits, target.float())
         elif auc_metric is not None:
-            ptr = (eval_indptr[lo:hi + 1] - eval_indptr[lo]).to(torch.int64).contiguous()
-            items = eval_items[int(t_lo[0]):int(t_hi[-1])].to(torch.int32).contiguous()
-            rows_auc = torch.empty(n, device=dev, dtype=torch.float32)
-            native.check(lib.bpr_auc_rows(logits.data_ptr(), n, I, ptr.data_ptr(), items.data_ptr(), rows_auc.data_ptr(),
-                                          torch.cuda.current_stream(dev).cuda_stream))
-            many = t_cnt > 4096  # (rows the kernel leaves to the sort-based form)
+            rows_auc = torch.full((n,), float("nan"), device=dev, dtype=torch.float32)
+            if total > 0:  # (the block's rows of the unique CSR: offsets into all of u_items)
+                native.check(lib.bpr_auc_rows(logits.data_ptr(), n, I, u_ptr[lo:hi + 1].data_ptr(), u_items.data_ptr(),
+                                              rows_auc.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            many = u_cnt[lo:hi] > 4096  # (rows the kernel leaves to the sort-based form)
             if bool(many.any()):
                 rows_auc[many] = auc_metric.compute(logits[many], target[many].float())
             auc_sum += rows_auc.sum()

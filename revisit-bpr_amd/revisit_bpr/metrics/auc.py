@@ -5,7 +5,8 @@ RocAucMany  : all (positive, negative) pairs of a row, dense [B, I, I] compariso
 RocAucManySlow : same quantity; the reference loops over users in Python, here it is one sort per
                  row — AUC = (sum of ranks of positives among valid items - n_pos(n_pos+1)/2) /
                  (n_pos n_neg) with strict '>' comparisons, which counts exactly the pairs
-                 pos > neg when scores are distinct and is corrected for ties below.
+                 pos > neg when scores are distinct and is corrected for ties below.  A pair with a
+                 NaN on either side is not a win, as in the pairwise forms (x > NaN, NaN > x: false).
 """
 from __future__ import annotations
 
@@ -69,10 +70,14 @@ class RocAucManySlow(_Auc):
         is_pos = target.ne(0)
         is_neg = target.eq(0) & mask.ne(0)
         # number of valid negatives strictly below each score: rank among negatives via sort
-        neg_scores = torch.where(is_neg, output, torch.full_like(output, float("inf")))
+        # x > NaN and NaN > x are false.  A NaN negative is below nothing: it joins the +inf fillers (left as NaN it
+        # would mislead searchsorted's bisection, which takes NaN for small) and still counts in n_neg.  A NaN positive
+        # (searchsorted would place it behind every negative) wins nothing
+        is_nan = torch.isnan(output)
+        neg_scores = torch.where(is_neg & ~is_nan, output, torch.full_like(output, float("inf")))
         sorted_neg, _ = torch.sort(neg_scores, dim=-1)
         below = torch.searchsorted(sorted_neg, output.contiguous(), right=False)  # strictly smaller
         n_neg = is_neg.sum(-1)
         below = torch.minimum(below, n_neg.unsqueeze(-1))
-        wins = (below * is_pos).sum(-1).float()
+        wins = (below * (is_pos & ~is_nan)).sum(-1).float()
         return wins / (is_pos.sum(-1) * n_neg).float()
