@@ -470,6 +470,9 @@ int bpr_bias_written(bpr_ctx* ctx);
  * bitmaps take at most `max_bytes` (default 1 GiB; 0 keeps the current cap) — the threshold is
  * doubled until they fit. */
 int bpr_set_heavy_users(bpr_ctx* ctx, int32_t threshold, int64_t max_bytes);
+/* The heavy table as the last sampling STREAM launch used it: `n` = users with a bitmap row (0: no table, or
+ * not built yet), `threshold` = the threshold it ended at (the requested one, doubled until the rows fit). */
+int bpr_heavy_users(bpr_ctx* ctx, int64_t* n, int32_t* threshold);
 
 /* ---- two-tier item reconciliation, HOT tier (several GPUs; no reference counterpart — the
  * reference's latent DDP, experiments/launcher.py:35-73, would all-reduce every gradient of every

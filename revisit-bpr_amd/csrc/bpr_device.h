@@ -162,17 +162,44 @@ struct SeenCsr {  // binary search in the user's sorted CSR slice (≈ log2(n_u)
 // seen CSR in HBM (288 GB make that cheap: a few thousand users x I/8 bytes) — building the LDS
 // structure costs a dependent HBM round trip per 128 seen items at every user change, and a user
 // with thousands of them is rebuilt by every group that walks one of its runs.  hoff = word offset
-// of the user's row in gbits, ~0u = light user (LDS structure).
+// of the user's row in the table, ~0u = light user (LDS structure built from the CSR).
+// Bitmap kernels (k_stream SEEN_BITMAP) STAGE a heavy user's row: at the user change the row — the
+// same W words as the group's LDS bitmap, 16-byte aligned — is copied into the LDS bitmap with
+// dwordx4 loads issued right behind the load of P[u] (heavy_stage), and every lookup of the
+// user's run is then the one ds_read a light user pays: SeenBitmap has no global branch.  (Read in
+// place, every candidate of every walk trip was a dependent global gather behind the order vector:
+// 612 against 832 M triples/s when all lookups are global, profiles/r06_hotlds.md.)  The staged-list
+// kernels (SeenList, item tables too large for bitmaps) still read the row in HBM.
 constexpr uint32_t NOT_HEAVY = 0xFFFFFFFFu;
 struct SeenBitmap {  // one LDS read: the group's I-bit bitmap of the current user (k_stream)
   const uint32_t* bm;
-  const uint32_t* __restrict__ gbits;
-  uint32_t hoff;
   __device__ __forceinline__ bool operator()(int32_t c) const {
-    const uint32_t w = hoff != NOT_HEAVY ? gbits[hoff + (uint32_t)(c >> 5)] : bm[c >> 5];
-    return ((w >> (c & 31)) & 1u) != 0u;
+    return ((bm[c >> 5] >> (c & 31)) & 1u) != 0u;
   }
 };
+// Copy a heavy user's row (W words, W a multiple of 4; both sides 16-byte aligned) into the group's
+// LDS bitmap: up to HEAVY_STAGE_VECS dwordx4 loads per lane in flight per trip — ONE trip at G = 32 up to
+// 32,768 items, so the copy costs one round trip.  Only the vectors the row has are loaded (ML-20M: 158
+// vectors, 5 per lane at G = 32): a slice of G vectors that starts past the end is skipped by a scalar
+// branch; inside the last slice the lanes past the end re-read the last vector and store nothing.
+constexpr int HEAVY_STAGE_VECS = 8;
+template <int G>
+__device__ __forceinline__ void heavy_stage(uint32_t* bm, const uint32_t* __restrict__ row, int W, int gl) {
+  uint4* bm4 = reinterpret_cast<uint4*>(bm);
+  const uint4* __restrict__ src = reinterpret_cast<const uint4*>(row);
+  const int n4 = W >> 2;
+  for (int kb = 0; kb < n4; kb += HEAVY_STAGE_VECS * G) {  // kb, n4: wave-uniform
+    uint4 v[HEAVY_STAGE_VECS];
+#pragma unroll
+    for (int q = 0; q < HEAVY_STAGE_VECS; ++q) {
+      v[q] = make_uint4(0u, 0u, 0u, 0u);
+      if (kb + q * G < n4) v[q] = src[min(kb + q * G + gl, n4 - 1)];
+    }
+#pragma unroll
+    for (int q = 0; q < HEAVY_STAGE_VECS; ++q)
+      if (kb + q * G + gl < n4) bm4[kb + q * G + gl] = v[q];
+  }
+}
 
 // the user's sorted seen list staged in LDS (k_stream, item tables too large for per-group
 // bitmaps): ≈ log2(n_u) LDS reads; users with more than the staged capacity use their HBM bitmap

@@ -526,7 +526,7 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) atomicOr(&bm[it[q] >> 5], 1u << (it[q] & 31));
       }
-      seen = SeenBitmap{bm, nullptr, NOT_HEAVY};
+      seen = SeenBitmap{bm};
     } else {
       seen = SeenCsr{a.indices, lo, hi};
     }

@@ -181,7 +181,7 @@ void k_stream(const StreamArgs a) {
     for (int k = gl; k < (W >> 2); k += G) bm4[k] = make_uint4(0u, 0u, 0u, 0u);
   }
   int32_t list_n = -1;
-  uint32_t hoff = NOT_HEAVY;       // current user's row in the heavy users' HBM bitmaps
+  uint32_t hoff = NOT_HEAVY;       // current user's row in the heavy users' HBM bitmaps (SEEN_LIST reads it in place)
   int64_t cur_lo = 0;              // CSR slice of the current user: indices[cur_lo .. cur_lo + cur_n)
   int32_t cur_n = 0;
   __shared__ float s_sigma[SAMPLER == NEG_ADAPTIVE ? G * E : 1];  // snapshot sigma (adaptive only)
@@ -232,6 +232,7 @@ void k_stream(const StreamArgs a) {
     int32_t my_u = 0, my_i = 0, my_si = -1;
     int64_t my_lo = 0;
     int32_t my_cnt = 0;  // the user's seen items: indices[my_lo .. my_lo + my_cnt)
+    uint32_t my_hoff = NOT_HEAVY;  // ... and, for a heavy user, the row of the heavy table (off the user-change chain)
     {
       const int tk = (gl == G - 1) ? t0 - 1 : t0 + gl;
       const bool in_run = run_act && gl < Lr && tk < t1;
@@ -243,6 +244,9 @@ void k_stream(const StreamArgs a) {
         if constexpr (SAMPLER != NEG_GIVEN) {
           my_lo = a.indptr[my_u];
           my_cnt = (int32_t)(a.indptr[my_u + 1] - my_lo);
+          if constexpr (SEEN == SEEN_BITMAP) {  // (the other kernels look it up at the user change)
+            if (a.heavy_off != nullptr && my_cnt > a.heavy_T) my_hoff = a.heavy_off[my_u];
+          }
         }
       }
     }
@@ -278,6 +282,8 @@ void k_stream(const StreamArgs a) {
       const int32_t i = group_bcast<G>(my_i, step, lane);
       const int64_t u_lo = group_bcast<G>(my_lo, step, lane);
       const int32_t u_cnt = group_bcast<G>(my_cnt, step, lane);
+      uint32_t u_hoff = NOT_HEAVY;
+      if constexpr (SEEN == SEEN_BITMAP) u_hoff = group_bcast<G>(my_hoff, step, lane);
       if (act && u != cur_u) {
         // ---- user change: write the previous user's row back, fetch the new one
         if (cur_u >= 0 && cur_u != a.pad_user) {
@@ -294,8 +300,15 @@ void k_stream(const StreamArgs a) {
         if constexpr (SAMPLER != NEG_GIVEN) {
           cur_lo = u_lo;
           cur_n = u_cnt;
-          hoff = NOT_HEAVY;
-          if (a.heavy_off != nullptr && cur_n > a.heavy_T) hoff = a.heavy_off[u];
+          hoff = u_hoff;
+          if constexpr (!BM) {
+            if (a.heavy_off != nullptr && cur_n > a.heavy_T) hoff = a.heavy_off[u];
+          }
+          if constexpr (BM) {
+            // a heavy user's precomputed row is STAGED: one copy of W words over the whole bitmap (no wipe), its
+            // loads issued behind P[u]'s (the compiler still waits for P[u] first: DESIGN.md §4.1)
+            if (hoff != NOT_HEAVY) heavy_stage<G>(bm, a.heavy_bits + hoff, W, gl);
+          }
           if (hoff == NOT_HEAVY) {
             if constexpr (BM) {
               // wipe: the whole bitmap with 16-byte LDS stores (W is a multiple of 4: 5 stores per
@@ -342,7 +355,7 @@ void k_stream(const StreamArgs a) {
             typename std::conditional<SEEN == SEEN_LIST, SeenList, SeenCsr>::type>::type;
         Seen seen;
         if constexpr (BM) {
-          seen = SeenBitmap{bm, a.heavy_bits, hoff};
+          seen = SeenBitmap{bm};
         } else if constexpr (SEEN == SEEN_LIST) {
           seen = SeenList{reinterpret_cast<const int32_t*>(bm), list_n, a.indices, cur_lo,
                           cur_lo + cur_n, a.heavy_bits, hoff};

@@ -660,7 +660,7 @@ __global__ __launch_bounds__(256, (E <= 4 ? VS_BLOCKS_E4 : (E <= 8 ? 2 : 1))) vo
           Seen seen;
           if constexpr (SEEN == SEEN_BITMAP) {
             seen_bitmap_build<G>(lds, a.bm_words, a.indices, lo, hi, gl);
-            seen = SeenBitmap{lds, nullptr, NOT_HEAVY};
+            seen = SeenBitmap{lds};
           } else if constexpr (SEEN == SEEN_LIST) {
             const int32_t ln = seen_list_build<G>(lds, a.bm_words, a.indices, lo, hi, gl);
             seen = SeenList{reinterpret_cast<const int32_t*>(lds), ln, a.indices, lo, hi, nullptr,

@@ -1344,6 +1344,15 @@ int bpr_set_heavy_users(bpr_ctx* c, int32_t threshold, int64_t max_bytes) {
   return BPR_OK;
 }
 
+int bpr_heavy_users(bpr_ctx* c, int64_t* n, int32_t* threshold) {
+  if (c == nullptr || n == nullptr || threshold == nullptr)
+    return fail(BPR_ERR_INVALID, "bpr_heavy_users: NULL argument");
+  const bool built = c->heavy_for != nullptr && c->heavy_for == c->indptr;
+  *n = built ? c->heavy_n : 0;
+  *threshold = built ? c->heavy_T : c->heavy_T_opt;
+  return BPR_OK;
+}
+
 int bpr_sync_cut(bpr_ctx* c, float* hot_base, float* hot_tot, int32_t hot_fold_prev, float* cold_base,
                  float* cold_own, float* cold_tot, float scale, int32_t cold_mode) {
   if (int rc = check_bound(c, "bpr_sync_cut")) return rc;

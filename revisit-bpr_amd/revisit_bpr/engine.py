@@ -151,7 +151,21 @@ class Engine:
         if os.environ.get("BPR_LDS_BLOCK"):
             self.set_tuning("lds_block", int(os.environ["BPR_LDS_BLOCK"]))
         if os.environ.get("BPR_HEAVY_T"):
-            native.check(self._lib.bpr_set_heavy_users(self._ctx, int(os.environ["BPR_HEAVY_T"]), 0))
+            self.set_heavy_users(int(os.environ["BPR_HEAVY_T"]))
+
+    def set_heavy_users(self, threshold: int, max_bytes: int = 0) -> None:
+        """``bpr_set_heavy_users``: users with more than `threshold` seen items (-1: none) get a precomputed seen
+        bitmap in HBM, which the bitmap STREAM kernels stage in LDS at a user change; the table takes at most
+        `max_bytes` (0: the current cap) — the threshold is doubled until it fits.  Rebuilt by the next sampling
+        STREAM launch."""
+        native.check(self._lib.bpr_set_heavy_users(self._ctx, int(threshold), int(max_bytes)))
+
+    def heavy_users(self) -> tuple[int, int]:
+        """``bpr_heavy_users``: (users with a row in the heavy table, the threshold it ended at) as the last sampling
+        STREAM launch used it; (0, requested threshold) before the table is built."""
+        n, t = ctypes.c_int64(), ctypes.c_int32()
+        native.check(self._lib.bpr_heavy_users(self._ctx, ctypes.byref(n), ctypes.byref(t)))
+        return int(n.value), int(t.value)
 
     def snapshot_partial(self) -> bool:
         """True while the snapshot the samplers read is a partial one (``bpr_adaptive_snapshot_partial``)."""

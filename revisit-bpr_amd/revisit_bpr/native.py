@@ -164,6 +164,7 @@ SIGNATURES = {
                                     c_void_p]),
     "bpr_set_hot_rows": (c_int, [c_void_p, c_int32, c_int32]),
     "bpr_set_heavy_users": (c_int, [c_void_p, c_int32, c_int64]),
+    "bpr_heavy_users": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int32)]),
     "bpr_set_hot_items": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "bpr_hot_rows": (c_int, [c_void_p, c_void_p]),
     "bpr_hot_tier_begin": (c_int, [c_void_p, c_void_p]),
