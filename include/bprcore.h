@@ -78,7 +78,13 @@ typedef enum bpr_mode {
 typedef enum bpr_sampler_kind {
   BPR_NEG_GIVEN = 0,   /* caller passes `neg` */
   BPR_NEG_UNIFORM = 1, /* revisit_bpr/modules/neg_samplers.py:31-37 (UniformSampler.sample) */
-  BPR_NEG_ADAPTIVE = 2 /* revisit_bpr/modules/neg_samplers.py:74-124 (AdaptiveSampler.sample) */
+  BPR_NEG_ADAPTIVE = 2, /* revisit_bpr/modules/neg_samplers.py:74-124 (AdaptiveSampler.sample) */
+  /* Dynamic negative sampling (extension; Zhang et al., SIGIR 2013): the highest-scoring of M unseen uniform
+   * candidates under the model as it is now (bpr_set_dynamic, bpr_sample_dynamic).  Accepted by bpr_train_stream /
+   * _cut (plain SGD); bpr_train_stream_acut, bpr_train_strict, bpr_train_stream_batched, the STRICT mode of bpr_step
+   * and the fold-in entry points return BPR_ERR_UNSUPPORTED for it before the device is touched: draw with
+   * bpr_sample_dynamic and pass the picks as BPR_NEG_GIVEN there. */
+  BPR_NEG_DYNAMIC = 3
 } bpr_sampler_kind;
 
 /* out_scalars layout written by bpr_forward_grad / bpr_step / bpr_train_stream (fp32, ADDED to —
@@ -126,6 +132,28 @@ int bpr_bind_opt_state(bpr_ctx* ctx, float* m_P, float* v_P, float* m_Q, float* 
  * negative does not depend on launch geometry or GPU count.  neg_out [B] int32. */
 int bpr_sample_uniform(bpr_ctx* ctx, const int32_t* users, int64_t B, uint64_t seed,
                        uint64_t offset, int32_t* neg_out);
+
+/* Dynamic negative sampling.  For the triple with counter t = offset + position, user u and M candidates:
+ *   candidates   bpr_sample_uniform's stream for (seed, t), item weights included: candidate k = 0 .. 4,095;
+ *   accepted     the candidates u has not seen; a_1 .. a_m = the first min(M, accepted) of them in order of k
+ *                (drawn with replacement: duplicates stay);
+ *   none         if none of the 4,096 is accepted the result is bpr_sample_uniform's (its exact pick by rank; item 0
+ *                when nothing is unseen);
+ *   score(a)     <P[u], Q[a]> (+ item_bias[a]) in fp32, on the rows as the kernel sees them;
+ *   pick         best = a_1; for i = 2 .. m: a_i replaces best if score(a_i) > score(best), or if score(best) is NaN
+ *                and score(a_i) is not.  Equal scores keep the earlier candidate, an all-NaN set keeps a_1.
+ * So M = 1 IS bpr_sample_uniform, and so is any M when all scores are equal.
+ * bpr_set_dynamic: M of the ctx's STREAM launches with BPR_NEG_DYNAMIC, 1 .. 32 (else BPR_ERR_INVALID), default 4 —
+ * a parameter of the method, not a bpr_set_tuning key.
+ * bpr_sample_dynamic: the stand-alone kernel, one draw per entry of users [B] from the ctx's tables, item_bias, seen
+ * CSR and item weights as they are in stream order; neg_out [B] int32, score_out [B] fp32 or NULL = the picks'
+ * scores.  It reduces a score in the order the STREAM kernel does at the ctx's embedding width, so on tables that do
+ * not move its picks are that kernel's, bit for bit.  candidates outside 1 .. 32, users or neg_out NULL, B < 0, no
+ * seen CSR: BPR_ERR_INVALID, nothing launched.  The rows are read as stored: with a stateful optimizer on the STRICT
+ * path call bpr_flush_lazy first. */
+int bpr_set_dynamic(bpr_ctx* ctx, int32_t candidates);
+int bpr_sample_dynamic(bpr_ctx* ctx, const int32_t* users, int64_t B, int32_t candidates, uint64_t seed,
+                       uint64_t offset, int32_t* neg_out, float* score_out /* may be NULL */);
 
 /* Item weights of the uniform sampler — BPRExperiment._static_sampling with
  * item_counts ** neg_sampling_alpha (experiments/bpr/exp.py:85-91, 282-293): P(negative = i) =
@@ -284,7 +312,9 @@ int bpr_get_grad(bpr_ctx* ctx, float* gP, float* gQ, float* gbias);
 /* One reference training iteration (example.py:172-180): sample (if sampler != GIVEN) →
  * forward → backward → optimizer step.  mode STRICT = phases A+B; mode STREAM = one fused launch
  * (SGD only).  `neg` is read when sampler == BPR_NEG_GIVEN, otherwise (if non-NULL) it receives
- * the sampled negatives.  seed/offset as in bpr_sample_uniform; adaptive_p = Geometric p. */
+ * the sampled negatives.  seed/offset as in bpr_sample_uniform; adaptive_p = Geometric p.
+ * BPR_NEG_DYNAMIC: mode STREAM only (STRICT: BPR_ERR_UNSUPPORTED — draw with bpr_sample_dynamic, step with
+ * BPR_NEG_GIVEN). */
 int bpr_step(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg, int64_t B,
              int32_t mode, int32_t sampler, float adaptive_p, uint64_t seed, uint64_t offset,
              float* out_logits_pos, float* out_logits_neg, float* out_scalars);
@@ -299,7 +329,8 @@ int bpr_step(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* ne
  * (neg_samplers.py:75,122-123): after that batch's negatives are drawn and before its optimizer
  * step; the batch counter belongs to the ctx and keeps counting across calls (epochs), as the
  * sampler's _iteration_cnt does (bpr_set_sampler_iter rewinds it).  With lazy optimizers the
- * refresh flushes first.  out_scalars accumulates over the epoch. */
+ * refresh flushes first.  out_scalars accumulates over the epoch.  BPR_NEG_DYNAMIC: BPR_ERR_UNSUPPORTED, checked
+ * before the device is touched. */
 int bpr_train_strict(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg_scratch,
                      int64_t n, int64_t B, int32_t sampler, float adaptive_p, uint64_t seed,
                      uint64_t offset, int64_t refresh_every, float* out_scalars);
@@ -310,7 +341,10 @@ int bpr_train_strict(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int
  * A model's item_bias is read and updated, for the duration of the launch, in a table of the
  * library's own (one item per 128-byte line: DESIGN.md §9.5), filled from the bound vector in stream
  * order before the launch and written back after it: the bound vector is current once the launch
- * has completed on the ctx stream, not while it runs. */
+ * has completed on the ctx stream, not while it runs.
+ * BPR_NEG_DYNAMIC (plain SGD, as every sampler here): each triple's negative is the hardest of bpr_set_dynamic's M
+ * candidates under the user row the kernel holds in registers and the item rows as it reads q_j (hot-row deltas
+ * included); `neg`, if non-NULL, receives the picks.  Such a launch never takes the LDS tier (bpr_set_hot_lds). */
 int bpr_train_stream(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg,
                      int64_t n, int32_t sampler, float adaptive_p, uint64_t seed, uint64_t offset,
                      int64_t max_inflight, float* out_scalars);
@@ -335,7 +369,8 @@ int bpr_train_stream_cut(bpr_ctx* ctx, const int32_t* users, const int32_t* pos,
  * r6 (default; bpr_set_tuning "acut_fold" 0 restores the form above): only the TRANSPOSE of the keys leaves the launch
  * stream — the fold of the hot block, the loss sums and the item_bias write-back stay on it (k_stream_epilogue, a few
  * microseconds) — so the item table is whole after every launch (bpr_hot_fold is a no-op), out_scalars arrives on the
- * launch stream, and the LDS tier (bpr_set_hot_lds) stays in use. */
+ * launch stream, and the LDS tier (bpr_set_hot_lds) stays in use.
+ * BPR_NEG_DYNAMIC has no snapshot to cut: BPR_ERR_UNSUPPORTED. */
 int bpr_train_stream_acut(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg,
                           int64_t n, int32_t sampler, float adaptive_p, uint64_t seed,
                           uint64_t offset, int64_t max_inflight, float* out_scalars);
@@ -358,7 +393,8 @@ int bpr_hot_fold(bpr_ctx* ctx);
  * batch; such a user row takes its optimizer step at once, under the row's lock, instead of parking
  * the gradient for the row's next visitor (same arithmetic, bit-identical in the max_inflight = 1
  * limit).  On by default except for Adam on a model with item_bias;
- * bpr_set_tuning(ctx, "vs_direct", 0 / 1) forces it off / on (a measurement and test aid). */
+ * bpr_set_tuning(ctx, "vs_direct", 0 / 1) forces it off / on (a measurement and test aid).
+ * BPR_NEG_DYNAMIC: BPR_ERR_UNSUPPORTED, checked before the device is touched. */
 int bpr_train_stream_batched(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg,
                              int64_t n, int64_t B, int32_t sampler, float adaptive_p,
                              uint64_t seed, uint64_t offset, int64_t max_inflight,
@@ -705,7 +741,7 @@ int bpr_rank_rows(const float* P, const float* Q, const float* item_bias /* or N
  * launch.  order [n] int32 or NULL: a permutation of the rows, the sequence in which they are handed to the groups of
  * the launch (longest rows first evens out the tail; NULL = list order; an entry outside [0, n) is passed over).
  * d in [1, 1024] (0: BPR_ERR_INVALID, more: BPR_ERR_UNSUPPORTED); n below 2^31; I * d and epochs * nnz below 2^31
- * (BPR_ERR_UNSUPPORTED); BPR_NEG_ADAPTIVE: BPR_ERR_UNSUPPORTED.  Arguments are validated before the device is
+ * (BPR_ERR_UNSUPPORTED); BPR_NEG_ADAPTIVE, BPR_NEG_DYNAMIC: BPR_ERR_UNSUPPORTED.  Arguments are validated before the device is
  * touched; n == 0 is BPR_OK.  indptr is read by the kernel only, except for ONE host read: the call copies indptr[0]
  * and indptr[n] back for the bound on epochs * nnz and waits for `hip_stream` to do so (the launch itself is
  * asynchronous; the call cannot be captured into a graph).  A device's first call allocates a few ticket words that
@@ -771,7 +807,7 @@ int bpr_fold_in_rows_adaptive(const float* Q, const float* item_bias /* or NULL 
  * the bits of Q_new, bias_new and neg_out do not depend on `order`, on m or the other rows, on the launch or on the
  * kernel's prefetch depth.  order [m] int32 or NULL: as bpr_fold_in_rows' (an entry outside [0, m) is passed over).
  * d in [1, 1024] (0: BPR_ERR_INVALID, more: BPR_ERR_UNSUPPORTED); m below 2^31; I * d, U * d and epochs * nnz below
- * 2^31 (BPR_ERR_UNSUPPORTED); BPR_NEG_ADAPTIVE: BPR_ERR_UNSUPPORTED; NaN lr or alpha_item: BPR_ERR_INVALID.  Arguments
+ * 2^31 (BPR_ERR_UNSUPPORTED); BPR_NEG_ADAPTIVE, BPR_NEG_DYNAMIC: BPR_ERR_UNSUPPORTED; NaN lr or alpha_item: BPR_ERR_INVALID.  Arguments
  * are validated before the device is touched; m == 0 is BPR_OK.  indptr is read by the kernel only, except for ONE
  * host read, bpr_fold_in_rows': the call copies indptr[0] and indptr[m] back for the bound on epochs * nnz and waits
  * for `hip_stream` to do so (the launch itself is asynchronous; the call cannot be captured into a graph).  It shares

@@ -34,6 +34,7 @@ struct bpr_ctx {
   float au = 0.f, ai = 0.f, an = 0.f;
   const float* w_accept = nullptr;  // item weights of the uniform sampler (alias table, caller-owned)
   const int32_t* w_alias = nullptr;
+  int dyn_M = 4;  // bpr_set_dynamic: candidates of a BPR_NEG_DYNAMIC draw (DYNAMIC_DEFAULT, bpr_dynamic_plan.h)
   int opt_kind = BPR_OPT_SGD;
   bpr_opt_params opt = {0.f, 0.f, 0.f, 0, 0.9f, 0.999f, 1e-8f, 0.99f};
   float *mP = nullptr, *vP = nullptr, *mQ = nullptr, *vQ = nullptr, *mb = nullptr, *vb = nullptr;

@@ -50,6 +50,9 @@ inline int dispatch_ge(int G, int E, F&& f) {
 struct StreamArgs;
 struct StreamPlan;
 int launch_stream_lds(bpr_ctx* c, const StreamArgs& a, int sampler, const StreamPlan& p, hipEvent_t stop);
+// bpr_dynamic.hip: the plain k_stream with dynamic negatives for the ctx's shape and a "seen?" structure
+using StreamKernelFn = void (*)(const StreamArgs);
+int stream_kernel_dynamic(const bpr_ctx* c, int seen, StreamKernelFn* out);
 
 struct Timer {
   bpr_ctx* c;

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "bpr_device.h"
+#include "bpr_dynamic.h"
 
 namespace bpr {
 
@@ -77,6 +78,7 @@ struct StreamArgs {
   const int32_t* hot_by_rank;
   int32_t lds_only;      // 1: hot rows past lds_L are updated in Q like cold rows (no hot tier that wants their deltas)
   int32_t tail1, tail2;  // LDSHOT: first triple of the zones of runs of run_len / 2 and run_len / 4 (n: no such zone)
+  int32_t dyn_M;         // NEG_DYNAMIC: candidates scored per triple (bpr_set_dynamic)
 };
 
 // A hot row's value is its base row plus its replica delta rows; returns where this wave adds its
@@ -96,6 +98,29 @@ __device__ __forceinline__ int32_t hot_row(float (&q)[E], const float* __restric
   }
   return ~(int32_t)((uint32_t)((wave & rmask) * H + slot) * (uint32_t)d);
 }
+// (the offset alone, for a row whose value the caller already holds)
+__device__ __forceinline__ int32_t hot_row_enc(int32_t slot, int32_t H, int32_t rmask, int wave, int d) {
+  return ~(int32_t)((uint32_t)((wave & rmask) * H + slot) * (uint32_t)d);
+}
+// k_stream's item rows as sample_dynamic reads its candidates (bpr_dynamic.h): what the kernel reads q_j with —
+// the row, its replica deltas if it is hot, its entry of the wide bias table.  tag = the row's hot slot.
+template <int G, int E>
+struct StreamRows {
+  const float* Q;
+  const float* bias;
+  const int32_t* hot_slot;
+  const float* hot_delta;
+  int32_t H, rmask;
+  int d;
+  __device__ __forceinline__ int32_t load(float (&q)[E], float& b, int32_t item, int gl) const {
+    load_row<G, E>(q, Q + (uint32_t)item * (uint32_t)d, d, gl);
+    if (bias != nullptr) b = bias[(uint32_t)item * (uint32_t)BIAS_LINE];
+    return hot_slot != nullptr ? hot_slot[item] : -1;
+  }
+  __device__ __forceinline__ void finish(float (&q)[E], int32_t tag, int gl) const {
+    if (tag >= 0) (void)hot_row<G, E>(q, hot_delta, tag, H, rmask, 0, d, gl);
+  }
+};
 __device__ __forceinline__ float* row_at(float* Q, float* delta, int32_t enc) {
   return enc >= 0 ? Q + (uint32_t)enc : delta + (uint32_t)(~enc);
 }
@@ -148,11 +173,15 @@ struct SigmaLds {
 template <int G, int E, int SAMPLER, int SEEN, bool FULL, bool PART = false, bool LDSHOT = false>
 __global__ __launch_bounds__(LDSHOT ? 1024 : 256,
                              (LDSHOT ? (E <= 4 ? 4 : (E <= 8 ? 3 : 2))
+                                     // (dynamic negatives keep eight candidate rows in registers: 3 waves at E = 4
+                                     // instead of spilling them — the sampler is there to have loads in flight)
+                                     : SAMPLER == NEG_DYNAMIC ? (E <= 2 ? BPR_STREAM_WAVES_PER_EU - 1 : (E <= 8 ? 3 : 2))
                                      : (E <= 4 ? ((SAMPLER == NEG_ADAPTIVE && SEEN == SEEN_LIST) || PART
                                                       ? BPR_STREAM_WAVES_PER_EU - 1
                                                       : BPR_STREAM_WAVES_PER_EU)
                                                : (E <= 8 ? 3 : 2))))
 void k_stream(const StreamArgs a) {
+  static_assert(!(LDSHOT && SAMPLER == NEG_DYNAMIC), "dynamic negatives: the plain kernel only");
   constexpr int GPW = 64 / G;
   const int lane = threadIdx.x & 63;
   const int gl = lane & (G - 1);
@@ -347,6 +376,8 @@ void k_stream(const StreamArgs a) {
       }
 
       int32_t j;
+      DynamicPick pick = {0, 0.f, 0.f, -1};  // NEG_DYNAMIC: the negative comes with its row (qj) and bias
+      float qj[E];
       if constexpr (SAMPLER == NEG_GIVEN) {
         j = a.neg[tt];
       } else {
@@ -378,6 +409,12 @@ void k_stream(const StreamArgs a) {
             j = sample_uniform<G>(seen, (int64_t)cur_n, a.indices + cur_lo, a.I, a.seed,
                                   a.offset + (uint64_t)tt, lane, a.iw);
           }
+        } else if constexpr (SAMPLER == NEG_DYNAMIC) {
+          // the hardest of dyn_M unseen candidates under the live user row pl (bpr_dynamic.h)
+          const StreamRows<G, E> rows{a.Q, a.bias, a.hot_slot, a.hot_delta, a.hot_H, a.hot_rmask, d};
+          pick = sample_dynamic<G, E>(qj, pl, rows, seen, (int64_t)cur_n, a.indices + cur_lo, a.I, a.seed,
+                                      a.offset + (uint64_t)tt, a.dyn_M, lane, a.iw);
+          j = pick.item;
         } else {
           const AdaptiveRandoms rnd = {group_bcast<G>(my_rnd.uf, step, lane),
                                        group_bcast<G>(my_rnd.r, step, lane)};
@@ -400,9 +437,9 @@ void k_stream(const StreamArgs a) {
       // only sit in registers while the sampler runs (they, not issue slots, bound the occupancy)
       int32_t irow = (int32_t)((uint32_t)i * (uint32_t)d);  // encoded row offsets (hot_row)
       int32_t jrow = (int32_t)((uint32_t)j * (uint32_t)d);
-      float qi[E], qj[E];
+      float qi[E];
       load_row<G, E>(qi, a.Q + (uint32_t)irow, d, gl);
-      load_row<G, E>(qj, a.Q + (uint32_t)jrow, d, gl);
+      if constexpr (SAMPLER != NEG_DYNAMIC) load_row<G, E>(qj, a.Q + (uint32_t)jrow, d, gl);
       const int32_t si = group_bcast<G>(my_si, step, lane);
       if constexpr (LDSHOT) {
         // codes (StreamArgs::lds_L): rank < lds_L -> this workgroup's LDS delta row, else the global block
@@ -419,7 +456,9 @@ void k_stream(const StreamArgs a) {
         }
       } else {
         if (si >= 0) irow = hot_row<G, E>(qi, a.hot_delta, si, a.hot_H, a.hot_rmask, wave, d, gl);
-        if (a.hot_slot != nullptr) {
+        if constexpr (SAMPLER == NEG_DYNAMIC) {  // (qj already holds the row with its deltas)
+          if (pick.tag >= 0) jrow = hot_row_enc(pick.tag, a.hot_H, a.hot_rmask, wave, d);
+        } else if (a.hot_slot != nullptr) {
           const int32_t sj = a.hot_slot[j];
           if (sj >= 0) jrow = hot_row<G, E>(qj, a.hot_delta, sj, a.hot_H, a.hot_rmask, wave, d, gl);
         }
@@ -427,7 +466,8 @@ void k_stream(const StreamArgs a) {
       float bi = 0.f, bj = 0.f;
       if (a.bias != nullptr) {
         bi = a.bias[(uint32_t)i * (uint32_t)BIAS_LINE];
-        bj = a.bias[(uint32_t)j * (uint32_t)BIAS_LINE];
+        if constexpr (SAMPLER == NEG_DYNAMIC) bj = pick.bias;
+        else bj = a.bias[(uint32_t)j * (uint32_t)BIAS_LINE];
       }
 
       // x_uij = <p_u, q_i - q_j> (+ bias difference): one group sum

@@ -12,11 +12,12 @@
 #include "bpr_host.h"
 #include "bpr_stream_plan.h"
 #include "bpr_refresh_plan.h"
+#include "bpr_dynamic_plan.h"
 
 namespace bpr {
 static_assert(ORDER_PAD == BPR_ORDER_PAD, "walk vector width vs snapshot padding");
 static_assert(SEEN_CSR == STREAM_SEEN_CSR && SEEN_BITMAP == STREAM_SEEN_BITMAP && SEEN_LIST == STREAM_SEEN_LIST &&
-                  NEG_GIVEN == BPR_NEG_GIVEN,
+                  NEG_GIVEN == BPR_NEG_GIVEN && NEG_DYNAMIC == BPR_NEG_DYNAMIC,
               "the launch plan names the kernels' template arguments");
 
 static thread_local std::string g_last_error;
@@ -293,8 +294,6 @@ static int stream_cus(bpr_ctx* c) {
 }
 
 // ---- STREAM ------------------------------------------------------------------------------------
-using StreamKernelFn = void (*)(const StreamArgs);
-
 template <int G, int E, int SMP, int SN>
 static StreamKernelFn stream_kernel_of(bool full, bool part) {
   if constexpr (SMP == NEG_ADAPTIVE)  // a partial snapshot: the instantiations whose walk can finish inside a bin
@@ -309,6 +308,7 @@ static StreamKernelFn stream_kernel_seen(int seen, bool full, bool part) {
 }
 // the plain k_stream instantiation for the ctx's shape (the LDSHOT ones: bpr_hotlds.hip)
 static int stream_kernel(const bpr_ctx* c, int sampler, int seen, bool part, StreamKernelFn* out) {
+  if (sampler == NEG_DYNAMIC) return stream_kernel_dynamic(c, seen, out);  // (bpr_dynamic.hip)
   return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
     using T = decltype(tag);
     constexpr int G = T::G, E = T::E;
@@ -543,7 +543,7 @@ int check_sampler(const bpr_ctx* c, const char* who, int32_t sampler, float adap
     if (neg == nullptr && B > 0) return fail(BPR_ERR_INVALID, std::string(who) + ": neg is NULL");
     return BPR_OK;
   }
-  if (sampler != BPR_NEG_UNIFORM && sampler != BPR_NEG_ADAPTIVE)
+  if (sampler != BPR_NEG_UNIFORM && sampler != BPR_NEG_ADAPTIVE && sampler != BPR_NEG_DYNAMIC)
     return fail(BPR_ERR_INVALID, std::string(who) + ": unknown sampler");
   if (c->indptr == nullptr) return fail(BPR_ERR_INVALID, std::string(who) + ": seen CSR not bound");
   if (sampler == BPR_NEG_ADAPTIVE) {
@@ -657,10 +657,9 @@ int bpr_bind_tables(bpr_ctx* c, float* P, int64_t U, float* Q, int64_t I, int32_
   c->keys_cut = false;
   c->U = U; c->I = I; c->d = d;
   c->pad_user = pad_user; c->pad_item = pad_item;
-  c->G = d <= 128 ? 32 : 64;
-  const int per_lane = (d + c->G - 1) / c->G;
-  c->E = c->G == 32 ? (per_lane <= 1 ? 1 : per_lane <= 2 ? 2 : 4)
-                    : (per_lane <= 4 ? 4 : per_lane <= 8 ? 8 : 16);
+  const GroupShape g = group_shape(d);  // (bpr_dynamic_plan.h: G = 32 up to d = 128, else 64)
+  c->G = g.G;
+  c->E = g.E;
   return BPR_OK;
 }
 
@@ -1040,6 +1039,8 @@ static int train_stream_impl(bpr_ctx* c, const int32_t* users, const int32_t* po
                              int64_t n, int32_t sampler, float adaptive_p, uint64_t seed,
                              uint64_t offset, int64_t max_inflight, float* out_scalars, bool cut,
                              bool acut = false) {
+  if (acut && sampler == BPR_NEG_DYNAMIC)
+    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_stream_acut: dynamic negatives have no snapshot to cut");
   if (c != nullptr) c->acut_call = acut;  // (check_bound folds pending hot deltas for everybody else)
   const int rc0 = check_triples(c, "bpr_train_stream", users, pos, n);
   if (c != nullptr) c->acut_call = false;
@@ -1079,6 +1080,7 @@ static int train_stream_impl(bpr_ctx* c, const int32_t* users, const int32_t* po
   a.au = c->au; a.ai = c->ai; a.an = c->an; a.lr = c->opt.lr;
   a.iw = ItemWeights{c->w_accept, c->w_alias};
   a.inv_log1mp = sampler == BPR_NEG_ADAPTIVE ? inv_log1mp(adaptive_p) : 0.f;
+  a.dyn_M = c->dyn_M;
   if (sampler != BPR_NEG_GIVEN) {
     if (int rc = heavy_build_impl(c)) return rc;
     a.heavy_off = c->heavy_off;
@@ -1132,6 +1134,9 @@ int bpr_hot_fold(bpr_ctx* c) {
 int bpr_step(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg, int64_t B,
              int32_t mode, int32_t sampler, float adaptive_p, uint64_t seed, uint64_t offset,
              float* out_logits_pos, float* out_logits_neg, float* out_scalars) {
+  if (sampler == BPR_NEG_DYNAMIC && mode == BPR_MODE_STRICT)
+    return fail(BPR_ERR_UNSUPPORTED, "bpr_step: dynamic negatives in STRICT mode: draw with bpr_sample_dynamic and "
+                                     "pass the picks as BPR_NEG_GIVEN");
   if (int rc = check_triples(c, "bpr_step", users, pos, B)) return rc;
   if (int rc = check_sampler(c, "bpr_step", sampler, adaptive_p, neg, B)) return rc;
   if (mode == BPR_MODE_STREAM) {
@@ -1159,6 +1164,9 @@ int bpr_step(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg,
 int bpr_train_strict(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg_scratch,
                      int64_t n, int64_t B, int32_t sampler, float adaptive_p, uint64_t seed,
                      uint64_t offset, int64_t refresh_every, float* out_scalars) {
+  if (sampler == BPR_NEG_DYNAMIC)
+    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_strict: dynamic negatives: draw each batch with bpr_sample_dynamic "
+                                     "and step with BPR_NEG_GIVEN");
   if (int rc = check_triples(c, "bpr_train_strict", users, pos, n)) return rc;
   if (B < 1) return fail(BPR_ERR_INVALID, "bpr_train_strict: B must be >= 1");
   if (int rc = check_sampler(c, "bpr_train_strict", sampler, adaptive_p, neg_scratch, n)) return rc;

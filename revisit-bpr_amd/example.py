@@ -26,7 +26,7 @@ from revisit_bpr.fast import StreamTrainer
 from revisit_bpr.metrics import NDCG, Precision, Recall, RocAucManySlow
 from revisit_bpr.models import BPR
 from revisit_bpr.models.bpr import MF
-from revisit_bpr.modules import AdaptiveSampler
+from revisit_bpr.modules import AdaptiveSampler, DynamicSampler
 
 log = logging.getLogger("example")
 
@@ -75,6 +75,12 @@ def strict_epoch(model, optimizer, sampler, users, items, seen_pad, batch_size, 
 @click.option("--seed", type=int, default=13, show_default=True)
 @click.option("--lr", type=float, default=0.00943667980759196, show_default=True)
 @click.option("--sampling-prob", type=float, default=1 / 700, show_default=True)
+@click.option("--sampler", "sampler_name", type=click.Choice(["adaptive", "dynamic"]), default="adaptive",
+              show_default=True, help="adaptive: the reference's adaptive oversampling; dynamic: the highest-scoring of "
+                                      "--candidates unseen uniform candidates under the live model (stream: fused; "
+                                      "strict on one GPU: drawn per batch, any --optimizer)")
+@click.option("--candidates", type=click.IntRange(1, 32), default=4, show_default=True,
+              help="--sampler dynamic: candidates scored per triple")
 @click.option("--mode", type=click.Choice(["stream", "batched", "strict"]), default="stream", show_default=True,
               help="stream: fused SGD launches (StreamTrainer); batched: one launch per refresh period with "
                    "virtual mini-batches, any --optimizer (BatchedStreamTrainer); strict: the reference's "
@@ -88,7 +94,7 @@ def strict_epoch(model, optimizer, sampler, users, items, seen_pad, batch_size, 
 @click.option("--refresh-cus", type=int, default=64, show_default=True,
               help="stream mode with --refresh-lag > 0: CUs the snapshot sort is masked to")
 def main(dataset_path, synthetic_name, num_users, num_items, embedding_dim, batch_size, epochs,
-         seed, lr, sampling_prob, mode, opt_name, refresh_lag, refresh_cus):
+         seed, lr, sampling_prob, sampler_name, candidates, mode, opt_name, refresh_lag, refresh_cus):
     logging.basicConfig(level=logging.INFO, format="%(asctime)s | %(message)s")
     if not torch.cuda.is_available():
         raise SystemExit("example.py needs an MI355X (no CPU path)")
@@ -132,6 +138,8 @@ def main(dataset_path, synthetic_name, num_users, num_items, embedding_dim, batc
 
     if mode == "stream" and opt_name != "sgd":
         raise SystemExit("--mode stream is the fused SGD kernel; use --mode batched for --optimizer " + opt_name)
+    if sampler_name == "dynamic" and (mode == "batched" or (mode == "strict" and world > 1)):
+        raise SystemExit("--sampler dynamic runs with --mode stream, or --mode strict on one GPU")
     if mode == "batched":
         from revisit_bpr.fast import BatchedStreamTrainer
 
@@ -159,7 +167,7 @@ def main(dataset_path, synthetic_name, num_users, num_items, embedding_dim, batc
             f = model.logits_model.get_features()
             sync = ItemSync([f["item"].data] + ([f["item_bias"].data] if f["item_bias"] is not None else []))
         trainer = StreamTrainer(model, users_t, items_t, t["indptr"], t["indices"], lr=lr,
-                                sampler="adaptive", adaptive_p=sampling_prob,
+                                sampler=sampler_name, candidates=candidates, adaptive_p=sampling_prob,
                                 batch_size=batch_size, seed=seed, rank=rank, item_sync=sync,
                                 refresh_lag="auto" if refresh_lag < 0 else refresh_lag,
                                 refresh_cus=refresh_cus if refresh_lag > 0 else 0)
@@ -182,8 +190,11 @@ def main(dataset_path, synthetic_name, num_users, num_items, embedding_dim, batc
         model.bind_seen_csr(t["indptr"], t["indices"])
         optimizer = make_optimizer()
         gen = torch.Generator(device=dev).manual_seed(seed)
-        sampler = AdaptiveSampler(model, num_items=num_items, sampling_prob=sampling_prob,
-                                  every=every, neg_gen=gen)
+        if sampler_name == "dynamic":
+            sampler = DynamicSampler(model, num_items=num_items, num_candidates=candidates, seed=seed)
+        else:
+            sampler = AdaptiveSampler(model, num_items=num_items, sampling_prob=sampling_prob,
+                                      every=every, neg_gen=gen)
         sampler.update_stats()
         model.train()
 

@@ -12,11 +12,11 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
-from revisit_bpr.native import (MODE_STREAM, MODE_STRICT, NEG_ADAPTIVE, NEG_GIVEN, NEG_UNIFORM,
+from revisit_bpr.native import (MODE_STREAM, MODE_STRICT, NEG_ADAPTIVE, NEG_DYNAMIC, NEG_GIVEN, NEG_UNIFORM,
                                 OPT_ADAM, OPT_MOMENTUM, OPT_RMSPROP, OPT_SGD)
 
 __all__ = ["Engine", "MaskedStream", "cu_mask", "resolve_reg_alphas", "MODE_STREAM", "MODE_STRICT", "NEG_ADAPTIVE",
-           "NEG_GIVEN", "NEG_UNIFORM", "OPT_ADAM", "OPT_MOMENTUM", "OPT_RMSPROP", "OPT_SGD"]
+           "NEG_DYNAMIC", "NEG_GIVEN", "NEG_UNIFORM", "OPT_ADAM", "OPT_MOMENTUM", "OPT_RMSPROP", "OPT_SGD"]
 
 
 def resolve_reg_alphas(reg_alphas: Optional[dict]) -> tuple[float, float, float]:
@@ -468,6 +468,23 @@ class Engine:
                                                   offset, out.data_ptr()))
         return out
 
+    def set_dynamic(self, candidates: int) -> None:
+        """Candidates per triple of `train_stream(sampler=NEG_DYNAMIC)` (``bpr_set_dynamic``): 1 .. 32, default 4."""
+        native.check(self._lib.bpr_set_dynamic(self._ctx, int(candidates)))
+
+    def sample_dynamic(self, users: torch.Tensor, candidates: int, seed: int, offset: int = 0,
+                       return_scores: bool = False):
+        """Dynamic negative sampling (``bpr_sample_dynamic``): per entry of `users` the highest-scoring of the first
+        `candidates` unseen items of `sample_uniform`'s candidate stream, scored on the tables as they are now.
+        candidates = 1 is `sample_uniform`.  return_scores: also the picks' scores, fp32."""
+        self._sync_stream()
+        users = self._ids(users, "users")
+        out = torch.empty_like(users)
+        score = torch.empty(users.numel(), dtype=torch.float32, device=self.device) if return_scores else None
+        native.check(self._lib.bpr_sample_dynamic(self._ctx, users.data_ptr(), users.numel(), int(candidates), seed,
+                                                  offset, out.data_ptr(), _ptr(score)))
+        return (out, score) if return_scores else out
+
     def adaptive_refresh(self) -> None:
         """AdaptiveSampler.update_stats: snapshot of the item table as of now, in stream order."""
         self._sync_stream()
@@ -706,7 +723,8 @@ class Engine:
         added to.  cut=True: the launch's epilogue also cuts the keys of the next adaptive snapshot
         (``bpr_train_stream_cut``) — the next `adaptive_refresh_begin` only queues the sort.
         cut="async": that cut runs on the side stream beside the NEXT launch and folds nothing
-        (``bpr_train_stream_acut``); call `hot_fold()` before reading the item table's storage."""
+        (``bpr_train_stream_acut``); call `hot_fold()` before reading the item table's storage.
+        sampler=NEG_DYNAMIC: the hardest of `set_dynamic`'s candidates per triple; `neg` (if given) receives the picks."""
         self._sync_stream()
         if users.dtype != torch.int32 or pos.dtype != torch.int32:
             raise ValueError("train_stream takes int32 id tensors (no hidden copies on the hot path)")

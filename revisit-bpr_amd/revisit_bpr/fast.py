@@ -199,7 +199,14 @@ def resolve_schedule(I: int, d: int, n: int, batch_size: int, lr: float, sampler
         raise ValueError("refresh_lag must be in [0, 1] or 'auto'")
     if not auto_lag and not 0.0 <= refresh_lag <= 1.0 or refresh_split < 1:
         raise ValueError("refresh_lag must be in [0, 1], refresh_split >= 1")
-    adaptive = {"adaptive": True, "uniform": False}[sampler]
+    # "dynamic" (the hardest of M uniform candidates, scored on the live rows) is scheduled as "uniform" is — no
+    # snapshot, so no refresh and no lag — and without the LDS tier, whose rows are not live: "auto" is 0, rows asked
+    # for are refused
+    adaptive = {"adaptive": True, "uniform": False, "dynamic": False}[sampler]
+    if sampler == "dynamic":
+        if not isinstance(hot_lds, str) and int(hot_lds) != 0:
+            raise ValueError("sampler 'dynamic' scores its candidates on the live item rows: no LDS tier (hot_lds 0)")
+        hot_lds = 0
     world = max(world, 1)
     every = max(1, int(I * math.log(I) / batch_size))
     # one refresh period = every*batch_size triples of the WHOLE job: with the users sharded
@@ -251,10 +258,14 @@ class StreamTrainer:
                  refresh_lag: float | str = 0.0, refresh_split: int = 1, refresh_cus: int = 0,
                  shard_refresh: bool = False, cadence: str = "job", hot_split: int = 1,
                  rounds: Optional[int] = None, jit_plan: bool = False, async_cut: bool | str = "auto",
-                 hot_lds: int | str = "auto", launch_split: int | str = "auto") -> None:
+                 hot_lds: int | str = "auto", launch_split: int | str = "auto", candidates: int = 4) -> None:
         """model: revisit_bpr.models.BPR on a ROCm device; users/items: int32 training triples on
         the device; seen CSR: int64 indptr [U+1], int32 indices.  `batch_size` only sets the
         adaptive refresh period int(I·ln I / batch_size) batches, as example.py:302.
+
+        sampler "dynamic" (extension): dynamic negative sampling — per triple the highest-scoring of `candidates`
+        (1 .. 32) unseen uniform candidates under the live rows (`Engine.set_dynamic`).  Scheduled as
+        "uniform": no snapshot, no refresh, no lag, no LDS tier.
 
         Snapshot schedule of the adaptive sampler (extensions; the defaults are the reference's
         ``update_stats`` every period, neg_samplers.py:122-132):
@@ -335,7 +346,9 @@ class StreamTrainer:
         self.engine.bind_seen_csr(seen_indptr, seen_indices)
         model._has_csr = True
         self.engine.set_optimizer(eng.OPT_SGD, lr=lr)
-        self.sampler = {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM}[sampler]
+        self.sampler = {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM, "dynamic": eng.NEG_DYNAMIC}[sampler]
+        if self.sampler == eng.NEG_DYNAMIC:
+            self.engine.set_dynamic(candidates)
         self.adaptive_p = adaptive_p
         self.cadence = cadence
         self.launch_split, self.chunk = sched.launch_split, sched.chunk
@@ -565,6 +578,13 @@ class StreamTrainer:
         self.epoch += 1
 
 
+def _refuse_dynamic(sampler: str, who: str) -> None:
+    if sampler == "dynamic":
+        raise ValueError(f"{who}: dynamic negatives run fused in StreamTrainer(sampler='dynamic') (plain SGD); with "
+                         "another optimizer draw them per batch with revisit_bpr.modules.DynamicSampler and step on "
+                         "the picks as given negatives")
+
+
 class StrictTrainer:
     """Epochs of the reference's exact mini-batch loop (sample → model(batch) → backward →
     optimizer.step()) inside the library, for every optimizer the engine mirrors (SGD, momentum /
@@ -591,6 +611,7 @@ class StrictTrainer:
         self.users, self.items = users.contiguous(), items.contiguous()
         self.n = users.numel()
         model.bind_seen_csr(seen_indptr, seen_indices)
+        _refuse_dynamic(sampler, type(self).__name__)
         self.sampler = {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM}[sampler]
         self.adaptive_p, self.batch = adaptive_p, batch_size
         I = self.engine.I
@@ -672,6 +693,7 @@ class BatchedStreamTrainer:
         self.users, self.items = users.contiguous(), items.contiguous()
         self.n = users.numel()
         model.bind_seen_csr(seen_indptr, seen_indices)
+        _refuse_dynamic(sampler, type(self).__name__)
         self.sampler = {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM}[sampler]
         self.adaptive_p, self.batch = adaptive_p, batch_size
         I, U = self.engine.I, self.engine.U

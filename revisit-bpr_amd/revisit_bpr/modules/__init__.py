@@ -1,3 +1,3 @@
-from revisit_bpr.modules.neg_samplers import AdaptiveSampler, Sampler, UniformSampler
+from revisit_bpr.modules.neg_samplers import AdaptiveSampler, DynamicSampler, Sampler, UniformSampler
 
-__all__ = ["Sampler", "UniformSampler", "AdaptiveSampler"]
+__all__ = ["Sampler", "UniformSampler", "AdaptiveSampler", "DynamicSampler"]

@@ -178,3 +178,43 @@ class AdaptiveSampler(Sampler):
         model = self._bpr()
         model.sync()  # lazy dense-optimizer replay: the snapshot must see current item rows
         model.engine().adaptive_refresh()
+
+
+class DynamicSampler(Sampler):
+    """Dynamic negative sampling (extension; Zhang et al., SIGIR 2013): `num_candidates` unseen items are drawn
+    uniformly, scored with the model as it is BEFORE the step, and the highest-scoring one is the negative
+    (``bpr_sample_dynamic``; num_candidates = 1 is the uniform sampler).  The picks are ordinary given negatives for
+    the step that follows, so any optimizer works.  One negative per row."""
+
+    def __init__(self, model, num_items: int, num_candidates: int = 4, seed: int = 13,
+                 neg_gen: Optional[torch.Generator] = None) -> None:
+        if not 1 <= int(num_candidates) <= 32:
+            raise ValueError("num_candidates must be in [1, 32]")
+        self._model = model
+        self._num_items = num_items
+        self._num_candidates = int(num_candidates)
+        self._seed = int(seed if neg_gen is None else neg_gen.initial_seed())
+        self._drawn = 0
+
+    def _bpr(self):
+        model = self._model
+        while hasattr(model, "module") and not hasattr(model, "logits_model"):
+            model = model.module  # DDP / accelerate wrappers
+        return model
+
+    def sample(self, batch: dict[str, torch.Tensor]) -> torch.Tensor:
+        if _num(batch) != 1:
+            raise ValueError("DynamicSampler draws one negative per row")
+        model = self._bpr()
+        eng = model.engine()
+        users = batch["user"].reshape(-1)
+        if not getattr(model, "_has_csr", False):
+            indptr, indices = csr_from_padded(users, batch["seen_items"], eng.U)
+            eng.bind_seen_csr(indptr, indices)
+        model.sync()  # lazy dense-optimizer replay: the candidates are scored on current rows
+        neg = eng.sample_dynamic(users, self._num_candidates, seed=self._seed, offset=self._drawn)
+        self._drawn += users.numel()
+        return neg.to(torch.long).unsqueeze(-1)
+
+    def update_stats(self) -> None:
+        """Nothing to refresh: the candidates are scored on the live tables."""

@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("BPR_LIB_PATH") or
 OK = 0
 OPT_SGD, OPT_MOMENTUM, OPT_ADAM, OPT_RMSPROP = 0, 1, 2, 3
 MODE_STRICT, MODE_STREAM = 0, 1
-NEG_GIVEN, NEG_UNIFORM, NEG_ADAPTIVE = 0, 1, 2
+NEG_GIVEN, NEG_UNIFORM, NEG_ADAPTIVE, NEG_DYNAMIC = 0, 1, 2, 3
 SCALARS = 4
 SIM_DOT, SIM_COSINE = 0, 1  # BPR_SIM_DOT, BPR_SIM_COSINE
 REFRESH_INFO_LEN = 8  # BPR_REFRESH_INFO_LEN: int32 entries bpr_adaptive_refresh_info fills
@@ -65,6 +65,8 @@ SIGNATURES = {
     "bpr_set_optimizer": (c_int, [c_void_p, c_int32, POINTER(OptParams)]),
     "bpr_bind_opt_state": (c_int, [c_void_p] + [c_void_p] * 6),
     "bpr_sample_uniform": (c_int, [c_void_p, c_void_p, c_int64, c_uint64, c_uint64, c_void_p]),
+    "bpr_set_dynamic": (c_int, [c_void_p, c_int32]),
+    "bpr_sample_dynamic": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_uint64, c_uint64, c_void_p, c_void_p]),
     "bpr_adaptive_refresh": (c_int, [c_void_p]),
     "bpr_adaptive_refresh_info": (c_int, [c_void_p, POINTER(c_int32)]),
     "bpr_adaptive_refresh_begin": (c_int, [c_void_p]),
