@@ -49,7 +49,15 @@ typedef enum bpr_opt_kind {
   BPR_OPT_SGD = 0,      /* torch.optim.SGD(lr)                               */
   BPR_OPT_MOMENTUM = 1, /* torch.optim.SGD(lr, momentum, dampening, nesterov) */
   BPR_OPT_ADAM = 2,     /* torch.optim.Adam(lr, betas, eps)                   */
-  BPR_OPT_RMSPROP = 3   /* torch.optim.RMSprop(lr, alpha, eps, momentum)      */
+  BPR_OPT_RMSPROP = 3,  /* torch.optim.RMSprop(lr, alpha, eps, momentum)      */
+  /* Extension (not in the reference configs): sum += g * g; w -= clr * g / (sqrt(sum) + eps) in fp32 with correctly
+   * rounded sqrt and divide, clr = lr / (1 + (t - 1) * lr_decay) in double, rounded once per step.  A zero gradient
+   * moves neither the row nor its sum, so a dense torch.optim.Adagrad IS the row-sparse update: nothing is replayed
+   * and bpr_flush_lazy / bpr_flush_items have nothing to do for it on the STRICT path.  Runs on STRICT (bpr_step,
+   * bpr_apply, bpr_train_strict) and on bpr_train_stream_batched.  bpr_train_stream and its cut variants — the fused
+   * k_stream, its LDS tier and the hot block — stay plain SGD and return BPR_ERR_UNSUPPORTED for this kind before
+   * the device is touched: these fold linear deltas.  Adagrad's step is not linear. */
+  BPR_OPT_ADAGRAD = 4   /* torch.optim.Adagrad(lr, lr_decay, eps) */
 } bpr_opt_kind;
 
 typedef struct bpr_opt_params {
@@ -58,8 +66,9 @@ typedef struct bpr_opt_params {
   float dampening; /* MOMENTUM */
   int32_t nesterov;
   float beta1, beta2; /* ADAM */
-  float eps;          /* ADAM (1e-8), RMSPROP (1e-8) */
+  float eps;          /* ADAM (1e-8), RMSPROP (1e-8), ADAGRAD (torch's default: 1e-10) */
   float alpha;        /* RMSPROP smoothing constant (0.99) */
+  float lr_decay;     /* ADAGRAD (0 = no decay); must be 0 for every other kind */
 } bpr_opt_params;
 
 /* How a step treats rows that occur several times in the same batch / chunk. */
@@ -70,8 +79,8 @@ typedef enum bpr_mode {
   BPR_MODE_STRICT = 0,
   /* Throughput path: one launch consumes a whole chunk of triples; every triple reads the latest
    * rows it can see and applies its update immediately with per-element fp32 atomics
-   * (asynchronous SGD, bounded staleness).  SGD only; the other optimizers have their own
-   * single-launch path, bpr_train_stream_batched. */
+   * (asynchronous SGD, bounded staleness).  SGD only; the other optimizers (BPR_OPT_ADAGRAD included) have their
+   * own single-launch path, bpr_train_stream_batched. */
   BPR_MODE_STREAM = 1
 } bpr_mode;
 
@@ -117,12 +126,15 @@ int bpr_bind_seen_csr(bpr_ctx* ctx, const int64_t* indptr, const int32_t* indice
 /* Model.regularization alphas after the resolution rules of model.py:74-86 were applied by the host. */
 int bpr_set_reg(bpr_ctx* ctx, float alpha_user, float alpha_item, float alpha_neg);
 
-/* torch.optim hyper-parameters (read from optimizer.param_groups by the host shim each step). */
+/* torch.optim hyper-parameters (read from optimizer.param_groups by the host shim each step).  The kind and its
+ * hyper-parameters are checked before the ctx is looked at: an unknown kind, a momentum outside [0, 1), lr_decay < 0
+ * (or NaN) and a non-zero lr_decay with any kind but BPR_OPT_ADAGRAD are BPR_ERR_INVALID. */
 int bpr_set_optimizer(bpr_ctx* ctx, int32_t kind, const bpr_opt_params* params);
 /* Optimizer state, same shapes as the tables (caller-owned so checkpoints keep working):
  *   MOMENTUM: m_* = momentum_buffer;  ADAM: m_* = exp_avg, v_* = exp_avg_sq;  RMSPROP: v_* = square_avg
- *   (+ m_* = momentum_buffer when momentum > 0).
- * *_bias may be NULL when there is no item_bias.  All zero-initialised by the caller. */
+ *   (+ m_* = momentum_buffer when momentum > 0);  ADAGRAD: v_* = sum (m_* may be NULL: never read or written).
+ * *_bias may be NULL when there is no item_bias.  All zero-initialised by the caller — except Adagrad's sum, which
+ * the caller fills with torch's initial_accumulator_value (0 by default): the library only ever adds to it. */
 int bpr_bind_opt_state(bpr_ctx* ctx, float* m_P, float* v_P, float* m_Q, float* v_Q,
                        float* m_bias, float* v_bias);
 
@@ -377,7 +389,7 @@ int bpr_train_stream_acut(bpr_ctx* ctx, const int32_t* users, const int32_t* pos
 int bpr_hot_fold(bpr_ctx* ctx);
 
 /* BATCHED STREAM — the single-launch throughput path for every optimizer kind (SGD, momentum /
- * Nesterov, Adam, RMSprop; configs/RQ3/time-split/ada-sampling-adam.yaml.j2:169-175 and 14 of the
+ * Nesterov, Adam, RMSprop, Adagrad; configs/RQ3/time-split/ada-sampling-adam.yaml.j2:169-175 and 14 of the
  * 22 BPR configs step torch.optim.Adam at experiments/trainer.py:79-81).  users/pos [n] are the
  * shuffled triple stream (bpr_shuffle_epoch; NOT grouped by user); triple k belongs to virtual
  * mini-batch k / B, i.e. optimizer step (steps so far) + 1 + k / B.  Per row the gradients of one

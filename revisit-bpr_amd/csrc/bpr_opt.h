@@ -1,13 +1,14 @@
-// bpr_opt.h — torch.optim update rules on registers (SGD / momentum / Adam / RMSprop) and the lazy
-// replay of the zero-gradient steps a DENSE torch optimizer applies to rows nobody touched
-// (SURVEY H2).  Shared by the STRICT kernels (bpr_kernels.h) and the batched STREAM kernels
+// bpr_opt.h — torch.optim update rules on registers (SGD / momentum / Adam / RMSprop / Adagrad) and
+// the lazy replay of the zero-gradient steps a DENSE torch optimizer applies to rows nobody touched
+// (SURVEY H2).  Adagrad has no such steps: sum + 0 * 0 and w - clr * 0 / (sqrt(sum) + eps) leave the
+// row as it is, so its dense semantics ARE the row-sparse ones and every replay returns at once.  Shared by the STRICT kernels (bpr_kernels.h) and the batched STREAM kernels
 // (bpr_vstream.h).  Pinned through the oracle to the reference's torch.optim trajectories.
 #pragma once
 #include "bpr_device.h"
 
 namespace bpr {
 
-enum { OPT_SGD = 0, OPT_MOMENTUM = 1, OPT_ADAM = 2, OPT_RMSPROP = 3 };
+enum { OPT_SGD = 0, OPT_MOMENTUM = 1, OPT_ADAM = 2, OPT_RMSPROP = 3, OPT_ADAGRAD = 4 };
 
 constexpr int ADAM_SERIES = 12;
 
@@ -23,7 +24,9 @@ struct OptDev {
   // (-1 = never / disabled); G = the geometric series of the eps expansion, for kk = kmax
   int64_t t_sat;
   float G[ADAM_SERIES];  // G(z_j) = z_j (1 - z_j^kmax) / (1 - z_j), z_j = b1 / b2^((j+1)/2)
-  float adam_step, adam_bc2;  // lr / (1 - b1^t), sqrt(1 - b2^t) of the step being applied (host)
+  // lr / (1 - b1^t), sqrt(1 - b2^t) of the step being applied (host).  Adagrad: adam_step carries
+  // clr = lr / (1 + (t - 1) lr_decay) of that step (bpr_opt_plan.h: adagrad_clr), adam_bc2 = 1
+  float adam_step, adam_bc2;
   float sv_min;          // closed form needs sqrt(v) >= eps * r^-kmax / 0.2 (series argument)
   float log2_z[ADAM_SERIES], zc[ADAM_SERIES];  // log2(z_j), z_j / (1 - z_j): G_j(k) for k < kmax
 };
@@ -31,7 +34,7 @@ struct OptDev {
 // zero-gradient steps s0+1 … s0+k applied to one element
 __device__ __forceinline__ void opt_replay(float& w, float& m, float& v, int64_t s0, int64_t k,
                                            const OptDev& o) {
-  if (k <= 0) return;
+  if (k <= 0 || o.kind == OPT_ADAGRAD) return;  // (Adagrad: a zero-gradient step moves nothing)
   if (o.kind == OPT_MOMENTUM) {
     const float muk = (float)exp((double)k * o.log_mu);
     const float c = o.nesterov ? o.mu : 1.0f;
@@ -72,7 +75,7 @@ __device__ __forceinline__ void opt_replay(float& w, float& m, float& v, int64_t
 template <int E, bool STATE = true>
 __device__ __forceinline__ void opt_replay_row(float (&w)[E], float (&m)[E], float (&v)[E],
                                                int64_t s0, int64_t k, const OptDev& o) {
-  if (k <= 0) return;
+  if (k <= 0 || o.kind == OPT_ADAGRAD) return;
   if (o.kind == OPT_MOMENTUM) {
     const float muk = (float)exp((double)k * o.log_mu);
     const float c = o.nesterov ? o.mu : 1.0f;
@@ -197,6 +200,13 @@ __device__ __forceinline__ void opt_update_at(float& w, float g, float& m, float
     v = o.b2 * v + (1.0f - o.b2) * g * g;
     const float denom = sqrtf(v) / adam_bc2_sqrt + o.eps;
     w = w - adam_step * (m / denom);
+  } else if (o.kind == OPT_ADAGRAD) {
+    // torch: state_sum.addcmul_(grad, grad); std = state_sum.sqrt().add_(eps);
+    // param.addcdiv_(grad, std, value=-clr) — correctly rounded sqrt and divide, clr in adam_step;
+    // the accumulator lives in v, m is not touched
+    v = v + g * g;
+    const float std_ = sqrtf(v) + o.eps;
+    w = w - adam_step * (g / std_);
   } else {
     v = o.alpha * v + (1.0f - o.alpha) * g * g;
     const float avg = sqrtf(v) + o.eps;
@@ -238,7 +248,7 @@ template <int G, int E>
 __device__ __forceinline__ void catch_up_row(float (&r)[E], const float* __restrict__ M,
                                              const float* __restrict__ V, int64_t row, int d,
                                              int gl, int64_t s0, int64_t k, const OptDev& o) {
-  if (k <= 0) return;
+  if (k <= 0 || o.kind == OPT_ADAGRAD) return;  // before the loads of M / V
   float m[E], v[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) {

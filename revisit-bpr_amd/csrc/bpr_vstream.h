@@ -1,5 +1,5 @@
 // bpr_vstream.h — BATCHED STREAM: the single-launch throughput path for EVERY torch.optim kind the
-// reference configs use (SGD, SGD-momentum / Nesterov, Adam, RMSprop), gfx950.
+// reference configs use (SGD, SGD-momentum / Nesterov, Adam, RMSprop) and for Adagrad, gfx950.
 //
 // The reference steps once per mini-batch of B triples: all B gradients are evaluated at the
 // pre-step parameters, duplicates are summed, and a DENSE optimizer then moves every row
@@ -145,7 +145,15 @@ struct VOpt {
   float zc[VADAM_SERIES], log2_z[VADAM_SERIES];  // z_j / (1 - z_j), log2 z_j   (zc[0] < 0: off)
   float sv_min;                                  // sqrt v >= eps r^-kmax / 0.02
   int32_t closed_min;                            // gaps of at least this many steps take the closed form
+  float lr_decay;                                // Adagrad: clr_t = lr / (1 + (t - 1) lr_decay)
 };
+
+// kinds whose state includes the first-moment / momentum table M (Adagrad keeps only its sum, in V), and kinds whose
+// dense zero-gradient step moves a row (Adagrad's does not: nothing to replay, nothing to bring to "now")
+template <int KIND>
+inline constexpr bool VO_HAS_M = KIND != OPT_SGD && KIND != OPT_ADAGRAD;
+template <int KIND>
+inline constexpr bool VO_REPLAYS = KIND != OPT_SGD && KIND != OPT_ADAGRAD;
 
 template <int KIND>
 __device__ __forceinline__ void vo_step_consts(const VOpt& o, int64_t t, float& step, float& ibc2) {
@@ -157,6 +165,11 @@ __device__ __forceinline__ void vo_step_consts(const VOpt& o, int64_t t, float& 
       step = o.lr / (-expm1f(tf * o.ln_b1));
       ibc2 = 1.0f / sqrtf(-expm1f(tf * o.ln_b2));
     }
+  }
+  if constexpr (KIND == OPT_ADAGRAD) {
+    // torch's clr of step t: in double, rounded to float once (as bpr_opt_plan.h: adagrad_clr)
+    if (o.lr_decay != 0.f)
+      step = (float)((double)o.lr / (1.0 + (double)(t - 1) * (double)o.lr_decay));
   }
 }
 
@@ -179,6 +192,12 @@ __device__ __forceinline__ void vo_update(float& w, float g, float& m, float& v,
     // element and this kernel is bound by VALU issue (profiles/r02_sq_counters_vstream.txt)
     const float denom = __builtin_amdgcn_sqrtf(v) * adam_ibc2 + o.eps;
     w = w - adam_step * (m * __builtin_amdgcn_rcpf(denom));
+  } else if constexpr (KIND == OPT_ADAGRAD) {
+    // torch's three lines with the correctly rounded sqrt and divide (the bits are the contract:
+    // the sequential limit is held to the same model as the STRICT kernels); adam_step = clr_t
+    v = v + g * g;
+    const float std_ = sqrtf(v) + o.eps;
+    w = w - adam_step * (g / std_);
   } else {
     v = o.alpha * v + (1.0f - o.alpha) * g * g;
     const float iavg = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) + o.eps);
@@ -350,17 +369,21 @@ __device__ __forceinline__ uint64_t vs_view(float (&w)[E], float& wb, const VTab
         load_row_sc1<G, E>(w, T.W + off, d, gl);
 #pragma unroll
         for (int e = 0; e < E; ++e) m[e] = v[e] = g[e] = 0.f;
+        // Adagrad: no replay reads the state — the sum is wanted only to apply a pending step in this view
+        const bool want_state = KIND != OPT_ADAGRAD || (h.gstep() > h.last() && h.gstep() < t);
         if constexpr (STATEFUL) {
-          if (T.M != nullptr) load_row_sc1<G, E>(m, T.M + off, d, gl);
-          if (T.V != nullptr) load_row_sc1<G, E>(v, T.V + off, d, gl);
+          if constexpr (VO_HAS_M<KIND>)
+            if (T.M != nullptr) load_row_sc1<G, E>(m, T.M + off, d, gl);
+          if (want_state && T.V != nullptr) load_row_sc1<G, E>(v, T.V + off, d, gl);
         }
         bm = bv = gb = 0.f;
         wb = 0.f;
         if (T.b != nullptr) {
           wb = ld_sc1(T.b + row);
           if constexpr (STATEFUL) {
-            if (T.mb != nullptr) bm = ld_sc1(T.mb + row);
-            if (T.vb != nullptr) bv = ld_sc1(T.vb + row);
+            if constexpr (VO_HAS_M<KIND>)
+              if (T.mb != nullptr) bm = ld_sc1(T.mb + row);
+            if (want_state && T.vb != nullptr) bv = ld_sc1(T.vb + row);
           }
         }
         pend = h.gstep() > h.last() && h.gstep() < t;  // a closed step nobody has applied yet
@@ -385,7 +408,7 @@ __device__ __forceinline__ uint64_t vs_view(float (&w)[E], float& wb, const VTab
 #pragma unroll 1
   for (int ph = pend ? 0 : 1; ph < 2; ++ph) {
     const int64_t k = ph == 0 ? gs - 1 - a : (t - 1) - a;
-    if constexpr (STATEFUL) {
+    if constexpr (VO_REPLAYS<KIND>) {
       vo_replay<KIND, E, true>(w, m, v, a, k, o);
       if (T.b != nullptr) vo_replay1<KIND, true>(wb, bm, bv, a, k, o);
     }
@@ -484,7 +507,8 @@ __device__ __forceinline__ void vs_contribute(const VTable& T, uint32_t row, int
             }
             load_row_sc1<G, E>(w, T.W + off, d, gl);
             if constexpr (STATEFUL) {
-              if (T.M != nullptr) load_row_sc1<G, E>(m, T.M + off, d, gl);
+              if constexpr (VO_HAS_M<KIND>)
+                if (T.M != nullptr) load_row_sc1<G, E>(m, T.M + off, d, gl);
               if (T.V != nullptr) load_row_sc1<G, E>(v, T.V + off, d, gl);
             }
             float wb = 0.f, bm = 0.f, bv = 0.f;
@@ -492,7 +516,8 @@ __device__ __forceinline__ void vs_contribute(const VTable& T, uint32_t row, int
             if (bias) {
               wb = ld_sc1(T.b + row);
               if constexpr (STATEFUL) {
-                if (T.mb != nullptr) bm = ld_sc1(T.mb + row);
+                if constexpr (VO_HAS_M<KIND>)
+                  if (T.mb != nullptr) bm = ld_sc1(T.mb + row);
                 if (T.vb != nullptr) bv = ld_sc1(T.vb + row);
               }
               if (close) gbo = xchg_zero(T.Gb + (size_t)h.slot() * (size_t)T.rows + row);
@@ -511,13 +536,15 @@ __device__ __forceinline__ void vs_contribute(const VTable& T, uint32_t row, int
             }
             store_row_sc1<G, E>(T.W + off, w, d, gl);
             if constexpr (STATEFUL) {
-              if (T.M != nullptr) store_row_sc1<G, E>(T.M + off, m, d, gl);
+              if constexpr (VO_HAS_M<KIND>)
+                if (T.M != nullptr) store_row_sc1<G, E>(T.M + off, m, d, gl);
               if (T.V != nullptr) store_row_sc1<G, E>(T.V + off, v, d, gl);
             }
             if (bias) {
               st_sc1(T.b + row, wb);
               if constexpr (STATEFUL) {
-                if (T.mb != nullptr) st_sc1(T.mb + row, bm);
+                if constexpr (VO_HAS_M<KIND>)
+                  if (T.mb != nullptr) st_sc1(T.mb + row, bm);
                 if (T.vb != nullptr) st_sc1(T.vb + row, bv);
               }
             }
@@ -760,21 +787,23 @@ __global__ __launch_bounds__(256) void k_vflush(const VFlushArgs a) {
     const VHdr h{T.H[row]};
     const int64_t a0 = h.last(), gs = h.gstep();
     const bool pending = gs > a0;
-    if (!pending && (!STATEFUL || a0 >= a.now)) continue;
+    if (!pending && (!VO_REPLAYS<KIND> || a0 >= a.now)) continue;  // (SGD, Adagrad: only pending steps)
     const size_t off = (size_t)row * (size_t)d;
     float w[E], m[E], v[E];
     load_row<G, E>(w, T.W + off, d, gl);
 #pragma unroll
     for (int e = 0; e < E; ++e) m[e] = v[e] = 0.f;
     if constexpr (STATEFUL) {
-      if (T.M != nullptr) load_row<G, E>(m, T.M + off, d, gl);
+      if constexpr (VO_HAS_M<KIND>)
+        if (T.M != nullptr) load_row<G, E>(m, T.M + off, d, gl);
       if (T.V != nullptr) load_row<G, E>(v, T.V + off, d, gl);
     }
     float wb = 0.f, bm = 0.f, bv = 0.f;
     if (T.b != nullptr) {
       wb = T.b[row];
       if constexpr (STATEFUL) {
-        if (T.mb != nullptr) bm = T.mb[row];
+        if constexpr (VO_HAS_M<KIND>)
+          if (T.mb != nullptr) bm = T.mb[row];
         if (T.vb != nullptr) bv = T.vb[row];
       }
     }
@@ -804,20 +833,22 @@ __global__ __launch_bounds__(256) void k_vflush(const VFlushArgs a) {
       }
       cur = gs;
     }
-    if constexpr (STATEFUL) {
+    if constexpr (VO_REPLAYS<KIND>) {
       vo_replay<KIND, E, true>(w, m, v, cur, a.now - cur, a.o);
       if (T.b != nullptr) vo_replay1<KIND, true>(wb, bm, bv, cur, a.now - cur, a.o);
     }
     store_row<G, E>(T.W + off, w, d, gl);
     if constexpr (STATEFUL) {
-      if (T.M != nullptr) store_row<G, E>(T.M + off, m, d, gl);
+      if constexpr (VO_HAS_M<KIND>)
+        if (T.M != nullptr) store_row<G, E>(T.M + off, m, d, gl);
       if (T.V != nullptr) store_row<G, E>(T.V + off, v, d, gl);
     }
     if (gl == 0) {
       if (T.b != nullptr) {
         T.b[row] = wb;
         if constexpr (STATEFUL) {
-          if (T.mb != nullptr) T.mb[row] = bm;
+          if constexpr (VO_HAS_M<KIND>)
+            if (T.mb != nullptr) T.mb[row] = bm;
           if (T.vb != nullptr) T.vb[row] = bv;
         }
       }

@@ -36,6 +36,7 @@ static VOpt vopt(const bpr_ctx* c) {
   const bpr_opt_params& p = c->opt;
   o.lr = p.lr; o.mu = p.momentum; o.damp = p.dampening; o.nesterov = p.nesterov;
   o.b1 = p.beta1; o.b2 = p.beta2; o.eps = p.eps; o.alpha = p.alpha;
+  o.lr_decay = p.lr_decay;
   auto ln = [](double x) { return x > 0.0 ? log(x) : -1.0e30; };
   auto l2 = [](double x) { return x > 0.0 ? log2(x) : -1.0e30; };
   o.ln_b1 = (float)ln(p.beta1); o.ln_b2 = (float)ln(p.beta2);
@@ -141,6 +142,9 @@ int vs_flush(bpr_ctx* c, bool users, bool items) {
         case BPR_OPT_ADAM:
           hipLaunchKernelGGL((k_vflush<G, E, OPT_ADAM>), dim3(grid), dim3(256), 0, c->stream, a);
           break;
+        case BPR_OPT_ADAGRAD:  // (pending gradient steps only: Adagrad has nothing to replay)
+          hipLaunchKernelGGL((k_vflush<G, E, OPT_ADAGRAD>), dim3(grid), dim3(256), 0, c->stream, a);
+          break;
         default:
           hipLaunchKernelGGL((k_vflush<G, E, OPT_RMSPROP>), dim3(grid), dim3(256), 0, c->stream, a);
       }
@@ -220,6 +224,7 @@ static int launch_vstream(bpr_ctx* c, VStreamArgs a, int sampler, int64_t cap_gr
           case BPR_OPT_SGD: go(smp, integral_constant<int, OPT_SGD>{}); break;
           case BPR_OPT_MOMENTUM: go(smp, integral_constant<int, OPT_MOMENTUM>{}); break;
           case BPR_OPT_ADAM: go(smp, integral_constant<int, OPT_ADAM>{}); break;
+          case BPR_OPT_ADAGRAD: go(smp, integral_constant<int, OPT_ADAGRAD>{}); break;
           default: go(smp, integral_constant<int, OPT_RMSPROP>{});
         }
       };

@@ -13,6 +13,7 @@
 #include "bpr_stream_plan.h"
 #include "bpr_refresh_plan.h"
 #include "bpr_dynamic_plan.h"
+#include "bpr_opt_plan.h"
 
 namespace bpr {
 static_assert(ORDER_PAD == BPR_ORDER_PAD, "walk vector width vs snapshot padding");
@@ -162,7 +163,10 @@ static TripleArgs triple_args(const bpr_ctx* c) {
   a.partials = c->dev_scalars;
   a.acc_partials = c->defer_stats ? 1 : 0;
   a.mP = c->mP; a.vP = c->vP; a.mQ = c->mQ; a.vQ = c->vQ; a.mb = c->mb; a.vb = c->vb;
-  a.lastP = c->lastP; a.lastQ = c->lastQ;
+  // (Adagrad: no zero-gradient motion to read rows through — the kernel skips the block, as for SGD)
+  if (opt_kind_lazy(c->opt_kind)) {
+    a.lastP = c->lastP; a.lastQ = c->lastQ;
+  }
   a.o = opt_dev(c, c->step + 1);
   return a;
 }
@@ -189,6 +193,7 @@ OptDev opt_dev(const bpr_ctx* c, int64_t t) {
     o.adam_step = (float)((double)o.lr / (1.0 - exp((double)t * o.log_b1)));
     o.adam_bc2 = (float)sqrt(1.0 - exp((double)t * o.log_b2));
   }
+  if (o.kind == OPT_ADAGRAD) o.adam_step = adagrad_clr(c->opt.lr, c->opt.lr_decay, t);  // the step's clr
   if (o.kind == OPT_ADAM && o.b1 > 0.f) {
     const double ratio = (double)o.b1 / sqrt((double)o.b2);
     o.kmax = ratio < 1.0 ? (int)ceil(log(1e-8) / log(ratio)) : 1 << 20;
@@ -231,7 +236,8 @@ static ApplyArgs apply_args(const bpr_ctx* c, int64_t t) {
 int check_opt_state(const bpr_ctx* c, const char* who) {
   const bool need_m = c->opt_kind == BPR_OPT_MOMENTUM || c->opt_kind == BPR_OPT_ADAM ||
                       (c->opt_kind == BPR_OPT_RMSPROP && c->opt.momentum > 0.f);
-  const bool need_v = c->opt_kind == BPR_OPT_ADAM || c->opt_kind == BPR_OPT_RMSPROP;
+  const bool need_v = c->opt_kind == BPR_OPT_ADAM || c->opt_kind == BPR_OPT_RMSPROP ||
+                      c->opt_kind == BPR_OPT_ADAGRAD;  // (Adagrad: v = sum, no m)
   if ((need_m && (!c->mP || !c->mQ || (c->bias && !c->mb))) ||
       (need_v && (!c->vP || !c->vQ || (c->bias && !c->vb))))
     return fail(BPR_ERR_INVALID,
@@ -557,7 +563,8 @@ int check_sampler(const bpr_ctx* c, const char* who, int32_t sampler, float adap
 
 // STRICT lazy replay: bring every row to step c->step (rows tracked by lastP / lastQ)
 int strict_flush_impl(bpr_ctx* c) {
-  if (c->opt_kind == BPR_OPT_SGD || c->GP == nullptr || c->step == 0) return BPR_OK;
+  // SGD and Adagrad: a dense zero-gradient step moves nothing — no kernel
+  if (!opt_kind_lazy(c->opt_kind) || c->GP == nullptr || c->step == 0) return BPR_OK;
   c->bias_w_valid = false;
   if (int rc = check_opt_state(c, "bpr_flush_lazy")) return rc;
   // (accumulated gradients of a batch in flight are left alone: the flush only advances w / m / v
@@ -688,13 +695,9 @@ int bpr_set_reg(bpr_ctx* c, float alpha_user, float alpha_item, float alpha_neg)
 }
 
 int bpr_set_optimizer(bpr_ctx* c, int32_t kind, const bpr_opt_params* params) {
-  if (c == nullptr || params == nullptr)
-    return fail(BPR_ERR_INVALID, "bpr_set_optimizer: NULL argument");
-  if (kind < BPR_OPT_SGD || kind > BPR_OPT_RMSPROP)
-    return fail(BPR_ERR_INVALID, "bpr_set_optimizer: unknown optimizer kind");
-  if ((kind == BPR_OPT_MOMENTUM || kind == BPR_OPT_RMSPROP) &&
-      !(params->momentum >= 0.f && params->momentum < 1.f))
-    return fail(BPR_ERR_INVALID, "bpr_set_optimizer: momentum must be in [0, 1)");
+  // the kind and its hyper-parameters first (bpr_opt_plan.h): a refusal of those needs no ctx
+  if (const char* msg = opt_params_error(kind, params)) return fail(BPR_ERR_INVALID, msg);
+  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_set_optimizer: ctx is NULL");
   if (c->vs_active && (kind != c->opt_kind || memcmp(&c->opt, params, sizeof(*params)) != 0)) {
     // batched STREAM: pending steps and the replay of missed ones use the hyper-parameters in
     // force when they were taken — bring every row to "now" before those change
@@ -774,7 +777,7 @@ static SampleArgs sample_args(const bpr_ctx* c) {
   a.indptr = c->indptr; a.indices = c->indices;
   a.order = c->order; a.sigma = c->sigma;
   a.iw = ItemWeights{c->w_accept, c->w_alias};
-  a.mP = c->mP; a.vP = c->vP; a.lastP = c->lastP;
+  a.mP = c->mP; a.vP = c->vP; a.lastP = opt_kind_lazy(c->opt_kind) ? c->lastP : nullptr;
   a.o = opt_dev(c, c->step + 1);
   return a;
 }
@@ -1049,8 +1052,8 @@ static int train_stream_impl(bpr_ctx* c, const int32_t* users, const int32_t* po
   if (int rc = check_sampler(c, "bpr_train_stream", sampler, adaptive_p, neg, n)) return rc;
   if (c->opt_kind != BPR_OPT_SGD)
     return fail(BPR_ERR_UNSUPPORTED,
-                "bpr_train_stream: this launch implements plain SGD only; momentum / Adam / RMSprop "
-                "run through bpr_train_stream_batched (one launch per refresh period) or STRICT "
+                "bpr_train_stream: this launch implements plain SGD only; momentum / Adam / RMSprop / "
+                "Adagrad run through bpr_train_stream_batched (one launch per refresh period) or STRICT "
                 "(bpr_forward_grad + bpr_apply)");
   if (c->pending != 0)
     return fail(BPR_ERR_INVALID, "bpr_train_stream: unapplied STRICT gradients pending");
@@ -1508,7 +1511,7 @@ int bpr_flush_items(bpr_ctx* c) {
   c->bias_w_valid = false;
   BPR_HIP_CHECK(hipSetDevice(c->device));
   if (c->vs_active) return vs_flush(c, false, true);
-  if (c->opt_kind == BPR_OPT_SGD || c->GP == nullptr || c->step == 0) return BPR_OK;
+  if (!opt_kind_lazy(c->opt_kind) || c->GP == nullptr || c->step == 0) return BPR_OK;
   if (int rc = check_opt_state(c, "bpr_flush_items")) return rc;
   ApplyArgs a = apply_args(c, c->step);
   return dispatch_ge(c->G, c->E, [&](auto tag) -> int {

@@ -85,7 +85,7 @@ def strict_epoch(model, optimizer, sampler, users, items, seen_pad, batch_size, 
               help="stream: fused SGD launches (StreamTrainer); batched: one launch per refresh period with "
                    "virtual mini-batches, any --optimizer (BatchedStreamTrainer); strict: the reference's "
                    "batch loop")
-@click.option("--optimizer", "opt_name", type=click.Choice(["sgd", "adam", "rmsprop", "nesterov"]),
+@click.option("--optimizer", "opt_name", type=click.Choice(["sgd", "adam", "rmsprop", "nesterov", "adagrad"]),
               default="sgd", show_default=True, help="batched / strict modes (stream is plain SGD)")
 @click.option("--refresh-lag", type=float, default=0.0, show_default=True,
               help="stream mode: 1 = the adaptive snapshot is sorted beside the previous launch "
@@ -134,6 +134,7 @@ def main(dataset_path, synthetic_name, num_users, num_items, embedding_dim, batc
         return {"sgd": lambda: torch.optim.SGD(p, lr=lr),
                 "adam": lambda: torch.optim.Adam(p, lr=lr, betas=(0.1, 0.999)),  # ada-sampling-adam.yaml.j2:175
                 "rmsprop": lambda: torch.optim.RMSprop(p, lr=lr, alpha=0.9),
+                "adagrad": lambda: torch.optim.Adagrad(p, lr=lr),  # (extension: not in the reference configs)
                 "nesterov": lambda: torch.optim.SGD(p, lr=lr, momentum=0.9, nesterov=True)}[opt_name]()
 
     if mode == "stream" and opt_name != "sgd":

@@ -13,10 +13,10 @@ import torch
 
 from revisit_bpr import native
 from revisit_bpr.native import (MODE_STREAM, MODE_STRICT, NEG_ADAPTIVE, NEG_DYNAMIC, NEG_GIVEN, NEG_UNIFORM,
-                                OPT_ADAM, OPT_MOMENTUM, OPT_RMSPROP, OPT_SGD)
+                                OPT_ADAGRAD, OPT_ADAM, OPT_MOMENTUM, OPT_RMSPROP, OPT_SGD)
 
 __all__ = ["Engine", "MaskedStream", "cu_mask", "resolve_reg_alphas", "MODE_STREAM", "MODE_STRICT", "NEG_ADAPTIVE",
-           "NEG_DYNAMIC", "NEG_GIVEN", "NEG_UNIFORM", "OPT_ADAM", "OPT_MOMENTUM", "OPT_RMSPROP", "OPT_SGD"]
+           "NEG_DYNAMIC", "NEG_GIVEN", "NEG_UNIFORM", "OPT_ADAGRAD", "OPT_ADAM", "OPT_MOMENTUM", "OPT_RMSPROP", "OPT_SGD"]
 
 
 def resolve_reg_alphas(reg_alphas: Optional[dict]) -> tuple[float, float, float]:
@@ -357,6 +357,7 @@ class Engine:
         age: the kernel cannot tell a stale order from a fresh one."""
         from revisit_bpr import foldin
 
+        self._refuse_foldin_adagrad("fold_in", "revisit_bpr.foldin.fold_in")
         if lr is None:
             lr = getattr(self, "_lr", None)
             if lr is None:
@@ -391,6 +392,7 @@ class Engine:
         asynchronous cut left is folded and rows a lazy optimizer has not replayed yet are flushed."""
         from revisit_bpr import foldin_items
 
+        self._refuse_foldin_adagrad("fold_in_items", "revisit_bpr.foldin_items.fold_in_items")
         if lr is None:
             lr = getattr(self, "_lr", None)
             if lr is None:
@@ -405,6 +407,15 @@ class Engine:
         self.flush_lazy()
         return foldin_items.fold_in_items(self.P, self.Q, self.item_bias, indptr, users, epochs=epochs, lr=lr,
                                           **kwargs)
+
+    def _refuse_foldin_adagrad(self, who: str, plain: str) -> None:
+        """The fold-in kernels take plain sequential SGD steps.  Under the other kinds the engine's rate is an SGD
+        rate all the same; Adagrad's multiplies g / sqrt(sum) and means something else, and there is no Adagrad
+        fold-in kernel: refused before anything is folded, flushed or launched."""
+        if self.opt_kind == OPT_ADAGRAD:
+            raise native.BprError(native.ERR_UNSUPPORTED,
+                                  f"Engine.{who}: the fold-in kernels are plain SGD and the engine's optimizer is "
+                                  f"Adagrad; call {plain} on the tables with an SGD learning rate")
 
     def _has_snapshot(self) -> bool:
         """True once a refresh has published a snapshot (`adaptive_snapshot()` would succeed)."""
@@ -431,9 +442,10 @@ class Engine:
 
     def set_optimizer(self, kind: int, lr: float, momentum: float = 0.0, dampening: float = 0.0,
                       nesterov: bool = False, betas=(0.9, 0.999), eps: float = 1e-8,
-                      alpha: float = 0.99) -> None:
+                      alpha: float = 0.99, lr_decay: float = 0.0) -> None:
+        """`lr_decay`: torch.optim.Adagrad's (OPT_ADAGRAD only; its `eps` default in torch is 1e-10)."""
         prm = native.OptParams(lr, momentum, dampening, int(nesterov), betas[0], betas[1], eps,
-                               alpha)
+                               alpha, lr_decay)
         native.check(self._lib.bpr_set_optimizer(self._ctx, kind, ctypes.byref(prm)))
         self.opt_kind = kind
         self._momentum = momentum
@@ -445,11 +457,12 @@ class Engine:
                                                   _ptr(mb), _ptr(vb)))
 
     def alloc_opt_state(self) -> dict:
-        """Zero state tensors of the shapes the current optimizer kind needs, bound to the ctx."""
+        """Zero state tensors of the shapes the current optimizer kind needs, bound to the ctx (Adagrad: only the
+        `v` tensors, its `sum`; fill them for a non-zero initial_accumulator_value)."""
         z = torch.zeros_like
         need_m = self.opt_kind in (OPT_MOMENTUM, OPT_ADAM) or (
             self.opt_kind == OPT_RMSPROP and getattr(self, "_momentum", 0.0) > 0)
-        need_v = self.opt_kind in (OPT_ADAM, OPT_RMSPROP)
+        need_v = self.opt_kind in (OPT_ADAM, OPT_RMSPROP, OPT_ADAGRAD)
         st = {
             "mP": z(self.P) if need_m else None, "vP": z(self.P) if need_v else None,
             "mQ": z(self.Q) if need_m else None, "vQ": z(self.Q) if need_v else None,

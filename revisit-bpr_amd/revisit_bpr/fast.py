@@ -327,6 +327,13 @@ class StreamTrainer:
         hot block stays on the launch stream, so the LDS tier stays in use): +1.4 % on the metric's configuration,
         the same curves (profiles/r06_parity_study.md).  "auto" (default): `auto_async_cut` — on with a masked side
         stream where the sorter has slack (tables of 2,048 .. 20,480 items)."""
+        if isinstance(lr, torch.optim.Optimizer):
+            # k_stream, its LDS tier and the hot block fold linear deltas; a stateful step (Adagrad's
+            # g / sqrt(sum) among them) is not linear
+            raise NotImplementedError(
+                f"StreamTrainer is plain SGD on the fused STREAM launch and takes a learning rate `lr`, not a "
+                f"torch.optim.{type(lr).__name__}: momentum / Adam / RMSprop / Adagrad run through "
+                f"BatchedStreamTrainer (or StrictTrainer)")
         if users.dtype != torch.int32 or items.dtype != torch.int32:
             raise ValueError("users / items must be int32 device tensors")
         self.model = model
@@ -588,7 +595,7 @@ def _refuse_dynamic(sampler: str, who: str) -> None:
 class StrictTrainer:
     """Epochs of the reference's exact mini-batch loop (sample → model(batch) → backward →
     optimizer.step()) inside the library, for every optimizer the engine mirrors (SGD, momentum /
-    Nesterov, Adam, RMSprop — the dense torch.optim semantics, see Model.train_strict).
+    Nesterov, Adam, RMSprop, Adagrad — the dense torch.optim semantics, see Model.train_strict).
 
     One GPU: one `bpr_train_strict` call per epoch.  Several: every rank runs the mini-batches of
     its own user shard and the replicated item table is reconciled by `item_sync` every
@@ -671,7 +678,7 @@ class StrictTrainer:
 
 class BatchedStreamTrainer:
     """Epochs of the reference's mini-batch loop with ANY torch.optim optimizer the engine mirrors
-    (SGD, momentum / Nesterov, Adam, RMSprop) as fused launches: per epoch a seeded device shuffle
+    (SGD, momentum / Nesterov, Adam, RMSprop, Adagrad) as fused launches: per epoch a seeded device shuffle
     (`bpr_shuffle_epoch`), then per sampler-refresh period `bpr_adaptive_refresh` + ONE
     `bpr_train_stream_batched` launch whose virtual mini-batches of `batch_size` triples take one
     dense optimizer step each (lazy replay for the rows a batch does not touch).  This is the

@@ -111,7 +111,7 @@ class _ArmUpdate(torch.autograd.Function):
 _FUSED_PARAMS: "dict[int, weakref.ReferenceType]" = {}
 _HOOK_INSTALLED = False
 
-_OPT_KINDS = {"SGD": 0, "Adam": 2, "RMSprop": 3}
+_OPT_KINDS = {"SGD": 0, "Adam": 2, "RMSprop": 3, "Adagrad": 4}
 
 
 def _optimizer_pre_hook(optimizer, args, kwargs):
@@ -297,25 +297,28 @@ class Model(torch.nn.Module):
         name = type(optimizer).__name__
         if name not in _OPT_KINDS:
             raise NotImplementedError(
-                f"fused BPR supports torch.optim SGD / Adam / RMSprop, got {name}; use "
+                f"fused BPR supports torch.optim SGD / Adam / RMSprop / Adagrad, got {name}; use "
                 "set_backend('torch') for other optimizers")
         if group.get("weight_decay", 0) or group.get("maximize", False) or group.get("amsgrad", False) \
                 or group.get("centered", False):
             raise NotImplementedError("weight_decay / maximize / amsgrad / centered are not fused")
+        if group.get("differentiable", False):
+            raise NotImplementedError("differentiable optimizers are not fused")
         kind = _OPT_KINDS[name]
         if name == "SGD" and group.get("momentum", 0) != 0:
             kind = 1
         sig = (kind, float(group["lr"]), group.get("momentum", 0.0), group.get("dampening", 0.0),
                bool(group.get("nesterov", False)), tuple(group.get("betas", (0.9, 0.999))),
-               group.get("eps", 1e-8), group.get("alpha", 0.99))
+               group.get("eps", 1e-8), group.get("alpha", 0.99), float(group.get("lr_decay", 0.0)))
         if sig != self._opt_sig:
             # rows are brought to "now" lazily with the CURRENT hyper-parameters: a changed lr /
             # betas / momentum (LR scheduler, manual edit) must not be applied to the zero-gradient
             # steps a row missed under the old ones — replay those first
+            # (Adagrad has no such steps: its flush launches nothing on the STRICT path)
             if self._opt_sig is not None and self._opt_sig[0] != 0 and eng.step_count > 0:
                 eng.flush_lazy()
             eng.set_optimizer(kind, lr=sig[1], momentum=sig[2], dampening=sig[3], nesterov=sig[4],
-                              betas=sig[5], eps=sig[6], alpha=sig[7])
+                              betas=sig[5], eps=sig[6], alpha=sig[7], lr_decay=sig[8])
             self._opt_sig = sig
             self._state_sig = None
         # the state tensors are looked up on every call: optimizer.load_state_dict() (checkpoint
@@ -398,7 +401,14 @@ class Model(torch.nn.Module):
             return
         rms_mom = kind == 3 and self._opt_sig is not None and self._opt_sig[2] != 0
         keys = {1: ("momentum_buffer", None), 2: ("exp_avg", "exp_avg_sq"),
-                3: ("momentum_buffer" if rms_mom else None, "square_avg")}[kind]
+                3: ("momentum_buffer" if rms_mom else None, "square_avg"), 4: (None, "sum")}[kind]
+        # Adagrad's accumulator starts at initial_accumulator_value (torch fills it in Adagrad.__init__,
+        # so it is normally there already); every other state tensor starts at zero
+        fill = 0.0
+        if kind == 4:
+            fused = {id(p) for p in self._fused_params()}
+            fill = next((float(g.get("initial_accumulator_value", 0.0)) for g in optimizer.param_groups
+                         if any(id(p) in fused for p in g["params"])), 0.0)
         bufs, created = [], False
         for prm in self._fused_params():
             st = optimizer.state[prm]
@@ -408,7 +418,7 @@ class Model(torch.nn.Module):
                     pair.append(None)
                     continue
                 if k not in st or st[k] is None:
-                    st[k] = torch.zeros_like(prm, memory_format=torch.preserve_format)
+                    st[k] = torch.full_like(prm, fill, memory_format=torch.preserve_format)
                     created = True
                 pair.append(st[k])
             st.setdefault("step", 0)

@@ -17,7 +17,8 @@ LIB_PATH = Path(os.environ.get("BPR_LIB_PATH") or
                 Path(__file__).resolve().parent.parent / "libbprcore.so")
 
 OK = 0
-OPT_SGD, OPT_MOMENTUM, OPT_ADAM, OPT_RMSPROP = 0, 1, 2, 3
+ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = -1, -2, -3, -4  # bpr_status
+OPT_SGD, OPT_MOMENTUM, OPT_ADAM, OPT_RMSPROP, OPT_ADAGRAD = 0, 1, 2, 3, 4
 MODE_STRICT, MODE_STREAM = 0, 1
 NEG_GIVEN, NEG_UNIFORM, NEG_ADAPTIVE, NEG_DYNAMIC = 0, 1, 2, 3
 SCALARS = 4
@@ -37,6 +38,7 @@ class OptParams(ctypes.Structure):
         ("beta2", c_float),
         ("eps", c_float),
         ("alpha", c_float),
+        ("lr_decay", c_float),
     ]
 
 
