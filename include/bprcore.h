@@ -93,7 +93,15 @@ typedef enum bpr_sampler_kind {
    * _cut (plain SGD); bpr_train_stream_acut, bpr_train_strict, bpr_train_stream_batched, the STRICT mode of bpr_step
    * and the fold-in entry points return BPR_ERR_UNSUPPORTED for it before the device is touched: draw with
    * bpr_sample_dynamic and pass the picks as BPR_NEG_GIVEN there. */
-  BPR_NEG_DYNAMIC = 3
+  BPR_NEG_DYNAMIC = 3,
+  /* The WARP objective (extension; Weston, Bengio, Usunier, IJCAI 2011 — LightFM's default loss): not a sampler of
+   * negatives for BPR's log-sigmoid loss but another pairwise loss, chosen here because it replaces the draw AND the
+   * step's weight: the first of N unseen uniform candidates that comes within `margin` of the positive's score, a
+   * step weighted by log(estimated rank), no step when nothing violates (bpr_set_warp, bpr_sample_warp).  Accepted
+   * and refused exactly where BPR_NEG_DYNAMIC is: bpr_train_stream / _cut and STREAM-mode bpr_step (plain SGD) run
+   * it; bpr_train_stream_acut, bpr_train_strict, bpr_train_stream_batched, the STRICT mode of bpr_step and the
+   * fold-in entry points return BPR_ERR_UNSUPPORTED for it before the device is touched. */
+  BPR_NEG_WARP = 4
 } bpr_sampler_kind;
 
 /* out_scalars layout written by bpr_forward_grad / bpr_step / bpr_train_stream (fp32, ADDED to —
@@ -166,6 +174,34 @@ int bpr_sample_uniform(bpr_ctx* ctx, const int32_t* users, int64_t B, uint64_t s
 int bpr_set_dynamic(bpr_ctx* ctx, int32_t candidates);
 int bpr_sample_dynamic(bpr_ctx* ctx, const int32_t* users, int64_t B, int32_t candidates, uint64_t seed,
                        uint64_t offset, int32_t* neg_out, float* score_out /* may be NULL */);
+
+/* The WARP objective.  For the triple with counter t = offset + position, user u, positive i, N = max_sampled:
+ *   candidates   bpr_sample_dynamic's: a_1 .. a_m = the first min(N, accepted) unseen candidates of
+ *                bpr_sample_uniform's stream for (seed, t) in order, item weights included, duplicates kept; if none
+ *                of the 4,096 is accepted, a_1 = bpr_sample_uniform's exact pick by rank (item 0 when nothing is unseen);
+ *   scores       x_i = <P[u], Q[i]> (+ item_bias[i]), x_k = <P[u], Q[a_k]> (+ item_bias[a_k]) in fp32, on the rows as
+ *                the kernel sees them;
+ *   violator     the smallest k with x_k > x_i - margin (a NaN on either side compares false: a NaN candidate never
+ *                violates, a NaN positive skips the triple); tries = k;
+ *   skipped      no k in 1 .. m violates: no step of any kind, nothing written, nothing added to the loss scalars;
+ *   weight       L = log(max(1, floor(n_unseen / tries))), n_unseen = (I - 1) - |seen(u)|, not clipped; L may be 0;
+ *   step         bpr_train_stream's plain-SGD step on (u, i, a_k) with L in the place of sigma(-x): the L2 terms, lr,
+ *                item_bias handling and hot block are the same (L = 0: the L2 terms alone);
+ *   scalars      slot 0 (the BPR-loss slot) carries sum L (margin - x_i + x_k), slot 1 the L2 term, slot 2 sum
+ *                |x_i - x_k|, slot 3 the count — all over the stepped triples only.
+ * N = 1 on a user whose every unseen item violates IS bpr_sample_uniform.
+ * bpr_set_warp: (max_sampled, margin) of the ctx's STREAM launches with BPR_NEG_WARP; max_sampled in 1 .. 32, margin
+ * finite and > 0 (else BPR_ERR_INVALID); default (10, 1.0f) — 10 is LightFM's max_sampled.
+ * bpr_sample_warp: the stand-alone kernel, one draw per entry of users / pos [n] from the ctx's tables, item_bias,
+ * seen CSR and item weights as they are in stream order.  neg_out [n] int32: the violator, -1 = skipped; tries_out
+ * [n] int32: k, 0 = skipped; xpos_out / xneg_out [n] fp32 or NULL: x_i and the violator's x_k (0 when skipped).  It
+ * reduces a score in the order the STREAM kernel does at the ctx's embedding width, so on tables that do not move its
+ * picks are that kernel's, bit for bit.  Bad max_sampled or margin, users / pos / neg_out / tries_out NULL, n < 0, no
+ * seen CSR: BPR_ERR_INVALID, nothing launched. */
+int bpr_set_warp(bpr_ctx* ctx, int32_t max_sampled, float margin);
+int bpr_sample_warp(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int64_t n, int32_t max_sampled,
+                    float margin, uint64_t seed, uint64_t offset, int32_t* neg_out, int32_t* tries_out,
+                    float* xpos_out /* may be NULL */, float* xneg_out /* may be NULL */);
 
 /* Item weights of the uniform sampler — BPRExperiment._static_sampling with
  * item_counts ** neg_sampling_alpha (experiments/bpr/exp.py:85-91, 282-293): P(negative = i) =
@@ -326,7 +362,8 @@ int bpr_get_grad(bpr_ctx* ctx, float* gP, float* gQ, float* gbias);
  * (SGD only).  `neg` is read when sampler == BPR_NEG_GIVEN, otherwise (if non-NULL) it receives
  * the sampled negatives.  seed/offset as in bpr_sample_uniform; adaptive_p = Geometric p.
  * BPR_NEG_DYNAMIC: mode STREAM only (STRICT: BPR_ERR_UNSUPPORTED — draw with bpr_sample_dynamic, step with
- * BPR_NEG_GIVEN). */
+ * BPR_NEG_GIVEN).  BPR_NEG_WARP: mode STREAM only (STRICT: BPR_ERR_UNSUPPORTED); `neg` receives -1 for a skipped
+ * triple. */
 int bpr_step(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg, int64_t B,
              int32_t mode, int32_t sampler, float adaptive_p, uint64_t seed, uint64_t offset,
              float* out_logits_pos, float* out_logits_neg, float* out_scalars);
@@ -341,8 +378,8 @@ int bpr_step(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* ne
  * (neg_samplers.py:75,122-123): after that batch's negatives are drawn and before its optimizer
  * step; the batch counter belongs to the ctx and keeps counting across calls (epochs), as the
  * sampler's _iteration_cnt does (bpr_set_sampler_iter rewinds it).  With lazy optimizers the
- * refresh flushes first.  out_scalars accumulates over the epoch.  BPR_NEG_DYNAMIC: BPR_ERR_UNSUPPORTED, checked
- * before the device is touched. */
+ * refresh flushes first.  out_scalars accumulates over the epoch.  BPR_NEG_DYNAMIC, BPR_NEG_WARP:
+ * BPR_ERR_UNSUPPORTED, checked before the device is touched. */
 int bpr_train_strict(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg_scratch,
                      int64_t n, int64_t B, int32_t sampler, float adaptive_p, uint64_t seed,
                      uint64_t offset, int64_t refresh_every, float* out_scalars);
@@ -356,7 +393,10 @@ int bpr_train_strict(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int
  * has completed on the ctx stream, not while it runs.
  * BPR_NEG_DYNAMIC (plain SGD, as every sampler here): each triple's negative is the hardest of bpr_set_dynamic's M
  * candidates under the user row the kernel holds in registers and the item rows as it reads q_j (hot-row deltas
- * included); `neg`, if non-NULL, receives the picks.  Such a launch never takes the LDS tier (bpr_set_hot_lds). */
+ * included); `neg`, if non-NULL, receives the picks.  Such a launch never takes the LDS tier (bpr_set_hot_lds).
+ * BPR_NEG_WARP (plain SGD): the WARP objective above with bpr_set_warp's (max_sampled, margin), scored as
+ * BPR_NEG_DYNAMIC scores; `neg`, if non-NULL, receives the violators, -1 for a skipped triple; out_scalars as stated
+ * there.  Never the LDS tier either. */
 int bpr_train_stream(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg,
                      int64_t n, int32_t sampler, float adaptive_p, uint64_t seed, uint64_t offset,
                      int64_t max_inflight, float* out_scalars);
@@ -382,7 +422,7 @@ int bpr_train_stream_cut(bpr_ctx* ctx, const int32_t* users, const int32_t* pos,
  * stream — the fold of the hot block, the loss sums and the item_bias write-back stay on it (k_stream_epilogue, a few
  * microseconds) — so the item table is whole after every launch (bpr_hot_fold is a no-op), out_scalars arrives on the
  * launch stream, and the LDS tier (bpr_set_hot_lds) stays in use.
- * BPR_NEG_DYNAMIC has no snapshot to cut: BPR_ERR_UNSUPPORTED. */
+ * BPR_NEG_DYNAMIC and BPR_NEG_WARP have no snapshot to cut: BPR_ERR_UNSUPPORTED. */
 int bpr_train_stream_acut(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg,
                           int64_t n, int32_t sampler, float adaptive_p, uint64_t seed,
                           uint64_t offset, int64_t max_inflight, float* out_scalars);
@@ -406,7 +446,7 @@ int bpr_hot_fold(bpr_ctx* ctx);
  * the gradient for the row's next visitor (same arithmetic, bit-identical in the max_inflight = 1
  * limit).  On by default except for Adam on a model with item_bias;
  * bpr_set_tuning(ctx, "vs_direct", 0 / 1) forces it off / on (a measurement and test aid).
- * BPR_NEG_DYNAMIC: BPR_ERR_UNSUPPORTED, checked before the device is touched. */
+ * BPR_NEG_DYNAMIC, BPR_NEG_WARP: BPR_ERR_UNSUPPORTED, checked before the device is touched. */
 int bpr_train_stream_batched(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg,
                              int64_t n, int64_t B, int32_t sampler, float adaptive_p,
                              uint64_t seed, uint64_t offset, int64_t max_inflight,
@@ -753,7 +793,7 @@ int bpr_rank_rows(const float* P, const float* Q, const float* item_bias /* or N
  * launch.  order [n] int32 or NULL: a permutation of the rows, the sequence in which they are handed to the groups of
  * the launch (longest rows first evens out the tail; NULL = list order; an entry outside [0, n) is passed over).
  * d in [1, 1024] (0: BPR_ERR_INVALID, more: BPR_ERR_UNSUPPORTED); n below 2^31; I * d and epochs * nnz below 2^31
- * (BPR_ERR_UNSUPPORTED); BPR_NEG_ADAPTIVE, BPR_NEG_DYNAMIC: BPR_ERR_UNSUPPORTED.  Arguments are validated before the device is
+ * (BPR_ERR_UNSUPPORTED); BPR_NEG_ADAPTIVE, BPR_NEG_DYNAMIC, BPR_NEG_WARP: BPR_ERR_UNSUPPORTED.  Arguments are validated before the device is
  * touched; n == 0 is BPR_OK.  indptr is read by the kernel only, except for ONE host read: the call copies indptr[0]
  * and indptr[n] back for the bound on epochs * nnz and waits for `hip_stream` to do so (the launch itself is
  * asynchronous; the call cannot be captured into a graph).  A device's first call allocates a few ticket words that
@@ -819,7 +859,7 @@ int bpr_fold_in_rows_adaptive(const float* Q, const float* item_bias /* or NULL 
  * the bits of Q_new, bias_new and neg_out do not depend on `order`, on m or the other rows, on the launch or on the
  * kernel's prefetch depth.  order [m] int32 or NULL: as bpr_fold_in_rows' (an entry outside [0, m) is passed over).
  * d in [1, 1024] (0: BPR_ERR_INVALID, more: BPR_ERR_UNSUPPORTED); m below 2^31; I * d, U * d and epochs * nnz below
- * 2^31 (BPR_ERR_UNSUPPORTED); BPR_NEG_ADAPTIVE, BPR_NEG_DYNAMIC: BPR_ERR_UNSUPPORTED; NaN lr or alpha_item: BPR_ERR_INVALID.  Arguments
+ * 2^31 (BPR_ERR_UNSUPPORTED); BPR_NEG_ADAPTIVE, BPR_NEG_DYNAMIC, BPR_NEG_WARP: BPR_ERR_UNSUPPORTED; NaN lr or alpha_item: BPR_ERR_INVALID.  Arguments
  * are validated before the device is touched; m == 0 is BPR_OK.  indptr is read by the kernel only, except for ONE
  * host read, bpr_fold_in_rows': the call copies indptr[0] and indptr[m] back for the bound on epochs * nnz and waits
  * for `hip_stream` to do so (the launch itself is asynchronous; the call cannot be captured into a graph).  It shares

@@ -46,7 +46,7 @@ __device__ __forceinline__ uint32_t draw(uint64_t seed, uint64_t t, uint32_t blo
 }
 
 enum : uint32_t { PURPOSE_UNIFORM = 0u, PURPOSE_ADAPTIVE = 1u };
-enum { NEG_GIVEN = 0, NEG_UNIFORM = 1, NEG_ADAPTIVE = 2, NEG_DYNAMIC = 3 };  // == bpr_sampler_kind
+enum { NEG_GIVEN = 0, NEG_UNIFORM = 1, NEG_ADAPTIVE = 2, NEG_DYNAMIC = 3, NEG_WARP = 4 };  // == bpr_sampler_kind
 constexpr int UNIFORM_MAX_CAND = 4096;  // rejection candidates tried before the exact rank pick
 
 // ---------------------------------------------------------------------------------------------

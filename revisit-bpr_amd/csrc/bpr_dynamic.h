@@ -60,21 +60,16 @@ struct DynamicPick {
   int32_t tag;  // what the accessor's load returned for the pick (k_stream: its hot slot, -1 = none)
 };
 
-// The item rows as the caller reads them — Rows has
-//   int32_t load(float (&q)[E], float& bias, int32_t item, int gl) const   issues the row's loads, returns a tag
-//   void finish(float (&q)[E], int32_t tag, int gl) const                  adds what depends on the tag (hot deltas)
-// p[] = the caller's register copy of the user row, q[] receives the chosen row (element layout of bpr_device.h:
-// entry e is factor e*G + gl), so the caller does not load q_j again.
-// All lanes of the wave must call this together (wave-uniform loops), as sample_uniform.
-template <int G, int E, typename Seen, typename Rows>
-__device__ __forceinline__ DynamicPick sample_dynamic(float (&q)[E], const float (&p)[E], const Rows& rows,
-                                                      const Seen& seen, int64_t n_seen,
-                                                      const int32_t* __restrict__ seen_ids, int64_t I, uint64_t seed,
-                                                      uint64_t t, int M, int lane, const ItemWeights& iw) {
+// The first min(M, accepted) accepted candidates of triple t, in order of k: lane s of the group keeps a_{s+1} in
+// `mine`; returns how many there are (1 .. M).  None of the 4,096 accepted: sample_uniform's exact pick by rank is a_1.
+// Shared with the WARP draw (bpr_warp.h).  All lanes of the wave must call this together (wave-uniform loops).
+template <int G, typename Seen>
+__device__ __forceinline__ int accepted_candidates(int32_t& mine, const Seen& seen, int64_t n_seen,
+                                                   const int32_t* __restrict__ seen_ids, int64_t I, uint64_t seed,
+                                                   uint64_t t, int M, int lane, const ItemWeights& iw) {
   static_assert(G >= 32, "lane s of the group keeps accepted candidate s: M <= 32 <= G");
   const int gl = lane & (G - 1);
-  // ---- the first min(M, accepted) accepted candidates, in order of k: lane s of the group keeps a_{s+1}
-  int32_t mine = 0;
+  mine = 0;
   int cnt = 0;
   constexpr int ROUNDS = UNIFORM_MAX_CAND / G;
   for (int round = 0; round < ROUNDS; ++round) {
@@ -99,6 +94,24 @@ __device__ __forceinline__ DynamicPick sample_dynamic(float (&q)[E], const float
     }
     cnt = 1;
   }
+  return cnt;
+}
+
+// The item rows as the caller reads them — Rows has
+//   int32_t load(float (&q)[E], float& bias, int32_t item, int gl) const   issues the row's loads, returns a tag
+//   void finish(float (&q)[E], int32_t tag, int gl) const                  adds what depends on the tag (hot deltas)
+// p[] = the caller's register copy of the user row, q[] receives the chosen row (element layout of bpr_device.h:
+// entry e is factor e*G + gl), so the caller does not load q_j again.
+// All lanes of the wave must call this together (wave-uniform loops), as sample_uniform.
+template <int G, int E, typename Seen, typename Rows>
+__device__ __forceinline__ DynamicPick sample_dynamic(float (&q)[E], const float (&p)[E], const Rows& rows,
+                                                      const Seen& seen, int64_t n_seen,
+                                                      const int32_t* __restrict__ seen_ids, int64_t I, uint64_t seed,
+                                                      uint64_t t, int M, int lane, const ItemWeights& iw) {
+  const int gl = lane & (G - 1);
+  // ---- the first min(M, accepted) accepted candidates, in order of k: lane s of the group keeps a_{s+1}
+  int32_t mine;
+  const int cnt = accepted_candidates<G>(mine, seen, n_seen, seen_ids, I, seed, t, M, lane, iw);
   // ---- score a_1 .. a_cnt, a chunk of rows in flight at a time, and keep the best
   constexpr int C = dynamic_inflight<E>();
   DynamicPick best = {0, 0.f, 0.f, -1};
@@ -134,5 +147,19 @@ __device__ __forceinline__ DynamicPick sample_dynamic(float (&q)[E], const float
   }
   return best;
 }
+
+// the item rows as stored (no hot block: the stand-alone kernels see the table folded)
+template <int G, int E>
+struct TableRows {
+  const float* Q;
+  const float* bias;  // the dense item_bias, or NULL
+  int d;
+  __device__ __forceinline__ int32_t load(float (&q)[E], float& b, int32_t item, int gl) const {
+    load_row<G, E>(q, Q + (int64_t)item * d, d, gl);
+    if (bias != nullptr) b = bias[item];
+    return -1;
+  }
+  __device__ __forceinline__ void finish(float (&)[E], int32_t, int) const {}
+};
 
 }  // namespace bpr

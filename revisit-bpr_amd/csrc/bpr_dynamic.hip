@@ -51,20 +51,6 @@ struct DynamicArgs {
   ItemWeights iw;
 };
 
-// the item rows as stored (no hot block: bpr_sample_dynamic sees the table folded)
-template <int G, int E>
-struct TableRows {
-  const float* Q;
-  const float* bias;
-  int d;
-  __device__ __forceinline__ int32_t load(float (&q)[E], float& b, int32_t item, int gl) const {
-    load_row<G, E>(q, Q + (int64_t)item * d, d, gl);
-    if (bias != nullptr) b = bias[item];
-    return -1;
-  }
-  __device__ __forceinline__ void finish(float (&)[E], int32_t, int) const {}
-};
-
 // A group per draw, grid-stride; the "seen?" answer is the binary search of the CSR slice, as the stand-alone
 // uniform kernel's (a draw tests a round or two of candidates).
 template <int G, int E>

@@ -163,6 +163,8 @@ int foldin_check_sampler(const char* who, const char* noun, int32_t sampler) {
     return fail(BPR_ERR_UNSUPPORTED, std::string(who) + ": adaptive negatives are not implemented for " + noun);
   if (sampler == BPR_NEG_DYNAMIC)
     return fail(BPR_ERR_UNSUPPORTED, std::string(who) + ": dynamic negatives are not implemented for " + noun);
+  if (sampler == BPR_NEG_WARP)
+    return fail(BPR_ERR_UNSUPPORTED, std::string(who) + ": the WARP objective is not implemented for " + noun);
   if (sampler != BPR_NEG_GIVEN && sampler != BPR_NEG_UNIFORM)
     return fail(BPR_ERR_INVALID, std::string(who) + ": unknown sampler " + std::to_string(sampler));
   return BPR_OK;

@@ -53,6 +53,8 @@ int launch_stream_lds(bpr_ctx* c, const StreamArgs& a, int sampler, const Stream
 // bpr_dynamic.hip: the plain k_stream with dynamic negatives for the ctx's shape and a "seen?" structure
 using StreamKernelFn = void (*)(const StreamArgs);
 int stream_kernel_dynamic(const bpr_ctx* c, int seen, StreamKernelFn* out);
+// bpr_warp.hip: the same for the WARP objective
+int stream_kernel_warp(const bpr_ctx* c, int seen, StreamKernelFn* out);
 
 struct Timer {
   bpr_ctx* c;

@@ -1,11 +1,13 @@
 // bpr_stream.h — k_stream, THE hot kernel of libbprcore (STREAM mode), and what it needs; a header of its own
-// because two translation units instantiate it (bprcore.hip: the plain kernel; bpr_hotlds.hip: the LDS tier of
-// the hot block).  See bpr_kernels.h for the kernels around it and DESIGN.md §4.1 for its roofline.
+// because several translation units instantiate it (bprcore.hip: the plain kernel; bpr_hotlds.hip: the LDS tier of
+// the hot block; bpr_dynamic.hip: dynamic negatives; bpr_warp.hip: the WARP objective).  See bpr_kernels.h for the
+// kernels around it and DESIGN.md §4.1 for its roofline.
 #pragma once
 #include <type_traits>
 
 #include "bpr_device.h"
 #include "bpr_dynamic.h"
+#include "bpr_warp.h"
 
 namespace bpr {
 
@@ -67,6 +69,10 @@ struct StreamArgs {
   const uint32_t* heavy_off;
   const uint32_t* heavy_bits;
   int32_t heavy_T;
+  // NEG_WARP: candidates tried per triple at most (bpr_set_warp).  It and warp_margin below sit in the two 4-byte holes
+  // the pointers' alignment left, so no field — nor the hidden arguments behind the struct — moves: the other
+  // samplers' kernels read their arguments where they did (profiles/warp_resources.md)
+  int32_t warp_N;
   // a PARTIAL adaptive snapshot (bpr_sort.h k_sort_partial): {kt, kb} per column and the key columns
   // the snapshot was sorted from (NULL: `order` is sorted whole)
   const int32_t* snap_meta;
@@ -75,11 +81,13 @@ struct StreamArgs {
   // -1 = cold, else (popularity rank << 16 | slot) — the lds_L most popular rows take this workgroup's
   // updates in a delta block in LDS, flushed into slot hot_by_rank[rank] of the global block at exit
   int32_t lds_L;
+  float warp_margin;     // NEG_WARP: the margin a violator comes within (the second hole, see warp_N)
   const int32_t* hot_by_rank;
   int32_t lds_only;      // 1: hot rows past lds_L are updated in Q like cold rows (no hot tier that wants their deltas)
   int32_t tail1, tail2;  // LDSHOT: first triple of the zones of runs of run_len / 2 and run_len / 4 (n: no such zone)
   int32_t dyn_M;         // NEG_DYNAMIC: candidates scored per triple (bpr_set_dynamic)
 };
+static_assert(sizeof(StreamArgs) == 272, "StreamArgs grew: every k_stream instantiation's hidden arguments move");
 
 // A hot row's value is its base row plus its replica delta rows; returns where this wave adds its
 // update: an encoded row offset — >= 0: element offset into Q, < 0: ~(element offset into the
@@ -175,13 +183,15 @@ __global__ __launch_bounds__(LDSHOT ? 1024 : 256,
                              (LDSHOT ? (E <= 4 ? 4 : (E <= 8 ? 3 : 2))
                                      // (dynamic negatives keep eight candidate rows in registers: 3 waves at E = 4
                                      // instead of spilling them — the sampler is there to have loads in flight)
-                                     : SAMPLER == NEG_DYNAMIC ? (E <= 2 ? BPR_STREAM_WAVES_PER_EU - 1 : (E <= 8 ? 3 : 2))
+                                     // (WARP holds the same chunk, and the positive's row beside it)
+                                     : (SAMPLER == NEG_DYNAMIC || SAMPLER == NEG_WARP) ? (E <= 2 ? BPR_STREAM_WAVES_PER_EU - 1 : (E <= 8 ? 3 : 2))
                                      : (E <= 4 ? ((SAMPLER == NEG_ADAPTIVE && SEEN == SEEN_LIST) || PART
                                                       ? BPR_STREAM_WAVES_PER_EU - 1
                                                       : BPR_STREAM_WAVES_PER_EU)
                                                : (E <= 8 ? 3 : 2))))
 void k_stream(const StreamArgs a) {
   static_assert(!(LDSHOT && SAMPLER == NEG_DYNAMIC), "dynamic negatives: the plain kernel only");
+  static_assert(!(LDSHOT && SAMPLER == NEG_WARP), "WARP: the plain kernel only");
   constexpr int GPW = 64 / G;
   const int lane = threadIdx.x & 63;
   const int gl = lane & (G - 1);
@@ -303,6 +313,7 @@ void k_stream(const StreamArgs a) {
 
     float x_mine = 0.f;  // statistics: logit of step gl of this run
     bool x_have = false;
+    float w_mine = 0.f;  // NEG_WARP: ... and its weight L
     for (int step = 0; step < Lr; ++step) {
       const int t = t0 + step;
       const bool act = run_act && t < t1;
@@ -377,7 +388,8 @@ void k_stream(const StreamArgs a) {
 
       int32_t j;
       DynamicPick pick = {0, 0.f, 0.f, -1};  // NEG_DYNAMIC: the negative comes with its row (qj) and bias
-      float qj[E];
+      WarpPick wp = {0, 0, 0.f, 0.f, 0.f, 0.f, -1, 0.f};  // NEG_WARP: the violator with both rows (qi, qj) and biases
+      float qj[E], qi[E];
       if constexpr (SAMPLER == NEG_GIVEN) {
         j = a.neg[tt];
       } else {
@@ -415,6 +427,13 @@ void k_stream(const StreamArgs a) {
           pick = sample_dynamic<G, E>(qj, pl, rows, seen, (int64_t)cur_n, a.indices + cur_lo, a.I, a.seed,
                                       a.offset + (uint64_t)tt, a.dyn_M, lane, a.iw);
           j = pick.item;
+        } else if constexpr (SAMPLER == NEG_WARP) {
+          // the first of warp_N unseen candidates within the margin of the positive under the live user row pl
+          // (bpr_warp.h); j = -1: nothing violates, the triple is skipped
+          const StreamRows<G, E> rows{a.Q, a.bias, a.hot_slot, a.hot_delta, a.hot_H, a.hot_rmask, d};
+          wp = sample_warp<G, E>(qi, qj, pl, rows, i, seen, (int64_t)cur_n, a.indices + cur_lo, a.I, a.seed,
+                                 a.offset + (uint64_t)tt, a.warp_N, a.warp_margin, lane, a.iw);
+          j = wp.item;
         } else {
           const AdaptiveRandoms rnd = {group_bcast<G>(my_rnd.uf, step, lane),
                                        group_bcast<G>(my_rnd.r, step, lane)};
@@ -437,9 +456,8 @@ void k_stream(const StreamArgs a) {
       // only sit in registers while the sampler runs (they, not issue slots, bound the occupancy)
       int32_t irow = (int32_t)((uint32_t)i * (uint32_t)d);  // encoded row offsets (hot_row)
       int32_t jrow = (int32_t)((uint32_t)j * (uint32_t)d);
-      float qi[E];
-      load_row<G, E>(qi, a.Q + (uint32_t)irow, d, gl);
-      if constexpr (SAMPLER != NEG_DYNAMIC) load_row<G, E>(qj, a.Q + (uint32_t)jrow, d, gl);
+      if constexpr (SAMPLER != NEG_WARP) load_row<G, E>(qi, a.Q + (uint32_t)irow, d, gl);
+      if constexpr (SAMPLER != NEG_DYNAMIC && SAMPLER != NEG_WARP) load_row<G, E>(qj, a.Q + (uint32_t)jrow, d, gl);
       const int32_t si = group_bcast<G>(my_si, step, lane);
       if constexpr (LDSHOT) {
         // codes (StreamArgs::lds_L): rank < lds_L -> this workgroup's LDS delta row, else the global block
@@ -455,41 +473,57 @@ void k_stream(const StreamArgs a) {
           else if (!a.lds_only) jrow = hot_row<G, E>(qj, a.hot_delta, sj & 0xFFFF, a.hot_H, a.hot_rmask, wave, d, gl);
         }
       } else {
-        if (si >= 0) irow = hot_row<G, E>(qi, a.hot_delta, si, a.hot_H, a.hot_rmask, wave, d, gl);
-        if constexpr (SAMPLER == NEG_DYNAMIC) {  // (qj already holds the row with its deltas)
-          if (pick.tag >= 0) jrow = hot_row_enc(pick.tag, a.hot_H, a.hot_rmask, wave, d);
+        if constexpr (SAMPLER == NEG_WARP) {  // (qi already holds the row with its deltas, as qj below)
+          if (si >= 0) irow = hot_row_enc(si, a.hot_H, a.hot_rmask, wave, d);
+        } else {
+          if (si >= 0) irow = hot_row<G, E>(qi, a.hot_delta, si, a.hot_H, a.hot_rmask, wave, d, gl);
+        }
+        if constexpr (SAMPLER == NEG_DYNAMIC || SAMPLER == NEG_WARP) {  // (qj already holds the row with its deltas)
+          const int32_t tj = SAMPLER == NEG_WARP ? wp.tag : pick.tag;
+          if (tj >= 0) jrow = hot_row_enc(tj, a.hot_H, a.hot_rmask, wave, d);
         } else if (a.hot_slot != nullptr) {
           const int32_t sj = a.hot_slot[j];
           if (sj >= 0) jrow = hot_row<G, E>(qj, a.hot_delta, sj, a.hot_H, a.hot_rmask, wave, d, gl);
         }
       }
       float bi = 0.f, bj = 0.f;
-      if (a.bias != nullptr) {
+      if constexpr (SAMPLER == NEG_WARP) {
+        bi = wp.bias_pos;
+        bj = wp.bias_neg;
+      } else if (a.bias != nullptr) {
         bi = a.bias[(uint32_t)i * (uint32_t)BIAS_LINE];
         if constexpr (SAMPLER == NEG_DYNAMIC) bj = pick.bias;
         else bj = a.bias[(uint32_t)j * (uint32_t)BIAS_LINE];
       }
 
       // x_uij = <p_u, q_i - q_j> (+ bias difference): one group sum
-      float xl = 0.f;
+      float x;
+      if constexpr (SAMPLER == NEG_WARP) {
+        x = wp.x_pos - wp.x_neg;  // (the two scores the violator was found by)
+      } else {
+        float xl = 0.f;
 #pragma unroll
-      for (int e = 0; e < E; ++e) xl = fmaf(pl[e], qi[e] - qj[e], xl);
-      float x = group_sum<G>(xl, lane);
-      x += bi - bj;
-      if (stats && act) {
+        for (int e = 0; e < E; ++e) xl = fmaf(pl[e], qi[e] - qj[e], xl);
+        x = group_sum<G>(xl, lane);
+        x += bi - bj;
+      }
+      // NEG_WARP: a skipped triple (no violator) writes nothing and counts nowhere
+      const bool upd = SAMPLER == NEG_WARP ? act && j >= 0 : act;
+      if (stats && upd) {
         // the L2 term is accumulated per lane (its slice of the rows): no group sums; lane k keeps
         // the logit of step k and the loss terms are evaluated once per run, lane-parallel
         s_reg += 0.5f * (a.ai * dot<E>(qi, qi) + a.an * dot<E>(qj, qj) + a.au * dot<E>(pl, pl));
         if (gl == step) {
           x_mine = x;
           x_have = true;
+          if constexpr (SAMPLER == NEG_WARP) w_mine = wp.weight;
         }
       }
-      // ---- SGD on the three rows (SURVEY §3.3 gradients), w = σ(−x); every gradient uses the
-      // pre-update values of this triple's rows
-      const float w = 1.0f / (1.0f + expf(x));
+      // ---- SGD on the three rows (SURVEY §3.3 gradients), w = σ(−x) — NEG_WARP: the rank weight L in its place —;
+      // every gradient uses the pre-update values of this triple's rows
+      const float w = SAMPLER == NEG_WARP ? wp.weight : 1.0f / (1.0f + expf(x));
       const float lr = a.lr;
-      if (act) {
+      if (upd) {
         // pad rows stay exactly zero: their update value is masked to 0 instead of branching
         const float mi = (i != a.pad_item) ? -lr : 0.f;
         const float mj = (j != a.pad_item) ? -lr : 0.f;
@@ -522,7 +556,8 @@ void k_stream(const StreamArgs a) {
       }
     }
     if (stats && x_have) {
-      s_loss += neg_logsigmoid(x_mine);
+      if constexpr (SAMPLER == NEG_WARP) s_loss += w_mine * (a.warp_margin - x_mine);  // L (margin - x_i + x_k)
+      else s_loss += neg_logsigmoid(x_mine);
       s_abs += fabsf(x_mine);
       s_cnt += 1.f;
     }

@@ -253,6 +253,9 @@ int bpr_train_stream_batched(bpr_ctx* c, const int32_t* users, const int32_t* po
   if (sampler == BPR_NEG_DYNAMIC)
     return fail(BPR_ERR_UNSUPPORTED, "bpr_train_stream_batched: dynamic negatives are not implemented for the "
                                      "batched STREAM kernel (bpr_train_stream runs them with plain SGD)");
+  if (sampler == BPR_NEG_WARP)
+    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_stream_batched: the WARP objective is not implemented for the "
+                                     "batched STREAM kernel (bpr_train_stream runs it with plain SGD)");
   if (c != nullptr) c->keys_cut = false;
   if (int rc = check_triples(c, "bpr_train_stream_batched", users, pos, n)) return rc;
   if (int rc = check_sampler(c, "bpr_train_stream_batched", sampler, adaptive_p, neg, n)) return rc;

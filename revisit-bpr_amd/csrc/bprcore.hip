@@ -18,7 +18,7 @@
 namespace bpr {
 static_assert(ORDER_PAD == BPR_ORDER_PAD, "walk vector width vs snapshot padding");
 static_assert(SEEN_CSR == STREAM_SEEN_CSR && SEEN_BITMAP == STREAM_SEEN_BITMAP && SEEN_LIST == STREAM_SEEN_LIST &&
-                  NEG_GIVEN == BPR_NEG_GIVEN && NEG_DYNAMIC == BPR_NEG_DYNAMIC,
+                  NEG_GIVEN == BPR_NEG_GIVEN && NEG_DYNAMIC == BPR_NEG_DYNAMIC && NEG_WARP == BPR_NEG_WARP,
               "the launch plan names the kernels' template arguments");
 
 static thread_local std::string g_last_error;
@@ -315,6 +315,7 @@ static StreamKernelFn stream_kernel_seen(int seen, bool full, bool part) {
 // the plain k_stream instantiation for the ctx's shape (the LDSHOT ones: bpr_hotlds.hip)
 static int stream_kernel(const bpr_ctx* c, int sampler, int seen, bool part, StreamKernelFn* out) {
   if (sampler == NEG_DYNAMIC) return stream_kernel_dynamic(c, seen, out);  // (bpr_dynamic.hip)
+  if (sampler == NEG_WARP) return stream_kernel_warp(c, seen, out);        // (bpr_warp.hip)
   return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
     using T = decltype(tag);
     constexpr int G = T::G, E = T::E;
@@ -549,7 +550,8 @@ int check_sampler(const bpr_ctx* c, const char* who, int32_t sampler, float adap
     if (neg == nullptr && B > 0) return fail(BPR_ERR_INVALID, std::string(who) + ": neg is NULL");
     return BPR_OK;
   }
-  if (sampler != BPR_NEG_UNIFORM && sampler != BPR_NEG_ADAPTIVE && sampler != BPR_NEG_DYNAMIC)
+  if (sampler != BPR_NEG_UNIFORM && sampler != BPR_NEG_ADAPTIVE && sampler != BPR_NEG_DYNAMIC &&
+      sampler != BPR_NEG_WARP)
     return fail(BPR_ERR_INVALID, std::string(who) + ": unknown sampler");
   if (c->indptr == nullptr) return fail(BPR_ERR_INVALID, std::string(who) + ": seen CSR not bound");
   if (sampler == BPR_NEG_ADAPTIVE) {
@@ -1044,6 +1046,8 @@ static int train_stream_impl(bpr_ctx* c, const int32_t* users, const int32_t* po
                              bool acut = false) {
   if (acut && sampler == BPR_NEG_DYNAMIC)
     return fail(BPR_ERR_UNSUPPORTED, "bpr_train_stream_acut: dynamic negatives have no snapshot to cut");
+  if (acut && sampler == BPR_NEG_WARP)
+    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_stream_acut: the WARP objective has no snapshot to cut");
   if (c != nullptr) c->acut_call = acut;  // (check_bound folds pending hot deltas for everybody else)
   const int rc0 = check_triples(c, "bpr_train_stream", users, pos, n);
   if (c != nullptr) c->acut_call = false;
@@ -1084,6 +1088,8 @@ static int train_stream_impl(bpr_ctx* c, const int32_t* users, const int32_t* po
   a.iw = ItemWeights{c->w_accept, c->w_alias};
   a.inv_log1mp = sampler == BPR_NEG_ADAPTIVE ? inv_log1mp(adaptive_p) : 0.f;
   a.dyn_M = c->dyn_M;
+  a.warp_N = c->warp_N;
+  a.warp_margin = c->warp_margin;
   if (sampler != BPR_NEG_GIVEN) {
     if (int rc = heavy_build_impl(c)) return rc;
     a.heavy_off = c->heavy_off;
@@ -1140,6 +1146,9 @@ int bpr_step(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg,
   if (sampler == BPR_NEG_DYNAMIC && mode == BPR_MODE_STRICT)
     return fail(BPR_ERR_UNSUPPORTED, "bpr_step: dynamic negatives in STRICT mode: draw with bpr_sample_dynamic and "
                                      "pass the picks as BPR_NEG_GIVEN");
+  if (sampler == BPR_NEG_WARP && mode == BPR_MODE_STRICT)
+    return fail(BPR_ERR_UNSUPPORTED, "bpr_step: the WARP objective in STRICT mode: it is fused into the plain-SGD "
+                                     "STREAM kernel only (bpr_train_stream)");
   if (int rc = check_triples(c, "bpr_step", users, pos, B)) return rc;
   if (int rc = check_sampler(c, "bpr_step", sampler, adaptive_p, neg, B)) return rc;
   if (mode == BPR_MODE_STREAM) {
@@ -1170,6 +1179,9 @@ int bpr_train_strict(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32
   if (sampler == BPR_NEG_DYNAMIC)
     return fail(BPR_ERR_UNSUPPORTED, "bpr_train_strict: dynamic negatives: draw each batch with bpr_sample_dynamic "
                                      "and step with BPR_NEG_GIVEN");
+  if (sampler == BPR_NEG_WARP)
+    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_strict: the WARP objective is fused into the plain-SGD STREAM kernel "
+                                     "only (bpr_train_stream)");
   if (int rc = check_triples(c, "bpr_train_strict", users, pos, n)) return rc;
   if (B < 1) return fail(BPR_ERR_INVALID, "bpr_train_strict: B must be >= 1");
   if (int rc = check_sampler(c, "bpr_train_strict", sampler, adaptive_p, neg_scratch, n)) return rc;

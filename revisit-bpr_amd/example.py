@@ -75,12 +75,17 @@ def strict_epoch(model, optimizer, sampler, users, items, seen_pad, batch_size, 
 @click.option("--seed", type=int, default=13, show_default=True)
 @click.option("--lr", type=float, default=0.00943667980759196, show_default=True)
 @click.option("--sampling-prob", type=float, default=1 / 700, show_default=True)
-@click.option("--sampler", "sampler_name", type=click.Choice(["adaptive", "dynamic"]), default="adaptive",
+@click.option("--sampler", "sampler_name", type=click.Choice(["adaptive", "dynamic", "warp"]), default="adaptive",
               show_default=True, help="adaptive: the reference's adaptive oversampling; dynamic: the highest-scoring of "
                                       "--candidates unseen uniform candidates under the live model (stream: fused; "
-                                      "strict on one GPU: drawn per batch, any --optimizer)")
+                                      "strict on one GPU: drawn per batch, any --optimizer); warp: the WARP objective "
+                                      "in BPR's place — the first of --max-sampled unseen candidates within --margin "
+                                      "of the positive, the step weighted by log(estimated rank) (--mode stream only)")
 @click.option("--candidates", type=click.IntRange(1, 32), default=4, show_default=True,
               help="--sampler dynamic: candidates scored per triple")
+@click.option("--max-sampled", type=click.IntRange(1, 32), default=10, show_default=True,
+              help="--sampler warp: candidates tried per triple at most")
+@click.option("--margin", type=float, default=1.0, show_default=True, help="--sampler warp: the margin (> 0)")
 @click.option("--mode", type=click.Choice(["stream", "batched", "strict"]), default="stream", show_default=True,
               help="stream: fused SGD launches (StreamTrainer); batched: one launch per refresh period with "
                    "virtual mini-batches, any --optimizer (BatchedStreamTrainer); strict: the reference's "
@@ -94,7 +99,7 @@ def strict_epoch(model, optimizer, sampler, users, items, seen_pad, batch_size, 
 @click.option("--refresh-cus", type=int, default=64, show_default=True,
               help="stream mode with --refresh-lag > 0: CUs the snapshot sort is masked to")
 def main(dataset_path, synthetic_name, num_users, num_items, embedding_dim, batch_size, epochs,
-         seed, lr, sampling_prob, sampler_name, candidates, mode, opt_name, refresh_lag, refresh_cus):
+         seed, lr, sampling_prob, sampler_name, candidates, max_sampled, margin, mode, opt_name, refresh_lag, refresh_cus):
     logging.basicConfig(level=logging.INFO, format="%(asctime)s | %(message)s")
     if not torch.cuda.is_available():
         raise SystemExit("example.py needs an MI355X (no CPU path)")
@@ -141,6 +146,8 @@ def main(dataset_path, synthetic_name, num_users, num_items, embedding_dim, batc
         raise SystemExit("--mode stream is the fused SGD kernel; use --mode batched for --optimizer " + opt_name)
     if sampler_name == "dynamic" and (mode == "batched" or (mode == "strict" and world > 1)):
         raise SystemExit("--sampler dynamic runs with --mode stream, or --mode strict on one GPU")
+    if sampler_name == "warp" and mode != "stream":
+        raise SystemExit("--sampler warp runs with --mode stream: the objective is fused into the plain-SGD kernel only")
     if mode == "batched":
         from revisit_bpr.fast import BatchedStreamTrainer
 
@@ -168,7 +175,8 @@ def main(dataset_path, synthetic_name, num_users, num_items, embedding_dim, batc
             f = model.logits_model.get_features()
             sync = ItemSync([f["item"].data] + ([f["item_bias"].data] if f["item_bias"] is not None else []))
         trainer = StreamTrainer(model, users_t, items_t, t["indptr"], t["indices"], lr=lr,
-                                sampler=sampler_name, candidates=candidates, adaptive_p=sampling_prob,
+                                sampler=sampler_name, candidates=candidates, max_sampled=max_sampled, margin=margin,
+                                adaptive_p=sampling_prob,
                                 batch_size=batch_size, seed=seed, rank=rank, item_sync=sync,
                                 refresh_lag="auto" if refresh_lag < 0 else refresh_lag,
                                 refresh_cus=refresh_cus if refresh_lag > 0 else 0)

@@ -188,6 +188,77 @@ def latent_factors(users: int, items: int, factors: int = 8, seed: int = 13) -> 
             np.vstack([np.zeros((1, factors)), Y]).astype(np.float32))
 
 
+_STRUCTURED_SHIFT = 30.0  # Zipf-Mandelbrot shift of generate_structured's popularity
+
+
+def _structured_draws(rng, num_users: int, num_items: int, interactions: int, rank: int):
+    """The seeded draws of `generate_structured`, in its order: (n_u, log pop, A, B)."""
+    n_u = np.exp(rng.standard_normal(num_users))  # log-normal activity, sigma 1
+    n_u = np.clip(np.round(n_u * (interactions / n_u.sum())), 1, max(1, num_items // 3)).astype(np.int64)
+    logpop = -np.log(rng.permutation(num_items) + 1.0 + _STRUCTURED_SHIFT)
+    A = rng.standard_normal((num_users, rank)) / np.sqrt(np.sqrt(rank))
+    B = rng.standard_normal((num_items, rank)) / np.sqrt(np.sqrt(rank))  # <a_u, b_i> ~ N(0, 1)
+    return n_u, logpop, A, B
+
+
+def generate_structured(num_users: int, num_items: int, interactions: int, *, rank: int = 16,
+                        popularity_skew: float = 1.0, temperature: float = 1.0, seed: int = 0,
+                        eval_users: int = 0, holdout: float = 0.2) -> Interactions:
+    """Data with PER-USER structure, for judging samplers and losses that exist to fix the ranking at the head
+    (`generate` draws items by popularity alone: every sampler ends at the same nDCG there).
+    Users and items get latent vectors a_u, b_i (`rank` factors, <a_u, b_i> ~ N(0, 1)) from a generator seeded
+    with `seed`; user u draws its n_u items WITHOUT replacement from
+    softmax((<a_u, b_i> + popularity_skew * log pop_i) / temperature) — Gumbel top-k —, pop_i Zipf over a random
+    permutation of the items, n_u log-normal and scaled to `interactions` in total.  temperature -> 0 makes a user's
+    items its top n_u by the logit, a large one makes them uniform; popularity_skew 0 leaves the factors alone.
+    Deterministic in `seed`, CPU only, O(num_users x num_items) time (blocked over users).  Returns what
+    `generate_named` returns (ids from 1, row 0 the pad row; `eval_users` users give up `holdout` of their items
+    as ranking targets); `structured_factors` returns a_u, b_i."""
+    if num_users < 1 or num_items < 3 or interactions < 1 or rank < 1 or not temperature > 0:
+        raise ValueError("generate_structured: num_users >= 1, num_items >= 3, interactions >= 1, rank >= 1, "
+                         "temperature > 0")
+    rng = np.random.default_rng(seed)
+    U, I = num_users + 1, num_items + 1
+    n_u, logpop, A, B = _structured_draws(rng, num_users, num_items, interactions, rank)
+    ku = np.repeat(np.arange(1, U, dtype=np.int64), n_u)
+    picks = []
+    block = max(1, min(num_users, (64 << 20) // num_items))
+    for lo in range(0, num_users, block):
+        hi = min(lo + block, num_users)
+        logit = (A[lo:hi] @ B.T + popularity_skew * logpop[None, :]) / temperature
+        score = logit + rng.gumbel(size=(hi - lo, num_items))
+        kmax = int(n_u[lo:hi].max())
+        top = np.argpartition(-score, kmax - 1, axis=1)[:, :kmax]
+        top = np.take_along_axis(top, np.argsort(-np.take_along_axis(score, top, axis=1), axis=1), axis=1)
+        picks.extend(top[r, :n_u[lo + r]] + 1 for r in range(hi - lo))
+    ki = np.concatenate(picks).astype(np.int64)
+    ev = np.sort(rng.choice(np.arange(1, U), size=min(eval_users, num_users), replace=False)) \
+        if eval_users > 0 else np.zeros(0, np.int64)
+    is_ev = np.zeros(U, bool)
+    is_ev[ev] = True
+    held = is_ev[ku] & (rng.random(ku.shape[0]) < holdout)
+    tr_u, tr_i = ku[~held], ki[~held]
+    o = np.lexsort((tr_i, tr_u))
+    tr_u, tr_i = tr_u[o], tr_i[o]
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(tr_u, minlength=U))]).astype(np.int64)
+    he_u, he_i = ku[held], ki[held]
+    o = np.lexsort((he_i, he_u))
+    he_u, he_i = he_u[o], he_i[o]
+    cnt = np.bincount(he_u, minlength=U)[ev] if ev.size else np.zeros(0, np.int64)
+    return Interactions(
+        num_users=U, num_items=I, users=tr_u.astype(np.int32), items=tr_i.astype(np.int32),
+        indptr=indptr, indices=tr_i.astype(np.int32), eval_users=ev.astype(np.int32),
+        eval_indptr=np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64), eval_items=he_i.astype(np.int32))
+
+
+def structured_factors(num_users: int, num_items: int, interactions: int, *, rank: int = 16,
+                       seed: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """What `generate_structured(num_users, num_items, interactions, rank=rank, seed=seed)` drew its items from:
+    (A [num_users + 1, rank], B [num_items + 1, rank], log pop [num_items + 1]), row 0 = the pad row, zero."""
+    _, logpop, A, B = _structured_draws(np.random.default_rng(seed), num_users, num_items, interactions, rank)
+    return (np.vstack([np.zeros((1, rank)), A]), np.vstack([np.zeros((1, rank)), B]), np.concatenate([[0.0], logpop]))
+
+
 def generate_named(name: str, eval_users: int = 0, seed: int = 13, scale: float = 1.0,
                    **kw) -> Interactions:
     users, items, actions, med, mn = SHAPES[name]

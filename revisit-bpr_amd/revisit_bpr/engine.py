@@ -12,11 +12,11 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
-from revisit_bpr.native import (MODE_STREAM, MODE_STRICT, NEG_ADAPTIVE, NEG_DYNAMIC, NEG_GIVEN, NEG_UNIFORM,
+from revisit_bpr.native import (MODE_STREAM, MODE_STRICT, NEG_ADAPTIVE, NEG_DYNAMIC, NEG_GIVEN, NEG_UNIFORM, NEG_WARP,
                                 OPT_ADAGRAD, OPT_ADAM, OPT_MOMENTUM, OPT_RMSPROP, OPT_SGD)
 
 __all__ = ["Engine", "MaskedStream", "cu_mask", "resolve_reg_alphas", "MODE_STREAM", "MODE_STRICT", "NEG_ADAPTIVE",
-           "NEG_DYNAMIC", "NEG_GIVEN", "NEG_UNIFORM", "OPT_ADAGRAD", "OPT_ADAM", "OPT_MOMENTUM", "OPT_RMSPROP", "OPT_SGD"]
+           "NEG_DYNAMIC", "NEG_GIVEN", "NEG_UNIFORM", "NEG_WARP", "OPT_ADAGRAD", "OPT_ADAM", "OPT_MOMENTUM", "OPT_RMSPROP", "OPT_SGD"]
 
 
 def resolve_reg_alphas(reg_alphas: Optional[dict]) -> tuple[float, float, float]:
@@ -498,6 +498,31 @@ class Engine:
                                                   offset, out.data_ptr(), _ptr(score)))
         return (out, score) if return_scores else out
 
+    def set_warp(self, max_sampled: int, margin: float = 1.0) -> None:
+        """The WARP objective of `train_stream(sampler=NEG_WARP)` (``bpr_set_warp``): at most `max_sampled` (1 .. 32,
+        default 10) unseen candidates tried per triple, a violator comes within `margin` (> 0, default 1.0) of the
+        positive's score."""
+        native.check(self._lib.bpr_set_warp(self._ctx, int(max_sampled), float(margin)))
+
+    def sample_warp(self, users: torch.Tensor, pos: torch.Tensor, max_sampled: int, seed: int, offset: int = 0,
+                    margin: float = 1.0, return_scores: bool = False):
+        """The WARP draw (``bpr_sample_warp``) on the tables as they are now: per (user, positive) the first of the
+        first `max_sampled` unseen items of `sample_uniform`'s candidate stream whose score exceeds the positive's
+        less `margin`.  Returns (neg, tries): neg = -1 and tries = 0 where nothing violates (the triple WARP skips);
+        return_scores: also (x_pos, x_neg), fp32, x_neg = 0 where skipped."""
+        self._sync_stream()
+        users, pos = self._ids(users, "users"), self._ids(pos, "pos")
+        if users.numel() != pos.numel():
+            raise ValueError("sample_warp: users and pos differ in length")
+        n = users.numel()
+        neg, tries = torch.empty_like(users), torch.empty_like(users)
+        xp = torch.empty(n, dtype=torch.float32, device=self.device) if return_scores else None
+        xn = torch.empty(n, dtype=torch.float32, device=self.device) if return_scores else None
+        native.check(self._lib.bpr_sample_warp(self._ctx, users.data_ptr(), pos.data_ptr(), n, int(max_sampled),
+                                               float(margin), seed, offset, neg.data_ptr(), tries.data_ptr(),
+                                               _ptr(xp), _ptr(xn)))
+        return (neg, tries, xp, xn) if return_scores else (neg, tries)
+
     def adaptive_refresh(self) -> None:
         """AdaptiveSampler.update_stats: snapshot of the item table as of now, in stream order."""
         self._sync_stream()
@@ -737,7 +762,10 @@ class Engine:
         (``bpr_train_stream_cut``) — the next `adaptive_refresh_begin` only queues the sort.
         cut="async": that cut runs on the side stream beside the NEXT launch and folds nothing
         (``bpr_train_stream_acut``); call `hot_fold()` before reading the item table's storage.
-        sampler=NEG_DYNAMIC: the hardest of `set_dynamic`'s candidates per triple; `neg` (if given) receives the picks."""
+        sampler=NEG_DYNAMIC: the hardest of `set_dynamic`'s candidates per triple; `neg` (if given) receives the picks.
+        sampler=NEG_WARP: the WARP objective with `set_warp`'s parameters — the first violator, a step weighted by
+        log(estimated rank), no step where nothing violates (`neg` receives -1 there; `scalars` count stepped triples
+        only and slot 0 carries sum L (margin - x_i + x_k))."""
         self._sync_stream()
         if users.dtype != torch.int32 or pos.dtype != torch.int32:
             raise ValueError("train_stream takes int32 id tensors (no hidden copies on the hot path)")

@@ -202,10 +202,11 @@ def resolve_schedule(I: int, d: int, n: int, batch_size: int, lr: float, sampler
     # "dynamic" (the hardest of M uniform candidates, scored on the live rows) is scheduled as "uniform" is — no
     # snapshot, so no refresh and no lag — and without the LDS tier, whose rows are not live: "auto" is 0, rows asked
     # for are refused
-    adaptive = {"adaptive": True, "uniform": False, "dynamic": False}[sampler]
-    if sampler == "dynamic":
+    # "warp" (the WARP objective: the first of N uniform candidates within the margin, scored on the live rows) likewise
+    adaptive = {"adaptive": True, "uniform": False, "dynamic": False, "warp": False}[sampler]
+    if sampler in ("dynamic", "warp"):
         if not isinstance(hot_lds, str) and int(hot_lds) != 0:
-            raise ValueError("sampler 'dynamic' scores its candidates on the live item rows: no LDS tier (hot_lds 0)")
+            raise ValueError(f"sampler '{sampler}' scores its candidates on the live item rows: no LDS tier (hot_lds 0)")
         hot_lds = 0
     world = max(world, 1)
     every = max(1, int(I * math.log(I) / batch_size))
@@ -258,7 +259,8 @@ class StreamTrainer:
                  refresh_lag: float | str = 0.0, refresh_split: int = 1, refresh_cus: int = 0,
                  shard_refresh: bool = False, cadence: str = "job", hot_split: int = 1,
                  rounds: Optional[int] = None, jit_plan: bool = False, async_cut: bool | str = "auto",
-                 hot_lds: int | str = "auto", launch_split: int | str = "auto", candidates: int = 4) -> None:
+                 hot_lds: int | str = "auto", launch_split: int | str = "auto", candidates: int = 4,
+                 max_sampled: int = 10, margin: float = 1.0) -> None:
         """model: revisit_bpr.models.BPR on a ROCm device; users/items: int32 training triples on
         the device; seen CSR: int64 indptr [U+1], int32 indices.  `batch_size` only sets the
         adaptive refresh period int(I·ln I / batch_size) batches, as example.py:302.
@@ -266,6 +268,12 @@ class StreamTrainer:
         sampler "dynamic" (extension): dynamic negative sampling — per triple the highest-scoring of `candidates`
         (1 .. 32) unseen uniform candidates under the live rows (`Engine.set_dynamic`).  Scheduled as
         "uniform": no snapshot, no refresh, no lag, no LDS tier.
+
+        sampler "warp" (extension): not BPR's loss but the WARP objective (Weston et al. 2011, LightFM's default) — per
+        triple the first of at most `max_sampled` (1 .. 32) unseen uniform candidates that comes within `margin` of
+        the positive's score, a step weighted by log(estimated rank), no step when nothing violates
+        (`Engine.set_warp`).  Scheduled as "uniform".  The epoch's `bpr_loss` is then the WARP loss
+        and `triples` counts the stepped triples.
 
         Snapshot schedule of the adaptive sampler (extensions; the defaults are the reference's
         ``update_stats`` every period, neg_samplers.py:122-132):
@@ -353,9 +361,12 @@ class StreamTrainer:
         self.engine.bind_seen_csr(seen_indptr, seen_indices)
         model._has_csr = True
         self.engine.set_optimizer(eng.OPT_SGD, lr=lr)
-        self.sampler = {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM, "dynamic": eng.NEG_DYNAMIC}[sampler]
+        self.sampler = {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM, "dynamic": eng.NEG_DYNAMIC,
+                        "warp": eng.NEG_WARP}[sampler]
         if self.sampler == eng.NEG_DYNAMIC:
             self.engine.set_dynamic(candidates)
+        if self.sampler == eng.NEG_WARP:
+            self.engine.set_warp(max_sampled, margin)
         self.adaptive_p = adaptive_p
         self.cadence = cadence
         self.launch_split, self.chunk = sched.launch_split, sched.chunk
@@ -592,6 +603,13 @@ def _refuse_dynamic(sampler: str, who: str) -> None:
                          "the picks as given negatives")
 
 
+def _refuse_warp(sampler: str, who: str) -> None:
+    if sampler == "warp":
+        raise ValueError(f"{who}: the WARP objective is fused into the plain-SGD STREAM kernel only "
+                         "(StreamTrainer(sampler='warp')): its draw and its step weight are one computation on the "
+                         "live rows, and no other trainer has a kernel for it")
+
+
 class StrictTrainer:
     """Epochs of the reference's exact mini-batch loop (sample → model(batch) → backward →
     optimizer.step()) inside the library, for every optimizer the engine mirrors (SGD, momentum /
@@ -619,6 +637,7 @@ class StrictTrainer:
         self.n = users.numel()
         model.bind_seen_csr(seen_indptr, seen_indices)
         _refuse_dynamic(sampler, type(self).__name__)
+        _refuse_warp(sampler, type(self).__name__)
         self.sampler = {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM}[sampler]
         self.adaptive_p, self.batch = adaptive_p, batch_size
         I = self.engine.I
@@ -701,6 +720,7 @@ class BatchedStreamTrainer:
         self.n = users.numel()
         model.bind_seen_csr(seen_indptr, seen_indices)
         _refuse_dynamic(sampler, type(self).__name__)
+        _refuse_warp(sampler, type(self).__name__)
         self.sampler = {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM}[sampler]
         self.adaptive_p, self.batch = adaptive_p, batch_size
         I, U = self.engine.I, self.engine.U

@@ -20,7 +20,7 @@ OK = 0
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = -1, -2, -3, -4  # bpr_status
 OPT_SGD, OPT_MOMENTUM, OPT_ADAM, OPT_RMSPROP, OPT_ADAGRAD = 0, 1, 2, 3, 4
 MODE_STRICT, MODE_STREAM = 0, 1
-NEG_GIVEN, NEG_UNIFORM, NEG_ADAPTIVE, NEG_DYNAMIC = 0, 1, 2, 3
+NEG_GIVEN, NEG_UNIFORM, NEG_ADAPTIVE, NEG_DYNAMIC, NEG_WARP = 0, 1, 2, 3, 4
 SCALARS = 4
 SIM_DOT, SIM_COSINE = 0, 1  # BPR_SIM_DOT, BPR_SIM_COSINE
 REFRESH_INFO_LEN = 8  # BPR_REFRESH_INFO_LEN: int32 entries bpr_adaptive_refresh_info fills
@@ -69,6 +69,9 @@ SIGNATURES = {
     "bpr_sample_uniform": (c_int, [c_void_p, c_void_p, c_int64, c_uint64, c_uint64, c_void_p]),
     "bpr_set_dynamic": (c_int, [c_void_p, c_int32]),
     "bpr_sample_dynamic": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "bpr_set_warp": (c_int, [c_void_p, c_int32, c_float]),
+    "bpr_sample_warp": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_uint64, c_uint64,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "bpr_adaptive_refresh": (c_int, [c_void_p]),
     "bpr_adaptive_refresh_info": (c_int, [c_void_p, POINTER(c_int32)]),
     "bpr_adaptive_refresh_begin": (c_int, [c_void_p]),
