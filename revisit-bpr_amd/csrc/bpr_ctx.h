@@ -34,9 +34,9 @@ struct bpr_ctx {
   float au = 0.f, ai = 0.f, an = 0.f;
   const float* w_accept = nullptr;  // item weights of the uniform sampler (alias table, caller-owned)
   const int32_t* w_alias = nullptr;
-  int warp_N = 10;          // bpr_set_warp: candidates a BPR_NEG_WARP draw tries at most (WARP_DEFAULT, bpr_warp_plan.h)
+  int warp_N = 10;          // bpr_set_warp: candidates a BPR_NEG_WARP draw tries at most (WARP_DEFAULT, bpr_scored_plan.h)
   float warp_margin = 1.f;  // ... and its margin
-  int dyn_M = 4;  // bpr_set_dynamic: candidates of a BPR_NEG_DYNAMIC draw (DYNAMIC_DEFAULT, bpr_dynamic_plan.h)
+  int dyn_M = 4;  // bpr_set_dynamic: candidates of a BPR_NEG_DYNAMIC draw (DYNAMIC_DEFAULT, bpr_scored_plan.h)
   int opt_kind = BPR_OPT_SGD;
   bpr_opt_params opt = {0.f, 0.f, 0.f, 0, 0.9f, 0.999f, 1e-8f, 0.99f};
   float *mP = nullptr, *vP = nullptr, *mQ = nullptr, *vQ = nullptr, *mb = nullptr, *vb = nullptr;

@@ -161,10 +161,7 @@ static int g_cus[FOLDIN_MAX_DEV];
 int foldin_check_sampler(const char* who, const char* noun, int32_t sampler) {
   if (sampler == BPR_NEG_ADAPTIVE)
     return fail(BPR_ERR_UNSUPPORTED, std::string(who) + ": adaptive negatives are not implemented for " + noun);
-  if (sampler == BPR_NEG_DYNAMIC)
-    return fail(BPR_ERR_UNSUPPORTED, std::string(who) + ": dynamic negatives are not implemented for " + noun);
-  if (sampler == BPR_NEG_WARP)
-    return fail(BPR_ERR_UNSUPPORTED, std::string(who) + ": the WARP objective is not implemented for " + noun);
+  if (int rc = refuse_scored(std::string(who) + " (" + noun + ")", sampler)) return rc;
   if (sampler != BPR_NEG_GIVEN && sampler != BPR_NEG_UNIFORM)
     return fail(BPR_ERR_INVALID, std::string(who) + ": unknown sampler " + std::to_string(sampler));
   return BPR_OK;

@@ -11,6 +11,8 @@
 
 #include <algorithm>
 
+#include "bpr_group_shape.h"
+
 namespace bpr {
 
 constexpr int FOLDIN_BLOCK = 256;    // threads of a workgroup: 8 groups of 32 lanes, or 4 of 64
@@ -41,9 +43,9 @@ struct FoldinPlan {
 
 // the same (G, E) as bpr_bind_tables chooses for a table of this d
 inline void foldin_ge(int d, int* G, int* E) {
-  *G = d <= 128 ? 32 : 64;
-  const int per_lane = (d + *G - 1) / *G;
-  *E = *G == 32 ? (per_lane <= 1 ? 1 : per_lane <= 2 ? 2 : 4) : (per_lane <= 4 ? 4 : per_lane <= 8 ? 8 : 16);
+  const GroupShape g = group_shape(d);
+  *G = g.G;
+  *E = g.E;
 }
 
 // depth `base` at E <= 4, halved per doubling of E past 4: the rings live in VGPRs

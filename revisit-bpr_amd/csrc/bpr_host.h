@@ -16,6 +16,8 @@ int check_triples(const bpr_ctx* c, const char* who, const int32_t* users, const
                   int64_t B);
 int check_sampler(const bpr_ctx* c, const char* who, int32_t sampler, float adaptive_p,
                   const int32_t* neg, int64_t B);
+// the scored samplers (sampler_scored, bpr_scored_plan.h) off plain-SGD bpr_train_stream: refused by name (bprcore.hip)
+int refuse_scored(const std::string& who, int32_t sampler);
 float inv_log1mp(float p);
 int strict_flush_impl(bpr_ctx* c);                          // STRICT lazy-replay flush (bprcore.hip)
 int vs_flush(bpr_ctx* c, bool users, bool items);           // bpr_vstream.hip
@@ -55,6 +57,11 @@ using StreamKernelFn = void (*)(const StreamArgs);
 int stream_kernel_dynamic(const bpr_ctx* c, int seen, StreamKernelFn* out);
 // bpr_warp.hip: the same for the WARP objective
 int stream_kernel_warp(const bpr_ctx* c, int seen, StreamKernelFn* out);
+// bpr_dynamic.hip: what bpr_sample_dynamic and bpr_sample_warp do once the call's part of the shape and of the
+// kernel arguments (bpr_scored.h) is filled: the checks, the plan and the launch of k_sample_scored
+struct ScoredShape;
+struct ScoredWarpArgs;
+int launch_sample_scored(bpr_ctx* c, const char* who, ScoredShape s, ScoredWarpArgs a);
 
 struct Timer {
   bpr_ctx* c;

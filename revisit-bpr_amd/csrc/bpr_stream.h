@@ -6,8 +6,7 @@
 #include <type_traits>
 
 #include "bpr_device.h"
-#include "bpr_dynamic.h"
-#include "bpr_warp.h"
+#include "bpr_scored.h"
 
 namespace bpr {
 
@@ -110,7 +109,7 @@ __device__ __forceinline__ int32_t hot_row(float (&q)[E], const float* __restric
 __device__ __forceinline__ int32_t hot_row_enc(int32_t slot, int32_t H, int32_t rmask, int wave, int d) {
   return ~(int32_t)((uint32_t)((wave & rmask) * H + slot) * (uint32_t)d);
 }
-// k_stream's item rows as sample_dynamic reads its candidates (bpr_dynamic.h): what the kernel reads q_j with —
+// k_stream's item rows as sample_scored reads its candidates (bpr_scored.h): what the kernel reads q_j with —
 // the row, its replica deltas if it is hot, its entry of the wide bias table.  tag = the row's hot slot.
 template <int G, int E>
 struct StreamRows {
@@ -184,14 +183,14 @@ __global__ __launch_bounds__(LDSHOT ? 1024 : 256,
                                      // (dynamic negatives keep eight candidate rows in registers: 3 waves at E = 4
                                      // instead of spilling them — the sampler is there to have loads in flight)
                                      // (WARP holds the same chunk, and the positive's row beside it)
-                                     : (SAMPLER == NEG_DYNAMIC || SAMPLER == NEG_WARP) ? (E <= 2 ? BPR_STREAM_WAVES_PER_EU - 1 : (E <= 8 ? 3 : 2))
+                                     : sampler_scored(SAMPLER) ? (E <= 2 ? BPR_STREAM_WAVES_PER_EU - 1 : (E <= 8 ? 3 : 2))
                                      : (E <= 4 ? ((SAMPLER == NEG_ADAPTIVE && SEEN == SEEN_LIST) || PART
                                                       ? BPR_STREAM_WAVES_PER_EU - 1
                                                       : BPR_STREAM_WAVES_PER_EU)
                                                : (E <= 8 ? 3 : 2))))
 void k_stream(const StreamArgs a) {
-  static_assert(!(LDSHOT && SAMPLER == NEG_DYNAMIC), "dynamic negatives: the plain kernel only");
-  static_assert(!(LDSHOT && SAMPLER == NEG_WARP), "WARP: the plain kernel only");
+  constexpr bool SCORED = sampler_scored(SAMPLER);  // NEG_DYNAMIC, NEG_WARP: the negative comes out of sample_scored
+  static_assert(!(LDSHOT && SCORED), "dynamic negatives, WARP: the plain kernel only");
   constexpr int GPW = 64 / G;
   const int lane = threadIdx.x & 63;
   const int gl = lane & (G - 1);
@@ -387,8 +386,8 @@ void k_stream(const StreamArgs a) {
       }
 
       int32_t j;
-      DynamicPick pick = {0, 0.f, 0.f, -1};  // NEG_DYNAMIC: the negative comes with its row (qj) and bias
-      WarpPick wp = {0, 0, 0.f, 0.f, 0.f, 0.f, -1, 0.f};  // NEG_WARP: the violator with both rows (qi, qj) and biases
+      // SCORED: the negative comes with its row (qj) and bias, NEG_WARP's violator with both rows (qi, qj) and biases
+      ScoredPick pick = {0, 0, 0.f, 0.f, 0.f, 0.f, -1, 0.f};
       float qj[E], qi[E];
       if constexpr (SAMPLER == NEG_GIVEN) {
         j = a.neg[tt];
@@ -421,19 +420,14 @@ void k_stream(const StreamArgs a) {
             j = sample_uniform<G>(seen, (int64_t)cur_n, a.indices + cur_lo, a.I, a.seed,
                                   a.offset + (uint64_t)tt, lane, a.iw);
           }
-        } else if constexpr (SAMPLER == NEG_DYNAMIC) {
-          // the hardest of dyn_M unseen candidates under the live user row pl (bpr_dynamic.h)
+        } else if constexpr (SCORED) {
+          // under the live user row pl (bpr_scored.h) — NEG_DYNAMIC: the hardest of dyn_M unseen candidates; NEG_WARP:
+          // the first of warp_N within the margin of the positive, j = -1: nothing violates, the triple is skipped
           const StreamRows<G, E> rows{a.Q, a.bias, a.hot_slot, a.hot_delta, a.hot_H, a.hot_rmask, d};
-          pick = sample_dynamic<G, E>(qj, pl, rows, seen, (int64_t)cur_n, a.indices + cur_lo, a.I, a.seed,
-                                      a.offset + (uint64_t)tt, a.dyn_M, lane, a.iw);
+          pick = sample_scored<G, E, SAMPLER>(qi, qj, pl, rows, i, seen, (int64_t)cur_n, a.indices + cur_lo, a.I, a.seed,
+                                              a.offset + (uint64_t)tt, SAMPLER == NEG_WARP ? a.warp_N : a.dyn_M,
+                                              a.warp_margin, lane, a.iw);
           j = pick.item;
-        } else if constexpr (SAMPLER == NEG_WARP) {
-          // the first of warp_N unseen candidates within the margin of the positive under the live user row pl
-          // (bpr_warp.h); j = -1: nothing violates, the triple is skipped
-          const StreamRows<G, E> rows{a.Q, a.bias, a.hot_slot, a.hot_delta, a.hot_H, a.hot_rmask, d};
-          wp = sample_warp<G, E>(qi, qj, pl, rows, i, seen, (int64_t)cur_n, a.indices + cur_lo, a.I, a.seed,
-                                 a.offset + (uint64_t)tt, a.warp_N, a.warp_margin, lane, a.iw);
-          j = wp.item;
         } else {
           const AdaptiveRandoms rnd = {group_bcast<G>(my_rnd.uf, step, lane),
                                        group_bcast<G>(my_rnd.r, step, lane)};
@@ -457,7 +451,7 @@ void k_stream(const StreamArgs a) {
       int32_t irow = (int32_t)((uint32_t)i * (uint32_t)d);  // encoded row offsets (hot_row)
       int32_t jrow = (int32_t)((uint32_t)j * (uint32_t)d);
       if constexpr (SAMPLER != NEG_WARP) load_row<G, E>(qi, a.Q + (uint32_t)irow, d, gl);
-      if constexpr (SAMPLER != NEG_DYNAMIC && SAMPLER != NEG_WARP) load_row<G, E>(qj, a.Q + (uint32_t)jrow, d, gl);
+      if constexpr (!SCORED) load_row<G, E>(qj, a.Q + (uint32_t)jrow, d, gl);
       const int32_t si = group_bcast<G>(my_si, step, lane);
       if constexpr (LDSHOT) {
         // codes (StreamArgs::lds_L): rank < lds_L -> this workgroup's LDS delta row, else the global block
@@ -478,9 +472,8 @@ void k_stream(const StreamArgs a) {
         } else {
           if (si >= 0) irow = hot_row<G, E>(qi, a.hot_delta, si, a.hot_H, a.hot_rmask, wave, d, gl);
         }
-        if constexpr (SAMPLER == NEG_DYNAMIC || SAMPLER == NEG_WARP) {  // (qj already holds the row with its deltas)
-          const int32_t tj = SAMPLER == NEG_WARP ? wp.tag : pick.tag;
-          if (tj >= 0) jrow = hot_row_enc(tj, a.hot_H, a.hot_rmask, wave, d);
+        if constexpr (SCORED) {  // (qj already holds the row with its deltas)
+          if (pick.tag >= 0) jrow = hot_row_enc(pick.tag, a.hot_H, a.hot_rmask, wave, d);
         } else if (a.hot_slot != nullptr) {
           const int32_t sj = a.hot_slot[j];
           if (sj >= 0) jrow = hot_row<G, E>(qj, a.hot_delta, sj, a.hot_H, a.hot_rmask, wave, d, gl);
@@ -488,18 +481,18 @@ void k_stream(const StreamArgs a) {
       }
       float bi = 0.f, bj = 0.f;
       if constexpr (SAMPLER == NEG_WARP) {
-        bi = wp.bias_pos;
-        bj = wp.bias_neg;
+        bi = pick.bias_pos;
+        bj = pick.bias_neg;
       } else if (a.bias != nullptr) {
         bi = a.bias[(uint32_t)i * (uint32_t)BIAS_LINE];
-        if constexpr (SAMPLER == NEG_DYNAMIC) bj = pick.bias;
+        if constexpr (SCORED) bj = pick.bias_neg;
         else bj = a.bias[(uint32_t)j * (uint32_t)BIAS_LINE];
       }
 
       // x_uij = <p_u, q_i - q_j> (+ bias difference): one group sum
       float x;
       if constexpr (SAMPLER == NEG_WARP) {
-        x = wp.x_pos - wp.x_neg;  // (the two scores the violator was found by)
+        x = pick.x_pos - pick.x_neg;  // (the two scores the violator was found by)
       } else {
         float xl = 0.f;
 #pragma unroll
@@ -516,12 +509,12 @@ void k_stream(const StreamArgs a) {
         if (gl == step) {
           x_mine = x;
           x_have = true;
-          if constexpr (SAMPLER == NEG_WARP) w_mine = wp.weight;
+          if constexpr (SAMPLER == NEG_WARP) w_mine = pick.weight;
         }
       }
       // ---- SGD on the three rows (SURVEY §3.3 gradients), w = σ(−x) — NEG_WARP: the rank weight L in its place —;
       // every gradient uses the pre-update values of this triple's rows
-      const float w = SAMPLER == NEG_WARP ? wp.weight : 1.0f / (1.0f + expf(x));
+      const float w = SAMPLER == NEG_WARP ? pick.weight : 1.0f / (1.0f + expf(x));
       const float lr = a.lr;
       if (upd) {
         // pad rows stay exactly zero: their update value is masked to 0 instead of branching
@@ -591,6 +584,23 @@ void k_stream(const StreamArgs a) {
     }
   }
   if (stats) reduce_scalars(a.partials, s_loss, s_reg, s_abs, s_cnt, lane);
+}
+
+// ---- which plain k_stream (the LDSHOT ones: bpr_hotlds.hip) a launch of sampler SMP runs at width d, for a "seen?"
+// structure; the translation unit that calls this holds the instantiations (bprcore.hip, bpr_dynamic.hip, bpr_warp.hip)
+using StreamKernelFn = void (*)(const StreamArgs);
+template <int G, int E, int SMP, int SN>
+StreamKernelFn stream_kernel_of(bool full, bool part) {
+  if constexpr (SMP == NEG_ADAPTIVE)  // a partial snapshot: the instantiations whose walk can finish inside a bin
+    if (part) return full ? &k_stream<G, E, SMP, SN, true, true> : &k_stream<G, E, SMP, SN, false, true>;
+  return full ? &k_stream<G, E, SMP, SN, true> : &k_stream<G, E, SMP, SN, false>;
+}
+template <int G, int E, int SMP>
+StreamKernelFn stream_kernel_seen(int seen, int d, bool part = false) {
+  const bool full = d == G * E;
+  if (seen == SEEN_BITMAP) return stream_kernel_of<G, E, SMP, SEEN_BITMAP>(full, part);
+  if (seen == SEEN_LIST) return stream_kernel_of<G, E, SMP, SEEN_LIST>(full, part);
+  return stream_kernel_of<G, E, SMP, SEEN_CSR>(full, part);
 }
 
 }  // namespace bpr

@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "../../include/bprcore.h"
+#include "bpr_scored_plan.h"
 
 namespace bpr {
 
@@ -103,11 +104,9 @@ inline StreamPlan plan_stream_block(const StreamShape& s) {
 inline bool plan_stream_lds(const StreamShape& s, StreamPlan& p) {
   if (!(s.tune_hot_lds > 0 && s.hot && s.lds_allowed && (s.sampler == BPR_NEG_GIVEN || s.force_seen != FORCE_CSR)))
     return false;
-  // dynamic negatives score their candidates on the LIVE rows: a hot row behind this workgroup's LDS delta is not one
-  // (and k_stream has no LDSHOT instantiation of that sampler)
-  if (s.sampler == BPR_NEG_DYNAMIC) return false;
-  // WARP compares its candidates with the positive on the live rows: refused for the same reason
-  if (s.sampler == BPR_NEG_WARP) return false;
+  // dynamic negatives score their candidates on the LIVE rows, WARP compares them with the positive there: a hot row
+  // behind this workgroup's LDS delta is not one (and k_stream has no LDSHOT instantiation of those samplers)
+  if (sampler_scored(s.sampler)) return false;
   const int G = s.G;
   unsigned block = s.E <= 4 ? 1024 : 512;  // (E >= 8: 64+ registers of rows per lane — two waves per SIMD)
   if (s.tune_lds_block > 0) block = std::min<unsigned>(block, (unsigned)s.tune_lds_block);

@@ -250,12 +250,7 @@ int bpr_train_stream_batched(bpr_ctx* c, const int32_t* users, const int32_t* po
                              int64_t n, int64_t B, int32_t sampler, float adaptive_p,
                              uint64_t seed, uint64_t offset, int64_t max_inflight,
                              float* out_scalars) {
-  if (sampler == BPR_NEG_DYNAMIC)
-    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_stream_batched: dynamic negatives are not implemented for the "
-                                     "batched STREAM kernel (bpr_train_stream runs them with plain SGD)");
-  if (sampler == BPR_NEG_WARP)
-    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_stream_batched: the WARP objective is not implemented for the "
-                                     "batched STREAM kernel (bpr_train_stream runs it with plain SGD)");
+  if (int rc = refuse_scored("bpr_train_stream_batched", sampler)) return rc;
   if (c != nullptr) c->keys_cut = false;
   if (int rc = check_triples(c, "bpr_train_stream_batched", users, pos, n)) return rc;
   if (int rc = check_sampler(c, "bpr_train_stream_batched", sampler, adaptive_p, neg, n)) return rc;

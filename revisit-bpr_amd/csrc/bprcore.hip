@@ -12,7 +12,7 @@
 #include "bpr_host.h"
 #include "bpr_stream_plan.h"
 #include "bpr_refresh_plan.h"
-#include "bpr_dynamic_plan.h"
+#include "bpr_group_shape.h"
 #include "bpr_opt_plan.h"
 
 namespace bpr {
@@ -300,18 +300,6 @@ static int stream_cus(bpr_ctx* c) {
 }
 
 // ---- STREAM ------------------------------------------------------------------------------------
-template <int G, int E, int SMP, int SN>
-static StreamKernelFn stream_kernel_of(bool full, bool part) {
-  if constexpr (SMP == NEG_ADAPTIVE)  // a partial snapshot: the instantiations whose walk can finish inside a bin
-    if (part) return full ? &k_stream<G, E, SMP, SN, true, true> : &k_stream<G, E, SMP, SN, false, true>;
-  return full ? &k_stream<G, E, SMP, SN, true> : &k_stream<G, E, SMP, SN, false>;
-}
-template <int G, int E, int SMP>
-static StreamKernelFn stream_kernel_seen(int seen, bool full, bool part) {
-  if (seen == SEEN_BITMAP) return stream_kernel_of<G, E, SMP, SEEN_BITMAP>(full, part);
-  if (seen == SEEN_LIST) return stream_kernel_of<G, E, SMP, SEEN_LIST>(full, part);
-  return stream_kernel_of<G, E, SMP, SEEN_CSR>(full, part);
-}
 // the plain k_stream instantiation for the ctx's shape (the LDSHOT ones: bpr_hotlds.hip)
 static int stream_kernel(const bpr_ctx* c, int sampler, int seen, bool part, StreamKernelFn* out) {
   if (sampler == NEG_DYNAMIC) return stream_kernel_dynamic(c, seen, out);  // (bpr_dynamic.hip)
@@ -319,10 +307,9 @@ static int stream_kernel(const bpr_ctx* c, int sampler, int seen, bool part, Str
   return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
     using T = decltype(tag);
     constexpr int G = T::G, E = T::E;
-    const bool full = c->d == G * E;
-    *out = sampler == NEG_GIVEN     ? stream_kernel_of<G, E, NEG_GIVEN, SEEN_CSR>(full, false)
-           : sampler == NEG_UNIFORM ? stream_kernel_seen<G, E, NEG_UNIFORM>(seen, full, false)
-                                    : stream_kernel_seen<G, E, NEG_ADAPTIVE>(seen, full, part);
+    *out = sampler == NEG_GIVEN     ? stream_kernel_of<G, E, NEG_GIVEN, SEEN_CSR>(c->d == G * E, false)
+           : sampler == NEG_UNIFORM ? stream_kernel_seen<G, E, NEG_UNIFORM>(seen, c->d)
+                                    : stream_kernel_seen<G, E, NEG_ADAPTIVE>(seen, c->d, part);
     return BPR_OK;
   });
 }
@@ -544,14 +531,19 @@ int check_triples(const bpr_ctx* c, const char* who, const int32_t* users,
   return BPR_OK;
 }
 
+int refuse_scored(const std::string& who, int32_t sampler) {
+  if (!sampler_scored(sampler)) return BPR_OK;
+  return fail(BPR_ERR_UNSUPPORTED, who + (sampler == BPR_NEG_WARP ? ": the WARP objective is" : ": dynamic negatives are") +
+                                       " fused into the plain-SGD STREAM kernel only (bpr_train_stream)");
+}
+
 int check_sampler(const bpr_ctx* c, const char* who, int32_t sampler, float adaptive_p,
                          const int32_t* neg, int64_t B) {
   if (sampler == BPR_NEG_GIVEN) {
     if (neg == nullptr && B > 0) return fail(BPR_ERR_INVALID, std::string(who) + ": neg is NULL");
     return BPR_OK;
   }
-  if (sampler != BPR_NEG_UNIFORM && sampler != BPR_NEG_ADAPTIVE && sampler != BPR_NEG_DYNAMIC &&
-      sampler != BPR_NEG_WARP)
+  if (sampler != BPR_NEG_UNIFORM && sampler != BPR_NEG_ADAPTIVE && !sampler_scored(sampler))
     return fail(BPR_ERR_INVALID, std::string(who) + ": unknown sampler");
   if (c->indptr == nullptr) return fail(BPR_ERR_INVALID, std::string(who) + ": seen CSR not bound");
   if (sampler == BPR_NEG_ADAPTIVE) {
@@ -666,7 +658,7 @@ int bpr_bind_tables(bpr_ctx* c, float* P, int64_t U, float* Q, int64_t I, int32_
   c->keys_cut = false;
   c->U = U; c->I = I; c->d = d;
   c->pad_user = pad_user; c->pad_item = pad_item;
-  const GroupShape g = group_shape(d);  // (bpr_dynamic_plan.h: G = 32 up to d = 128, else 64)
+  const GroupShape g = group_shape(d);  // (bpr_group_shape.h: G = 32 up to d = 128, else 64)
   c->G = g.G;
   c->E = g.E;
   return BPR_OK;
@@ -1044,10 +1036,8 @@ static int train_stream_impl(bpr_ctx* c, const int32_t* users, const int32_t* po
                              int64_t n, int32_t sampler, float adaptive_p, uint64_t seed,
                              uint64_t offset, int64_t max_inflight, float* out_scalars, bool cut,
                              bool acut = false) {
-  if (acut && sampler == BPR_NEG_DYNAMIC)
-    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_stream_acut: dynamic negatives have no snapshot to cut");
-  if (acut && sampler == BPR_NEG_WARP)
-    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_stream_acut: the WARP objective has no snapshot to cut");
+  if (acut)  // (no snapshot to cut)
+    if (int rc = refuse_scored("bpr_train_stream_acut", sampler)) return rc;
   if (c != nullptr) c->acut_call = acut;  // (check_bound folds pending hot deltas for everybody else)
   const int rc0 = check_triples(c, "bpr_train_stream", users, pos, n);
   if (c != nullptr) c->acut_call = false;
@@ -1143,12 +1133,8 @@ int bpr_hot_fold(bpr_ctx* c) {
 int bpr_step(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg, int64_t B,
              int32_t mode, int32_t sampler, float adaptive_p, uint64_t seed, uint64_t offset,
              float* out_logits_pos, float* out_logits_neg, float* out_scalars) {
-  if (sampler == BPR_NEG_DYNAMIC && mode == BPR_MODE_STRICT)
-    return fail(BPR_ERR_UNSUPPORTED, "bpr_step: dynamic negatives in STRICT mode: draw with bpr_sample_dynamic and "
-                                     "pass the picks as BPR_NEG_GIVEN");
-  if (sampler == BPR_NEG_WARP && mode == BPR_MODE_STRICT)
-    return fail(BPR_ERR_UNSUPPORTED, "bpr_step: the WARP objective in STRICT mode: it is fused into the plain-SGD "
-                                     "STREAM kernel only (bpr_train_stream)");
+  if (mode == BPR_MODE_STRICT)  // (dynamic: draw with bpr_sample_dynamic, pass the picks as BPR_NEG_GIVEN)
+    if (int rc = refuse_scored("bpr_step (STRICT mode)", sampler)) return rc;
   if (int rc = check_triples(c, "bpr_step", users, pos, B)) return rc;
   if (int rc = check_sampler(c, "bpr_step", sampler, adaptive_p, neg, B)) return rc;
   if (mode == BPR_MODE_STREAM) {
@@ -1176,12 +1162,8 @@ int bpr_step(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg,
 int bpr_train_strict(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg_scratch,
                      int64_t n, int64_t B, int32_t sampler, float adaptive_p, uint64_t seed,
                      uint64_t offset, int64_t refresh_every, float* out_scalars) {
-  if (sampler == BPR_NEG_DYNAMIC)
-    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_strict: dynamic negatives: draw each batch with bpr_sample_dynamic "
-                                     "and step with BPR_NEG_GIVEN");
-  if (sampler == BPR_NEG_WARP)
-    return fail(BPR_ERR_UNSUPPORTED, "bpr_train_strict: the WARP objective is fused into the plain-SGD STREAM kernel "
-                                     "only (bpr_train_stream)");
+  // (dynamic: draw each batch with bpr_sample_dynamic, step with BPR_NEG_GIVEN)
+  if (int rc = refuse_scored("bpr_train_strict", sampler)) return rc;
   if (int rc = check_triples(c, "bpr_train_strict", users, pos, n)) return rc;
   if (B < 1) return fail(BPR_ERR_INVALID, "bpr_train_strict: B must be >= 1");
   if (int rc = check_sampler(c, "bpr_train_strict", sampler, adaptive_p, neg_scratch, n)) return rc;

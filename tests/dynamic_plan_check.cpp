@@ -1,11 +1,13 @@
-// A stand-alone host program over revisit-bpr_amd/csrc/bpr_dynamic_plan.h and bpr_stream_plan.h:
+// A stand-alone host program over revisit-bpr_amd/csrc/bpr_scored_plan.h, bpr_group_shape.h and bpr_stream_plan.h:
 // tests/test_dynamic_model_cpu.py compiles it with the host compiler under -fsanitize=address,undefined and runs it.
 // It holds the range of M, the argument checks and the grid of the stand-alone kernel, the group shape every width
-// gets, the STREAM plan's refusal of the LDS tier for dynamic negatives — and that the plans of a uniform and an
-// adaptive launch are what they were before the sampler existed.  Exit status 0: all held.
+// gets — the fold-in plan's (bpr_foldin_plan.h) included —, the STREAM plan's refusal of the LDS tier for dynamic
+// negatives — and that the plans of a uniform and an adaptive launch are what they were before the sampler existed.
+// Exit status 0: all held.
 #include <stdio.h>
 
-#include "bpr_dynamic_plan.h"
+#include "bpr_foldin_plan.h"
+#include "bpr_scored_plan.h"
 #include "bpr_stream_plan.h"
 
 using namespace bpr;
@@ -49,6 +51,12 @@ int main() {
     CHECK(g.E == 1 || g.E == 2 || g.E == 4 || g.E == 8 || g.E == 16);
     CHECK(g.E == (g.G == 32 ? 1 : 4) || g.G * g.E / 2 < d);  // the smallest E that holds the row
     CHECK(dynamic_inflight_rows(g.E) * g.E <= 32 && dynamic_inflight_rows(g.E) >= 2);
+    // the fold-in plan's group shape is this one (it used to restate the rule: the value it had is the one held above)
+    const FoldinPlan f = plan_foldin(1000, d);
+    CHECK(f.G == g.G && f.E == g.E && f.G == (d <= 128 ? 32 : 64) && f.groups_per_block == FOLDIN_BLOCK / g.G);
+    int fG = 0, fE = 0;
+    foldin_ge(d, &fG, &fE);
+    CHECK(fG == g.G && fE == g.E);
   }
   CHECK(group_shape(128).E == 4 && group_shape(129).G == 64 && group_shape(256).E == 4 && group_shape(257).E == 8 &&
         group_shape(20).E == 1 && group_shape(33).E == 2 && group_shape(1024).E == 16);
@@ -59,9 +67,10 @@ int main() {
     for (int d : {1, 20, 32, 64, 128, 129, 256, 512, 1024})
       for (int64_t m : {(int64_t)0, (int64_t)1, (int64_t)4, (int64_t)32, (int64_t)33})
         for (int64_t cap : {(int64_t)0, (int64_t)1, (int64_t)7, (int64_t)1 << 20}) {
-          DynamicShape s = {};
-          s.B = B; s.I = 300; s.d = d; s.candidates = m; s.have_users = s.have_out = s.have_seen = true; s.grid_cap = cap;
-          const DynamicPlan p = plan_dynamic(s);
+          ScoredShape s = {};
+          s.kind = BPR_NEG_DYNAMIC;
+          s.B = B; s.I = 300; s.d = d; s.count = m; s.have_users = s.have_neg = s.have_seen = true; s.grid_cap = cap;
+          const ScoredPlan p = plan_scored(s);
           ++plans;
           if (m < 1 || m > 32) {
             CHECK(p.rc == BPR_ERR_INVALID && p.grid == 0);
@@ -77,21 +86,22 @@ int main() {
           CHECK(p.chunks == (int)((m + dynamic_inflight_rows(p.E) - 1) / dynamic_inflight_rows(p.E)));
         }
   {
-    DynamicShape s = {};
-    s.B = 8; s.I = 300; s.d = 32; s.candidates = 4; s.have_users = s.have_out = s.have_seen = true;
-    CHECK(plan_dynamic(s).rc == BPR_OK);
-    DynamicShape t = s; t.have_users = false;
-    CHECK(plan_dynamic(t).rc == BPR_ERR_INVALID);
-    t = s; t.have_out = false;
-    CHECK(plan_dynamic(t).rc == BPR_ERR_INVALID);
+    ScoredShape s = {};
+    s.kind = BPR_NEG_DYNAMIC;
+    s.B = 8; s.I = 300; s.d = 32; s.count = 4; s.have_users = s.have_neg = s.have_seen = true;
+    CHECK(plan_scored(s).rc == BPR_OK);
+    ScoredShape t = s; t.have_users = false;
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
+    t = s; t.have_neg = false;
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.have_seen = false;
-    CHECK(plan_dynamic(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.B = -1;
-    CHECK(plan_dynamic(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.d = 0;
-    CHECK(plan_dynamic(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.d = 1025;
-    CHECK(plan_dynamic(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
   }
   // ---- STREAM: the LDS tier is taken for uniform and adaptive at the timed shape, never for dynamic; the "seen?"
   // structure of a dynamic launch is the uniform launch's

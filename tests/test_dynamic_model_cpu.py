@@ -1,6 +1,6 @@
 """Dynamic negative sampling on the CPU: the numpy model (tests/dynamic_model.py) against the oracle where the two
 must coincide, the statistics of the pick, the share of triples the float32 kernels may decide differently on every
-committed input of tests/test_gpu_dynamic.py, and the launch plan (bpr_dynamic_plan.h, bpr_stream_plan.h) in a program
+committed input of tests/test_gpu_dynamic.py, and the launch plan (bpr_scored_plan.h, bpr_stream_plan.h) in a program
 of its own under the host sanitizers."""
 import subprocess
 from pathlib import Path
@@ -149,7 +149,7 @@ def test_every_triple_of_the_sequential_cases_is_decided(d):
 
 # ---- 4. the plan ----------------------------------------------------------------------------------------------------------
 def test_plan_headers_alone_under_the_host_sanitizers(tmp_path):
-    """bpr_dynamic_plan.h and bpr_stream_plan.h are plain C++: built into a program of its own with
+    """bpr_scored_plan.h and bpr_stream_plan.h are plain C++: built into a program of its own with
     -fsanitize=address,undefined, tests/dynamic_plan_check.cpp runs clean (the range of M, the grid, no LDS tier for
     dynamic negatives, the uniform and adaptive plans unchanged)."""
     exe = tmp_path / "dynamic_plan_check"

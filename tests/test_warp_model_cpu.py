@@ -1,6 +1,6 @@
 """The WARP objective on the CPU: the numpy model (tests/warp_model.py) against the oracle where the two must
 coincide, the statistics of the draw, the share of triples the float32 kernels may decide differently on every
-committed input of tests/test_gpu_warp.py, the structured data generator, and the launch plan (bpr_warp_plan.h,
+committed input of tests/test_gpu_warp.py, the structured data generator, and the launch plan (bpr_scored_plan.h,
 bpr_stream_plan.h) in a program of its own under the host sanitizers."""
 import math
 import subprocess
@@ -207,7 +207,7 @@ def test_generate_structured():
 
 # ---- 5. the plan ----------------------------------------------------------------------------------------------------------
 def test_plan_headers_alone_under_the_host_sanitizers(tmp_path):
-    """bpr_warp_plan.h and bpr_stream_plan.h are plain C++: built into a program of its own with
+    """bpr_scored_plan.h and bpr_stream_plan.h are plain C++: built into a program of its own with
     -fsanitize=address,undefined, tests/warp_plan_check.cpp runs clean."""
     exe = tmp_path / "warp_plan_check"
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",

@@ -1,4 +1,4 @@
-// A stand-alone host program over revisit-bpr_amd/csrc/bpr_warp_plan.h and bpr_stream_plan.h:
+// A stand-alone host program over revisit-bpr_amd/csrc/bpr_scored_plan.h and bpr_stream_plan.h:
 // tests/test_warp_model_cpu.py compiles it with the host compiler under -fsanitize=address,undefined and runs it.
 // It holds the range of max_sampled and of the margin, the argument checks and the grid of the stand-alone kernel,
 // the STREAM plan of a WARP launch — the uniform sampler's "seen?" structures, never the LDS tier — and that the
@@ -9,8 +9,8 @@
 
 #include <limits>
 
+#include "bpr_scored_plan.h"
 #include "bpr_stream_plan.h"
-#include "bpr_warp_plan.h"
 
 using namespace bpr;
 
@@ -39,9 +39,10 @@ static bool same(const StreamPlan& a, const StreamPlan& b) {
          a.tail1 == b.tail1 && a.tail2 == b.tail2;
 }
 
-static WarpShape good() {
-  WarpShape s = {};
-  s.B = 8; s.I = 300; s.d = 32; s.max_sampled = 10; s.margin = 1.0f;
+static ScoredShape good() {
+  ScoredShape s = {};
+  s.kind = BPR_NEG_WARP;
+  s.B = 8; s.I = 300; s.d = 32; s.count = 10; s.margin = 1.0f;
   s.have_users = s.have_pos = s.have_neg = s.have_tries = s.have_seen = true;
   return s;
 }
@@ -50,6 +51,8 @@ int main() {
   static_assert(BPR_NEG_WARP == 4, "the ABI's number of the kind");
   static_assert(WARP_MIN == 1 && WARP_MAX == 32 && WARP_DEFAULT == 10, "the range of max_sampled and its default");
   CHECK(WARP_DEFAULT_MARGIN == 1.0f);
+  CHECK(sampler_scored(BPR_NEG_DYNAMIC) && sampler_scored(BPR_NEG_WARP) && !sampler_scored(BPR_NEG_GIVEN) &&
+        !sampler_scored(BPR_NEG_UNIFORM) && !sampler_scored(BPR_NEG_ADAPTIVE) && !sampler_scored(5) && !sampler_scored(-1));
   // ---- the ranges
   for (int64_t m : {(int64_t)-5, (int64_t)0, (int64_t)33, (int64_t)64, (int64_t)1 << 40}) CHECK(!warp_max_sampled_ok(m));
   for (int64_t m = 1; m <= 32; ++m) CHECK(warp_max_sampled_ok(m));
@@ -63,9 +66,9 @@ int main() {
     for (int d : {1, 20, 32, 64, 128, 129, 256, 512, 1024})
       for (int64_t m : {(int64_t)0, (int64_t)1, (int64_t)10, (int64_t)32, (int64_t)33})
         for (int64_t cap : {(int64_t)0, (int64_t)1, (int64_t)7, (int64_t)1 << 20}) {
-          WarpShape s = good();
-          s.B = B; s.d = d; s.max_sampled = m; s.grid_cap = cap;
-          const WarpPlan p = plan_warp(s);
+          ScoredShape s = good();
+          s.B = B; s.d = d; s.count = m; s.grid_cap = cap;
+          const ScoredPlan p = plan_scored(s);
           ++plans;
           if (m < 1 || m > 32) {
             CHECK(p.rc == BPR_ERR_INVALID && p.grid == 0);
@@ -81,27 +84,27 @@ int main() {
           CHECK(p.chunks == (int)((m + dynamic_inflight_rows(p.E) - 1) / dynamic_inflight_rows(p.E)));
         }
   {
-    const WarpShape s = good();
-    CHECK(plan_warp(s).rc == BPR_OK);
-    WarpShape t = s; t.have_users = false;
-    CHECK(plan_warp(t).rc == BPR_ERR_INVALID);
+    const ScoredShape s = good();
+    CHECK(plan_scored(s).rc == BPR_OK);
+    ScoredShape t = s; t.have_users = false;
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.have_pos = false;
-    CHECK(plan_warp(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.have_neg = false;
-    CHECK(plan_warp(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.have_tries = false;
-    CHECK(plan_warp(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.have_seen = false;
-    CHECK(plan_warp(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.B = -1;
-    CHECK(plan_warp(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.d = 0;
-    CHECK(plan_warp(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     t = s; t.d = 1025;
-    CHECK(plan_warp(t).rc == BPR_ERR_INVALID);
+    CHECK(plan_scored(t).rc == BPR_ERR_INVALID);
     for (float m : {0.f, -1.f, inf, nan}) {
       t = s; t.margin = m;
-      CHECK(plan_warp(t).rc == BPR_ERR_INVALID && plan_warp(t).grid == 0);
+      CHECK(plan_scored(t).rc == BPR_ERR_INVALID && plan_scored(t).grid == 0);
     }
   }
   // ---- STREAM: the LDS tier is taken for uniform and adaptive at the timed shape, never for dynamic or WARP; the
