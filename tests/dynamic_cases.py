@@ -7,12 +7,38 @@ import dynamic_model as dm
 
 SEED = 0x9E3779B97F4A7C15  # (tests/counter64_cases.py: high word non-zero, top bit set)
 MS = (2, 4, 8, 16, 32)
-DS = (20, 32, 64, 128, 256)  # every group layout up to d = 256 (E = 1, 1, 2, 4 at G = 32; 4 at G = 64), one d % 4 != 0
+# every group layout of the library's widths 1 .. 1024, each at a full width and at a partial one (the last lanes'
+# entries past d): G = 32 with E = 1 (20: d % 4 != 0; 32), 2 (40; 64) and 4 (128); G = 64 with E = 4 (256), 8 (300; 512)
+# and 16 (1000; 1024).  The rows of a draw are scored in chunks of inflight_rows(d) = 8, 4 and 2 rows at E <= 4, 8, 16.
+DS = (20, 32, 40, 64, 128, 256, 300, 512, 1000, 1024)
 PICK_U, PICK_I, PICK_N, PICK_SEEN = 64, 300, 2048, 30
-SEQ_DS = (32, 64, 128, 256)
+SEQ_DS = (32, 64, 128, 256, 300, 512, 1000, 1024)
 SEQ_U, SEQ_I, SEQ_N, SEQ_LR, SEQ_REG, SEQ_M = 60, 90, 400, 0.05, (0.01, 0.02, 0.03), 4
 # seeds of the sequential problems, chosen on the CPU so that every one of the 400 triples is decided
-SEQ_SEED = {32: 5, 64: 5, 128: 5, 256: 5}
+SEQ_SEED = {32: 5, 64: 5, 128: 5, 256: 5, 300: 1, 512: 1, 1000: 6, 1024: 4}
+# SEQ_M = 4 is ONE chunk at E = 8: the same limit at (d, M) with M over two chunks and more (8 = 4 + 4, 10 = 4 + 4 + 2),
+# seeds chosen the same way
+SEQ_CHUNKED = {(300, 8): 1, (512, 10): 2}
+# the stand-alone kernel's grid: DYNAMIC_MAX_GRID = 2,048 blocks of 256 threads (bpr_scored_plan.h), a group of G lanes
+# per draw, so ONE pass of its grid-stride loop is 2048 * 256 / 64 = 8,192 draws at G = 64 and 16,384 at G = 32.
+# GRID_N[d]: two full passes and a ragged third at d = 512; one pass and an ODD tail at d = 64, where the last wave's
+# second group has no draw.
+GRID_PASS = {512: 8192, 64: 16384}
+GRID_N = {512: 2 * 8192 + 5, 64: 16384 + 3}
+GRID_M, GRID_WINDOW, GRID_SLICE = 8, 600, 4096
+
+
+def group_shape(d):
+    """(G, E) of width d: bpr_group_shape.h."""
+    G = 32 if d <= 128 else 64
+    per = (d + G - 1) // G
+    return G, ((1 if per <= 1 else 2 if per <= 2 else 4) if G == 32 else (4 if per <= 4 else 8 if per <= 8 else 16))
+
+
+def inflight_rows(d):
+    """Candidate rows of one chunk at width d: dynamic_inflight_rows(E) of bpr_scored_plan.h."""
+    E = group_shape(d)[1]
+    return 8 if E <= 4 else 4 if E <= 8 else 2
 
 
 def csr(rows):
@@ -76,24 +102,55 @@ def pick_model(M, d, bias):
     return _cache[key]
 
 
-def seq_problem(d):
-    """test_stream_sequential_limit_equals_b1_sgd's shape at width d."""
-    key = ("seq", d)
+def seq_problem(d, M=SEQ_M):
+    """test_stream_sequential_limit_equals_b1_sgd's shape at width d (M: which committed seed)."""
+    key = ("seq", d, M)
     if key not in _cache:
-        pr = problem(SEQ_U, SEQ_I, d, 30, seed=SEQ_SEED[d], n=SEQ_N, scale=8.0 / d ** 0.5 * 0.25)
+        seed = SEQ_SEED[d] if M == SEQ_M else SEQ_CHUNKED[(d, M)]
+        pr = problem(SEQ_U, SEQ_I, d, 30, seed=seed, n=SEQ_N, scale=8.0 / d ** 0.5 * 0.25)
         _cache[key] = pr
     return _cache[key]
 
 
-def seq_model(d):
+def seq_model(d, M=SEQ_M):
     """The sequential trainer on a copy of the problem: (P, Q, negatives, decided, scalars)."""
-    key = ("seq_model", d)
+    key = ("seq_model", d, M)
     if key not in _cache:
-        pr = seq_problem(d)
+        pr = seq_problem(d, M)
         P, Q = pr["P"].copy(), pr["Q"].copy()
-        neg, dec, sc = dm.train_sequential(P, Q, None, pr["indptr"], pr["indices"], pr["users"], pr["pos"], SEQ_M,
+        neg, dec, sc = dm.train_sequential(P, Q, None, pr["indptr"], pr["indices"], pr["users"], pr["pos"], M,
                                            SEQ_LR, SEQ_REG, seed=9, offset=100)
         _cache[key] = (P, Q, neg, dec, sc)
+    return _cache[key]
+
+
+def grid_windows(d):
+    """The two stretches of a GRID_N[d] launch that are compared with the model: GRID_WINDOW draws across the first
+    pass boundary of the grid-stride loop, and the last GRID_WINDOW draws (the ragged tail)."""
+    n, edge = GRID_N[d], GRID_PASS[d]
+    return ((edge - GRID_WINDOW // 2, min(edge + GRID_WINDOW // 2, n)), (n - GRID_WINDOW, n))
+
+
+def grid_problem(d):
+    """The pick tables of width d (with the bias) under GRID_N[d] users."""
+    key = ("grid", d)
+    if key not in _cache:
+        pr = dict(pick_problem(d, True))
+        pr["users"] = np.random.default_rng(78).integers(1, PICK_U, size=GRID_N[d]).astype(np.int32)
+        _cache[key] = pr
+    return _cache[key]
+
+
+def grid_model(d, window):
+    """dynamic_model.sample (M = GRID_M) of the draws window = (lo, hi) of the grid case, at offset = lo."""
+    key = ("grid_model", d, window)
+    if key not in _cache:
+        pr = grid_problem(d)
+        lo, hi = window
+        out = dm.sample(pr["P"], pr["Q"], pr["b"], pr["indptr"], pr["indices"], pr["users"][lo:hi], GRID_M, SEED, lo)
+        for a in out:
+            a.setflags(write=False)
+        _cache[key] = out
     return _cache[key]
 
 

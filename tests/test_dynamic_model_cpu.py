@@ -139,12 +139,64 @@ def test_undecided_share_of_the_gpu_pick_cases(d, bias):
 
 @pytest.mark.parametrize("d", dc.SEQ_DS)
 def test_every_triple_of_the_sequential_cases_is_decided(d):
-    P, Q, neg, dec, sc = dc.seq_model(d)
+    check_sequential_case_is_decided(d, dc.SEQ_M)
+
+
+@pytest.mark.parametrize("d,M", sorted(dc.SEQ_CHUNKED))
+def test_every_triple_of_the_chunked_sequential_cases_is_decided(d, M):
+    check_sequential_case_is_decided(d, M)
+
+
+def check_sequential_case_is_decided(d, M):
+    P, Q, neg, dec, sc = dc.seq_model(d, M)
     assert dec.all(), int((~dec).sum())
     assert np.isfinite(P).all() and np.isfinite(Q).all() and sc[3] == dc.SEQ_N
-    pr = dc.seq_problem(d)
+    pr = dc.seq_problem(d, M)
     for u, j in zip(pr["users"], neg):
         assert j != 0 and j not in pr["indices"][pr["indptr"][u]:pr["indptr"][u + 1]]
+
+
+def test_the_case_files_cover_every_group_layout_at_a_full_and_a_partial_width():
+    """(G, E) and the rows of a chunk as tests/dynamic_cases.py mirrors them from bpr_group_shape.h and
+    bpr_scored_plan.h, and what DS, SEQ_DS and SEQ_CHUNKED promise about them."""
+    assert [dc.group_shape(d) for d in (1, 32, 33, 64, 65, 128, 129, 256, 257, 512, 513, 1024)] == [
+        (32, 1), (32, 1), (32, 2), (32, 2), (32, 4), (32, 4), (64, 4), (64, 4), (64, 8), (64, 8), (64, 16), (64, 16)]
+    assert [dc.inflight_rows(d) for d in (32, 64, 128, 256, 257, 512, 513, 1024)] == [8, 8, 8, 8, 4, 4, 2, 2]
+    layouts = {(32, 1), (32, 2), (32, 4), (64, 4), (64, 8), (64, 16)}
+    for ds in (dc.DS, dc.SEQ_DS):
+        assert {dc.group_shape(d) for d in ds} == layouts
+    for G, E in layouts - {(32, 4), (64, 4)}:  # full: every lane's E entries inside the row; partial: some past d
+        assert any(dc.group_shape(d) == (G, E) and d == G * E for d in dc.DS)
+        assert any(dc.group_shape(d) == (G, E) and d < G * E for d in dc.DS)
+    for d, M in dc.SEQ_CHUNKED:
+        assert M > dc.inflight_rows(d) == 4
+    for d, n in dc.GRID_N.items():
+        G = dc.group_shape(d)[0]
+        assert dc.GRID_PASS[d] == 2048 * 256 // G < n and n % (64 // G) == 64 // G - 1
+
+
+@pytest.mark.parametrize("d", sorted(dc.GRID_N))
+def test_undecided_share_of_the_gpu_grid_windows(d):
+    n = dc.GRID_N[d]
+    (lo, hi), (tlo, thi) = dc.grid_windows(d)
+    assert lo < dc.GRID_PASS[d] < hi <= n and thi == n and thi - tlo == dc.GRID_WINDOW
+    for w in dc.grid_windows(d):
+        _, _, dec, _, acc = dc.grid_model(d, w)
+        print(f"d {d} draws {w}: undecided {1 - dec.mean():.4%}")
+        assert 1.0 - dec.mean() <= 0.01 and (acc == dc.GRID_M).all()
+
+
+def test_the_twins_of_the_ties_case_fall_into_different_chunks():
+    """test_gpu_dynamic's identical-rows case (14 items, 2 seen, M = 8, seed 41) at its wide widths: the accepted lists
+    hold both twins 3 and 9 in different chunks of 4 and of 2 rows, in either order, often enough for its assertions."""
+    for d in (512, 1024):
+        pr = dc.problem(8, 14, d, 2, seed=13, n=1024)
+        lists = dm.accepted_lists(pr["indptr"], pr["indices"], 14, pr["users"], 8, 41, 0)
+        C = dc.inflight_rows(d)
+        cross = [c.index(3) < c.index(9) for c in lists if 3 in c and 9 in c and c.index(3) // C != c.index(9) // C]
+        same = [c for c in lists if 3 in c and 9 in c and c.index(3) // C == c.index(9) // C]
+        print(f"chunks of {C}: twins in different chunks {len(cross)} (3 first {sum(cross)}), in one chunk {len(same)}")
+        assert len(cross) >= 20 and 0 < sum(cross) < len(cross) and same
 
 
 # ---- 4. the plan ----------------------------------------------------------------------------------------------------------

@@ -73,20 +73,26 @@ def test_picks_and_scores_match_the_model(d, bias):
 
 
 # ---- 3. every "seen?" structure of the fused kernel ------------------------------------------------------------------------
-@pytest.mark.parametrize("seen", ["", "csr", "bitmap", "list", "list-overflow"])
-def test_every_seen_structure_gives_the_stand_alone_picks(seen, monkeypatch):
-    d, U, I, n, per_user = 256, 60, 90, 400, 30
+SEEN_STRUCTURES = ["", "csr", "bitmap", "list", "list-overflow", "heavy"]
+
+
+def check_seen_structure(seen, d, monkeypatch):
+    U, I, n, per_user = 60, 90, 400, 30
     if seen == "list-overflow":  # > 512 seen items per user: the staged list does not hold them
         I, per_user, seen = 1500, 700, "list"
-    if seen:
+    if seen and seen != "heavy":
         monkeypatch.setenv("BPR_SEEN", seen)
     pr = dc.problem(U, I, d, per_user, seed=5, n=n)
     e = engine(pr, False)
+    if seen == "heavy":
+        e.set_heavy_users(4, 0)  # more than 4 seen items = heavy: every user's bitmap is staged from the table
     e.set_optimizer(kind=0, lr=0.0)
     e.set_dynamic(4)
     users, pos = dev(pr["users"]), dev(pr["pos"])
     negs = torch.zeros(n, dtype=torch.int32, device="cuda")
     e.train_stream(users, pos, sampler=NEG_DYNAMIC, neg=negs, seed=9, offset=100)
+    if seen == "heavy":
+        assert e.heavy_users()[0] > 0
     want = e.sample_dynamic(users, 4, seed=9, offset=100)
     assert torch.equal(negs, want)
     got = negs.cpu().numpy()
@@ -94,9 +100,28 @@ def test_every_seen_structure_gives_the_stand_alone_picks(seen, monkeypatch):
         assert j != 0 and j not in pr["indices"][pr["indptr"][u]:pr["indptr"][u + 1]]
 
 
+@pytest.mark.parametrize("seen", SEEN_STRUCTURES)
+def test_every_seen_structure_gives_the_stand_alone_picks(seen, monkeypatch):
+    check_seen_structure(seen, 256, monkeypatch)
+
+
+@pytest.mark.parametrize("seen", SEEN_STRUCTURES)
+def test_every_seen_structure_gives_the_stand_alone_picks_at_sixteen_entries_a_lane(seen, monkeypatch):
+    check_seen_structure(seen, 1000, monkeypatch)  # (64, 16), partial: the 4 candidates are two chunks of two rows
+
+
 # ---- 4. edges -------------------------------------------------------------------------------------------------------------
+# (the edge cases at d = 32 keep their names; the same bodies run again at the widths whose chunks are 4 and 2 rows)
 def test_a_user_with_one_unseen_item_and_a_user_with_none():
-    ed = dc.nearly_all_seen()
+    check_one_unseen_and_none(32)
+
+
+def test_a_user_with_one_unseen_item_and_a_user_with_none_at_sixteen_entries_a_lane():
+    check_one_unseen_and_none(1024)
+
+
+def check_one_unseen_and_none(d):
+    ed = dc.nearly_all_seen(d=d)
     _, _, _, _, acc = dm.sample(ed["P"], ed["Q"], None, ed["indptr"], ed["indices"], ed["users"], 8, dc.SEED, 0)
     assert (acc == 0).any() and ((acc > 0) & (acc < 8)).any()  # "none: the rank pick" and "fewer than M" both occur
     e = engine(ed, False)
@@ -123,7 +148,23 @@ def test_a_zero_user_row_is_the_uniform_sampler():
 
 
 def test_identical_rows_keep_the_earlier_candidate_and_nan_rows_never_win():
-    U, I, d, n, M = 8, 14, 32, 1024, 8
+    check_identical_rows_and_nan_rows(32)
+
+
+@pytest.mark.parametrize("d", [512, 1024])
+def test_identical_rows_in_different_chunks_keep_the_earlier_candidate(d):
+    """The M = 8 candidates are two chunks of four rows at d = 512 and four of two at d = 1024: the twins sit in
+    different chunks in some triples, in either order, and in the same chunk in others."""
+    both, cross, cross_first_x = check_identical_rows_and_nan_rows(d)
+    print(f"d {d}: both twins in {both} triples, in different chunks of {dc.inflight_rows(d)} rows in {cross}, "
+          f"x first in {cross_first_x} of those")
+    assert dc.inflight_rows(d) < 8
+    assert cross >= 20 and 0 < cross_first_x < cross and cross < both
+
+
+def check_identical_rows_and_nan_rows(d):
+    U, I, n, M = 8, 14, 1024, 8
+    C = dc.inflight_rows(d)
     pr = dc.problem(U, I, d, 2, seed=13, n=n)
     Q = pr["Q"]
     x, y, bad, top = 3, 9, 6, 5.0
@@ -136,7 +177,7 @@ def test_identical_rows_keep_the_earlier_candidate_and_nan_rows_never_win():
     Q[0] = 0
     e = engine(pr, False)
     got = e.sample_dynamic(dev(pr["users"]), M, seed=41, offset=0).cpu().numpy()
-    both = first_x = 0
+    both = first_x = cross = cross_first_x = 0
     for b, u in enumerate(pr["users"]):
         r = dm.pick(41, b, int(u), M, pr["P"], Q, None, pr["indptr"], pr["indices"])
         c = r["cands"]
@@ -145,6 +186,9 @@ def test_identical_rows_keep_the_earlier_candidate_and_nan_rows_never_win():
         if x in c and y in c:
             both += 1
             first_x += c.index(x) < c.index(y)
+            if c.index(x) // C != c.index(y) // C:  # the first of each twin: in different chunks of C rows
+                cross += 1
+                cross_first_x += c.index(x) < c.index(y)
             assert got[b] == (x if c.index(x) < c.index(y) else y), (b, c, got[b])
         if r["decided"]:
             assert got[b] == r["item"]
@@ -155,10 +199,11 @@ def test_identical_rows_keep_the_earlier_candidate_and_nan_rows_never_win():
     pr2["Q"][5, 0] = np.nan
     e2 = engine(pr2, False)
     assert (e2.sample_dynamic(dev(pr2["users"]), 4, seed=2, offset=0) == 5).all()
+    return both, cross, cross_first_x
 
 
 # ---- 5. the fused kernel on static tables ------------------------------------------------------------------------------
-@pytest.mark.parametrize("d", [32, 128, 256])
+@pytest.mark.parametrize("d", [32, 128, 256, 512, 1000])
 def test_fused_picks_equal_the_stand_alone_kernel_on_static_tables(d):
     pr = dc.pick_problem(d, True)
     e = engine(pr, True, reg=(0.01, 0.02, 0.03))
@@ -187,22 +232,80 @@ def test_fused_picks_equal_the_stand_alone_kernel_on_static_tables(d):
 # ---- 6. the sequential limit ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("d", dc.SEQ_DS)
 def test_sequential_limit_equals_the_sequential_model(d):
-    pr = dc.seq_problem(d)
-    Po, Qo, neg_o, dec, sco = dc.seq_model(d)
+    check_sequential_limit(d, dc.SEQ_M)
+
+
+@pytest.mark.parametrize("d,M", sorted(dc.SEQ_CHUNKED))
+def test_sequential_limit_with_candidates_over_several_chunks_of_four_rows(d, M):
+    assert M > dc.inflight_rows(d) == 4
+    check_sequential_limit(d, M)
+
+
+def check_sequential_limit(d, M):
+    pr = dc.seq_problem(d, M)
+    Po, Qo, neg_o, dec, sco = dc.seq_model(d, M)
     assert dec.all()
     e = engine(pr, False, reg=dc.SEQ_REG)
     e.set_optimizer(kind=0, lr=dc.SEQ_LR)
-    e.set_dynamic(dc.SEQ_M)
+    e.set_dynamic(M)
     negs = torch.zeros(dc.SEQ_N, dtype=torch.int32, device="cuda")
     sc = torch.zeros(4, device="cuda")
     e.train_stream(dev(pr["users"]), dev(pr["pos"]), sampler=NEG_DYNAMIC, neg=negs, seed=9, offset=100,
                    max_inflight=1, scalars=sc)
     got = negs.cpu().numpy()
     assert np.array_equal(got, neg_o), np.nonzero(got != neg_o)[0][:5]
-    print(f"d {d}: max error P {maxerr(e.P.cpu().numpy(), Po):.3g} Q {maxerr(e.Q.cpu().numpy(), Qo):.3g}")
+    print(f"d {d} M {M}: max error P {maxerr(e.P.cpu().numpy(), Po):.3g} Q {maxerr(e.Q.cpu().numpy(), Qo):.3g}")
     assert close(e.P.cpu().numpy(), Po, 1e-5), maxerr(e.P.cpu().numpy(), Po)
     assert close(e.Q.cpu().numpy(), Qo, 1e-5), maxerr(e.Q.cpu().numpy(), Qo)
     assert close(sc.cpu().numpy()[:3], sco[:3], 1e-4)
+
+
+# ---- 6a. the stand-alone kernel's grid-stride passes and its ragged last wave --------------------------------------------
+UNWRITTEN, UNWRITTEN_SCORE = -7, -12345.0
+
+
+def launch_over_sentinels(e, users, M, offset):
+    """bpr_sample_dynamic into buffers filled with sentinels: (items, scores), every element of which was written."""
+    from revisit_bpr import native
+
+    n = users.numel()
+    neg = torch.full((n,), UNWRITTEN, dtype=torch.int32, device="cuda")
+    sc = torch.full((n,), UNWRITTEN_SCORE, dtype=torch.float32, device="cuda")
+    e._sync_stream()
+    native.check(e._lib.bpr_sample_dynamic(e._ctx, users.data_ptr(), n, M, dc.SEED, offset, neg.data_ptr(),
+                                           sc.data_ptr()))
+    assert (neg != UNWRITTEN).all() and (sc != UNWRITTEN_SCORE).all()
+    return neg, sc
+
+
+@pytest.mark.parametrize("d", sorted(dc.GRID_N))
+def test_a_launch_past_the_grid_is_its_slices_the_model_and_at_one_candidate_the_oracle(d):
+    """More draws than one pass of k_sample_scored's grid (dynamic_cases.GRID_N: 8,192 draws a pass at G = 64, 16,384
+    at G = 32) with a ragged last wave — at d = 64 an odd tail, the wave's second group without a draw."""
+    n, G = dc.GRID_N[d], dc.group_shape(d)[0]
+    assert n > dc.GRID_PASS[d] == 2048 * 256 // G and n % (64 // G) == 64 // G - 1 and n % (256 // G) != 0
+    pr = dc.grid_problem(d)
+    e = engine(pr, True)
+    users = dev(pr["users"])
+    # one candidate: the uniform sampler's draw, all n of them
+    one, _ = launch_over_sentinels(e, users, 1, 0)
+    assert np.array_equal(one.cpu().numpy(),
+                          oracle.sample_uniform(pr["indptr"], pr["indices"], pr["I"], pr["users"], dc.SEED, 0))
+    # the whole launch is the launches of its slices, each at its own offset
+    neg, sc = launch_over_sentinels(e, users, dc.GRID_M, 0)
+    for lo in range(0, n, dc.GRID_SLICE):
+        part, psc = e.sample_dynamic(users[lo:lo + dc.GRID_SLICE], dc.GRID_M, seed=dc.SEED, offset=lo,
+                                     return_scores=True)
+        assert torch.equal(neg[lo:lo + dc.GRID_SLICE], part) and torch.equal(sc[lo:lo + dc.GRID_SLICE], psc), lo
+    # and the model's draws across the pass boundary and at the tail
+    got, gsc = neg.cpu().numpy(), sc.cpu().numpy().astype(np.float64)
+    for lo, hi in dc.grid_windows(d):
+        items, msc, dec, mg, acc = dc.grid_model(d, (lo, hi))
+        print(f"d {d} draws {lo} .. {hi}: undecided {1 - dec.mean():.4%}, agree {np.mean(got[lo:hi] == items):.4%}")
+        assert 1.0 - dec.mean() <= 0.01 and (acc == dc.GRID_M).all()
+        bad = np.nonzero(dec & (got[lo:hi] != items))[0]
+        assert bad.size == 0, (lo, bad[:5], got[lo:hi][bad[:5]], items[bad[:5]])
+        assert (np.abs(gsc[lo:hi][dec] - msc[dec]) <= mg[dec]).all()
 
 
 # ---- 7. the Python surface --------------------------------------------------------------------------------------------------

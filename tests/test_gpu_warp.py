@@ -84,9 +84,21 @@ def fused_negatives(e, pr, N, seed, offset, margin=wc.MARGIN, scalars=None, **kw
     return negs
 
 
-@pytest.mark.parametrize("seen", ["", "csr", "bitmap", "list", "list-overflow", "heavy"])
+SEEN_STRUCTURES = ["", "csr", "bitmap", "list", "list-overflow", "heavy"]
+
+
+@pytest.mark.parametrize("seen", SEEN_STRUCTURES)
 def test_every_seen_structure_gives_the_stand_alone_negatives(seen, monkeypatch):
-    d, U, I, n, per_user = 256, 60, 90, 400, 30
+    check_seen_structure(seen, 256, monkeypatch)
+
+
+@pytest.mark.parametrize("seen", SEEN_STRUCTURES)
+def test_every_seen_structure_gives_the_stand_alone_negatives_at_sixteen_entries_a_lane(seen, monkeypatch):
+    check_seen_structure(seen, 1000, monkeypatch)  # (64, 16), partial: the 10 candidates are five chunks of two rows
+
+
+def check_seen_structure(seen, d, monkeypatch):
+    U, I, n, per_user = 60, 90, 400, 30
     if seen == "list-overflow":  # > 512 seen items per user: the staged list does not hold them
         I, per_user = 1500, 700
     if seen and seen != "heavy":
@@ -115,8 +127,17 @@ def test_the_staged_sorted_list_of_a_large_catalogue():
     assert np.array_equal(negs.cpu().numpy(), got[0])
 
 
+# (the edge cases at d = 32 keep their names; the same bodies run again at the widths whose chunks are 4 and 2 rows)
 def test_users_with_one_unseen_item_with_none_and_with_fewer_than_n():
-    ed = wc.one_unseen()
+    check_one_unseen_none_and_fewer_than_n(32)
+
+
+def test_users_with_one_unseen_item_with_none_and_with_fewer_than_n_at_sixteen_entries_a_lane():
+    check_one_unseen_none_and_fewer_than_n(1024)
+
+
+def check_one_unseen_none_and_fewer_than_n(d):
+    ed = wc.one_unseen(d=d)
     e = engine(ed, False)
     neg, tries, _, _ = gpu_sample(e, ed, 8)
     assert (neg == ed["unseen"]).all() and (tries == 1).all()
@@ -136,26 +157,29 @@ def test_users_with_one_unseen_item_with_none_and_with_fewer_than_n():
 
 
 # ---- 3. order: the FIRST violator ------------------------------------------------------------------------------------------
-def order_problem(n=2048, I=41, d=32):
-    """Score of item a = a for user 1, who has seen item 1; the positive is item 38 and the margin 1.5, so items
-    37 .. 40 violate: a tenth of the candidates, no score near a bound."""
-    P = np.zeros((2, d), np.float32)
-    P[1, 0] = 1.0
-    Q = np.zeros((I, d), np.float32)
-    Q[1:, 0] = np.arange(1, I)
-    indptr, indices = np.array([0, 0, 1], np.int64), np.array([1], np.int32)
-    return dict(P=P, Q=Q, b=None, indptr=indptr, indices=indices, I=I, d=d, users=np.full(n, 1, np.int32),
-                pos=np.full(n, 38, np.int32))
+order_problem = wc.order_problem
 
 
 def test_the_first_violator_wins_not_the_best_and_chunks_past_it_do_not_matter():
-    pr = order_problem()
+    check_first_violator(32)
+
+
+@pytest.mark.parametrize("d", [512, 1024])
+def test_the_first_violator_wins_at_every_place_of_a_chunk_of_four_and_of_two_rows(d):
+    assert dc.inflight_rows(d) == (4 if d == 512 else 2)
+    check_first_violator(d)
+
+
+def check_first_violator(d):
+    pr = order_problem(d=d)
     e = engine(pr, False)
-    lists = dc.dm.accepted_lists(pr["indptr"], pr["indices"], pr["I"], pr["users"], 32, 5, 0)
+    lists = wc.order_lists()
     for N in (10, 32):
         model = wm.sample(pr["P"], pr["Q"], None, pr["indptr"], pr["indices"], pr["users"], pr["pos"], N, 1.5, 5, 0,
                           lists=lists)
         assert not model[4].any()
+        # the violator at every place k = 1 .. N, and nowhere: every place of every chunk is a stopping point
+        assert np.array_equal(np.unique(model[1]), np.arange(N + 1))
         neg, tries, _, _ = gpu_sample(e, pr, N, margin=1.5, seed=5)
         assert np.array_equal(neg, model[0]) and np.array_equal(tries, model[1])
         later_better = [b for b in range(len(neg)) if neg[b] > 0 and max(lists[b][:N]) > neg[b]]
@@ -168,7 +192,16 @@ def test_the_first_violator_wins_not_the_best_and_chunks_past_it_do_not_matter()
 
 
 def test_a_nan_candidate_never_violates_and_a_nan_positive_skips():
-    pr = order_problem(n=512, I=12)
+    check_nan_candidate_and_nan_positive(32)
+
+
+@pytest.mark.parametrize("d", [512, 1024])
+def test_a_nan_candidate_never_violates_in_chunks_of_four_and_of_two_rows(d):
+    check_nan_candidate_and_nan_positive(d)
+
+
+def check_nan_candidate_and_nan_positive(d):
+    pr = order_problem(n=512, I=12, d=d)
     pr["pos"][:] = 2  # every item but 1 violates at margin 1.5
     pr["Q"][5, 1] = np.nan  # (user 1's factor 1 is zero: 0 * NaN = NaN)
     e = engine(pr, False)
@@ -185,8 +218,17 @@ def test_a_nan_candidate_never_violates_and_a_nan_positive_skips():
 # ---- 4. skipped triples write nothing ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("hot", [False, True])
 def test_skipped_triples_write_nothing_and_the_scalars_are_the_models(hot):
-    pr = wc.skip_problem()
-    Po, Qo, bo, neg_o, tries_o, und, sco = wc.skip_model()
+    check_skipped_triples(hot, 32)
+
+
+@pytest.mark.parametrize("hot", [False, True])
+def test_skipped_triples_write_nothing_at_sixteen_entries_a_lane(hot):
+    check_skipped_triples(hot, 640)  # (64, 16), partial: the 10 candidates are five chunks of two rows
+
+
+def check_skipped_triples(hot, d):
+    pr = wc.skip_problem(d)
+    Po, Qo, bo, neg_o, tries_o, und, sco = wc.skip_model(10, d)
     assert not und.any()
     e = engine(pr, True, reg=wc.SEQ_REG)
     if hot:  # the hot block in front of the rows, the skipped users' positive among its items
@@ -224,7 +266,7 @@ def test_skipped_triples_write_nothing_and_the_scalars_are_the_models(hot):
 
 
 # ---- 5. the fused kernel on static tables ------------------------------------------------------------------------------
-@pytest.mark.parametrize("d", [32, 128, 256])
+@pytest.mark.parametrize("d", [32, 128, 256, 512, 1000])
 def test_fused_negatives_equal_the_stand_alone_kernel_on_static_tables(d):
     pr = wc.pick_problem(d, True)
     e = engine(pr, True, reg=(0.01, 0.02, 0.03))
@@ -266,23 +308,76 @@ def test_one_try_on_all_violating_users_is_the_uniform_launch():
 # ---- 6. the sequential limit ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("d", wc.SEQ_DS)
 def test_sequential_limit_equals_the_sequential_model(d):
-    pr = wc.seq_problem(d)
-    Po, Qo, neg_o, tries_o, und, sco = wc.seq_model(d)
+    check_sequential_limit(d, wc.SEQ_MAX)
+
+
+@pytest.mark.parametrize("d,N", sorted(wc.SEQ_CHUNKED))
+def test_sequential_limit_with_candidates_over_several_chunks_of_four_rows(d, N):
+    assert N > dc.inflight_rows(d) == 4
+    check_sequential_limit(d, N)
+
+
+def check_sequential_limit(d, N):
+    pr = wc.seq_problem(d, N)
+    Po, Qo, neg_o, tries_o, und, sco = wc.seq_model(d, N)
     assert not und.any()
     e = engine(pr, False, reg=wc.SEQ_REG)
     e.set_optimizer(kind=0, lr=wc.SEQ_LR)
-    e.set_warp(wc.SEQ_MAX, wc.MARGIN)
+    e.set_warp(N, wc.MARGIN)
     negs = torch.zeros(wc.SEQ_N, dtype=torch.int32, device="cuda")
     sc = torch.zeros(4, device="cuda")
     e.train_stream(dev(pr["users"]), dev(pr["pos"]), sampler=NEG_WARP, neg=negs, seed=9, offset=100,
                    max_inflight=1, scalars=sc)
     got = negs.cpu().numpy()
     assert np.array_equal(got, neg_o), np.nonzero(got != neg_o)[0][:5]
-    print(f"d {d}: skipped {np.mean(got < 0):.3f}, max error P {maxerr(e.P.cpu().numpy(), Po):.3g} "
+    print(f"d {d} N {N}: skipped {np.mean(got < 0):.3f}, max error P {maxerr(e.P.cpu().numpy(), Po):.3g} "
           f"Q {maxerr(e.Q.cpu().numpy(), Qo):.3g}, scalars {sc.cpu().numpy()} model {sco}")
     assert close(e.P.cpu().numpy(), Po, 1e-5), maxerr(e.P.cpu().numpy(), Po)
     assert close(e.Q.cpu().numpy(), Qo, 1e-5), maxerr(e.Q.cpu().numpy(), Qo)
     assert close(sc.cpu().numpy(), sco, 1e-5)
+
+
+# ---- 6a. the stand-alone kernel's grid-stride passes and its ragged last wave --------------------------------------------
+UNWRITTEN, UNWRITTEN_SCORE = -7, -12345.0
+
+
+def launch_over_sentinels(e, users, pos, N, offset):
+    """bpr_sample_warp into buffers filled with sentinels: (neg, tries, x_pos, x_neg), every element of which was
+    written."""
+    from revisit_bpr import native
+
+    n = users.numel()
+    neg, tries = (torch.full((n,), UNWRITTEN, dtype=torch.int32, device="cuda") for _ in range(2))
+    xp, xn = (torch.full((n,), UNWRITTEN_SCORE, dtype=torch.float32, device="cuda") for _ in range(2))
+    e._sync_stream()
+    native.check(e._lib.bpr_sample_warp(e._ctx, users.data_ptr(), pos.data_ptr(), n, N, wc.MARGIN, wc.SEED, offset,
+                                        neg.data_ptr(), tries.data_ptr(), xp.data_ptr(), xn.data_ptr()))
+    assert (neg != UNWRITTEN).all() and (tries != UNWRITTEN).all()
+    assert (xp != UNWRITTEN_SCORE).all() and (xn != UNWRITTEN_SCORE).all()
+    return neg, tries, xp, xn
+
+
+@pytest.mark.parametrize("d", sorted(dc.GRID_N))
+def test_a_launch_past_the_grid_is_its_slices_and_the_model(d):
+    """More draws than one pass of k_sample_scored's grid (dynamic_cases.GRID_N: 8,192 draws a pass at G = 64, 16,384
+    at G = 32) with a ragged last wave — at d = 64 an odd tail, the wave's second group without a draw."""
+    n, G = dc.GRID_N[d], dc.group_shape(d)[0]
+    assert n > dc.GRID_PASS[d] == 2048 * 256 // G and n % (64 // G) == 64 // G - 1 and n % (256 // G) != 0
+    pr = wc.grid_problem(d)
+    e = engine(pr, True)
+    users, pos = dev(pr["users"]), dev(pr["pos"])
+    whole = launch_over_sentinels(e, users, pos, wc.GRID_MAX, 0)
+    # the whole launch is the launches of its slices, each at its own offset: items, tries and both scores
+    for lo in range(0, n, dc.GRID_SLICE):
+        hi = lo + dc.GRID_SLICE
+        part = e.sample_warp(users[lo:hi], pos[lo:hi], wc.GRID_MAX, seed=wc.SEED, offset=lo, margin=wc.MARGIN,
+                             return_scores=True)
+        for a, b in zip(whole, part):
+            assert torch.equal(a[lo:hi], b), lo
+    # and the model's draws across the pass boundary and at the tail
+    got = [t.cpu().numpy() for t in whole]
+    for lo, hi in dc.grid_windows(d):
+        check_against_model([a[lo:hi] for a in got], wc.grid_model(d, (lo, hi)), f"d {d} draws {lo} .. {hi}")
 
 
 def test_a_zero_weight_takes_only_its_l2_step():

@@ -125,6 +125,7 @@ def test_undecided_share_and_mix_of_the_gpu_pick_cases(d, bias):
             assert (tries == 0).sum() >= 3 and (tries > 1).mean() > 0.02
         if N >= 10:
             assert (tries > 8).any()  # a violator past the first chunk of 8 rows
+            assert ((tries == 3) | (tries == 4)).any()  # and in the second chunk of 2 rows, the first of 4 and of 8
 
 
 def test_undecided_share_of_the_other_gpu_cases():
@@ -139,6 +140,34 @@ def test_undecided_share_of_the_other_gpu_cases():
     assert (acc == 0).any() and ((acc > 0) & (acc < 8)).any()
 
 
+def test_undecided_share_of_the_wide_edge_cases():
+    """The d = 1024 runs of the one / none / fewer-than-N unseen case, and the order case's tries."""
+    ed = wc.one_unseen(d=1024)
+    items, tries, _, _, und, _, acc = wm.sample(ed["P"], ed["Q"], None, ed["indptr"], ed["indices"], ed["users"],
+                                                ed["pos"], 8, wc.MARGIN, wc.SEED, 0)
+    assert not und.any() and (items == ed["unseen"]).all() and (tries == 1).all()
+    assert (acc == 0).any() and ((acc > 0) & (acc < 8)).any()
+    few = np.full(len(ed["users"]), 3, np.int32)
+    assert wm.sample(ed["P"], ed["Q"], None, ed["indptr"], ed["indices"], few, ed["pos"], 8, wc.MARGIN, wc.SEED,
+                     0)[4].mean() <= 0.01
+    # the violator of the order case at every place 1 .. 32 and nowhere, at any width (scores are the item ids)
+    for d in (32, 512, 1024):
+        pr = wc.order_problem(d=d)
+        _, tries, _, _, und, _, _ = wm.sample(pr["P"], pr["Q"], None, pr["indptr"], pr["indices"], pr["users"],
+                                              pr["pos"], 32, 1.5, 5, 0, lists=wc.order_lists())
+        assert not und.any() and np.array_equal(np.unique(tries), np.arange(33))
+        print(f"d {d}: triples per tries 0 .. 32: {np.bincount(tries).tolist()}")
+
+
+@pytest.mark.parametrize("d", sorted(wc.dc.GRID_N))
+def test_undecided_share_of_the_gpu_grid_windows(d):
+    for w in wc.dc.grid_windows(d):
+        _, tries, _, _, und, _, acc = wc.grid_model(d, w)
+        print(f"d {d} draws {w}: undecided {und.mean():.4%}, triples per tries {np.bincount(tries).tolist()}")
+        assert und.mean() <= 0.01 and (acc == wc.GRID_MAX).all()
+        assert (tries == 0).any() and (tries > 8).any()  # skips, and a violator past the widest chunk
+
+
 @pytest.mark.parametrize("d", wc.SEQ_DS)
 def test_every_triple_of_the_sequential_cases_is_decided(d):
     P, Q, neg, tries, und, sc = wc.seq_model(d)
@@ -150,9 +179,32 @@ def test_every_triple_of_the_sequential_cases_is_decided(d):
         assert j == -1 or (j != 0 and j not in pr["indices"][pr["indptr"][u]:pr["indptr"][u + 1]])
 
 
+@pytest.mark.parametrize("d,N", sorted(wc.SEQ_CHUNKED))
+def test_every_triple_of_the_chunked_sequential_cases_is_decided(d, N):
+    """N over several chunks of four rows: violators in the first chunk, in every later one, and skips."""
+    P, Q, neg, tries, und, sc = wc.seq_model(d, N)
+    assert not und.any(), int(und.sum())
+    assert np.isfinite(P).all() and np.isfinite(Q).all() and sc[3] == (neg >= 0).sum()
+    print(f"d {d} N {N}: triples per tries 0 .. {N}: {np.bincount(tries, minlength=N + 1).tolist()}")
+    assert (neg < 0).sum() >= 20 and wc.dc.inflight_rows(d) == 4
+    for lo in range(0, N, 4):  # a violator in every chunk
+        assert ((tries > lo) & (tries <= lo + 4)).sum() >= 5, lo
+    pr = wc.seq_problem(d, N)
+    for u, j in zip(pr["users"], neg):
+        assert j == -1 or (j != 0 and j not in pr["indices"][pr["indptr"][u]:pr["indptr"][u + 1]])
+
+
 def test_the_skip_case_skips_exactly_its_users():
-    pr = wc.skip_problem()
-    P, Q, b, neg, tries, und, sc = wc.skip_model()
+    check_skip_case(32)
+
+
+def test_the_skip_case_at_sixteen_entries_a_lane_skips_exactly_its_users():
+    check_skip_case(640)  # (a width at which the model leaves no triple of the case undecided)
+
+
+def check_skip_case(d):
+    pr = wc.skip_problem(d)
+    P, Q, b, neg, tries, und, sc = wc.skip_model(10, d)
     sk = np.isin(pr["users"], pr["skipped"])
     assert not und.any() and sk.sum() >= 20 and (neg[sk] == -1).all() and (neg[~sk] >= 0).mean() > 0.5
     assert np.array_equal(P[pr["skipped"]], pr["P"][pr["skipped"]]) and np.array_equal(Q[pr["top"]], pr["Q"][pr["top"]])

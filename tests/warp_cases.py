@@ -15,12 +15,20 @@ import warp_model as wm
 SEED = dc.SEED
 MARGIN = 1.0
 NS = (1, 2, 10, 32)
-DS = (20, 32, 128, 256)  # G = 32 with E = 1, 1, 4 and G = 64 with E = 4; 20 is no multiple of 4
+# every group layout of the library's widths 1 .. 1024 (tests/dynamic_cases.py: DS), each at a full width and at a
+# partial one: G = 32 with E = 1 (20: no multiple of 4; 32), 2 (40; 64) and 4 (128); G = 64 with E = 4 (256), 8 (300; 512)
+# and 16 (1000; 1024) — chunks of 8, 4 and 2 candidate rows
+DS = (20, 32, 40, 64, 128, 256, 300, 512, 1000, 1024)
 PICK_U, PICK_I, PICK_N, PICK_SEEN = 64, 300, 1024, 30
-SEQ_DS = (32, 128, 256)
+SEQ_DS = (32, 128, 256, 300, 512, 1000, 1024)
 SEQ_U, SEQ_I, SEQ_N, SEQ_LR, SEQ_REG, SEQ_MAX = 60, 90, 400, 0.05, (0.01, 0.02, 0.03), 4
 # seeds of the sequential problems, chosen on the CPU so that every one of the 400 triples is decided
-SEQ_SEED = {32: 5, 128: 5, 256: 5}
+SEQ_SEED = {32: 5, 128: 5, 256: 5, 300: 1, 512: 2, 1000: 1, 1024: 3}
+# SEQ_MAX = 4 is ONE chunk at E = 8: the same limit at (d, N) with N over two chunks and more (8 = 4 + 4, 10 = 4 + 4 + 2),
+# seeds chosen the same way
+SEQ_CHUNKED = {(300, 8): 2, (512, 10): 3}
+# the grid-stride pass and the ragged tail of the stand-alone kernel: tests/dynamic_cases.py GRID_PASS, GRID_N
+GRID_MAX = 10
 
 _cache = {}
 
@@ -116,22 +124,70 @@ def big_model(N=10):
     return _cache[key]
 
 
-def seq_problem(d):
-    key = ("seq", d)
+def seq_problem(d, N=SEQ_MAX):
+    key = ("seq", d, N)
     if key not in _cache:
-        _cache[key] = problem(SEQ_U, SEQ_I, d, 30, seed=SEQ_SEED[d], n=SEQ_N, small=0.05, large=2.0)
+        seed = SEQ_SEED[d] if N == SEQ_MAX else SEQ_CHUNKED[(d, N)]
+        _cache[key] = problem(SEQ_U, SEQ_I, d, 30, seed=seed, n=SEQ_N, small=0.05, large=2.0)
     return _cache[key]
 
 
-def seq_model(d):
+def seq_model(d, N=SEQ_MAX):
     """The sequential trainer on a copy of the problem: (P, Q, negatives, tries, undecided, scalars)."""
-    key = ("seq_model", d)
+    key = ("seq_model", d, N)
     if key not in _cache:
-        pr = seq_problem(d)
+        pr = seq_problem(d, N)
         P, Q = pr["P"].copy(), pr["Q"].copy()
         neg, tries, und, sc = wm.train_sequential(P, Q, None, pr["indptr"], pr["indices"], pr["users"], pr["pos"],
-                                                  SEQ_MAX, MARGIN, SEQ_LR, SEQ_REG, seed=9, offset=100)
+                                                  N, MARGIN, SEQ_LR, SEQ_REG, seed=9, offset=100)
         _cache[key] = (P, Q, neg, tries, und, sc)
+    return _cache[key]
+
+
+def grid_problem(d):
+    """The pick tables of width d (with the bias) under dynamic_cases.GRID_N[d] (user, positive) pairs."""
+    key = ("grid", d)
+    if key not in _cache:
+        pr = dict(pick_problem(d, True))
+        rng = np.random.default_rng(79)
+        pr["users"] = rng.integers(1, PICK_U, size=dc.GRID_N[d]).astype(np.int32)
+        pr["pos"] = rng.integers(1, PICK_I, size=dc.GRID_N[d]).astype(np.int32)
+        _cache[key] = pr
+    return _cache[key]
+
+
+def grid_model(d, window):
+    """warp_model.sample (N = GRID_MAX) of the draws window = (lo, hi) of the grid case, at offset = lo."""
+    key = ("grid_model", d, window)
+    if key not in _cache:
+        pr = grid_problem(d)
+        lo, hi = window
+        out = wm.sample(pr["P"], pr["Q"], pr["b"], pr["indptr"], pr["indices"], pr["users"][lo:hi], pr["pos"][lo:hi],
+                        GRID_MAX, MARGIN, SEED, lo)
+        for a in out:
+            a.setflags(write=False)
+        _cache[key] = out
+    return _cache[key]
+
+
+def order_problem(n=2048, I=41, d=32):
+    """Score of item a = a for user 1, who has seen item 1; the positive is item 38 and the margin 1.5, so items
+    37 .. 40 violate: a tenth of the candidates, no score near a bound."""
+    P = np.zeros((2, d), np.float32)
+    P[1, 0] = 1.0
+    Q = np.zeros((I, d), np.float32)
+    Q[1:, 0] = np.arange(1, I)
+    indptr, indices = np.array([0, 0, 1], np.int64), np.array([1], np.int32)
+    return dict(P=P, Q=Q, b=None, indptr=indptr, indices=indices, I=I, d=d, users=np.full(n, 1, np.int32),
+                pos=np.full(n, 38, np.int32))
+
+
+def order_lists(n=2048):
+    """The accepted lists (N = 32, seed 5) of the order problem: they depend on neither d nor the tables."""
+    key = ("order_lists", n)
+    if key not in _cache:
+        pr = order_problem(n)
+        _cache[key] = dm.accepted_lists(pr["indptr"], pr["indices"], pr["I"], pr["users"], 32, 5, 0)
     return _cache[key]
 
 
@@ -160,11 +216,11 @@ def skip_problem(d=32, n=256):
     return _cache[key]
 
 
-def skip_model(N=10):
+def skip_model(N=10, d=32):
     """The sequential trainer on the skip problem: (P, Q, bias, negatives, tries, undecided, scalars)."""
-    key = ("skip_model", N)
+    key = ("skip_model", N, d)
     if key not in _cache:
-        pr = skip_problem()
+        pr = skip_problem(d)
         P, Q, b = pr["P"].copy(), pr["Q"].copy(), pr["b"].copy()
         neg, tries, und, sc = wm.train_sequential(P, Q, b, pr["indptr"], pr["indices"], pr["users"], pr["pos"], N, MARGIN,
                                                   SEQ_LR, SEQ_REG, seed=3, offset=2 ** 32 - 100)
