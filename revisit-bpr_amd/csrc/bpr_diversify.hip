@@ -40,7 +40,7 @@
 #include <string>
 
 #include "bpr_diversify_plan.h"
-#include "bpr_host.h"
+#include "bpr_serving_host.h"
 #include "bpr_topk_shared.h"
 
 namespace bpr {
@@ -277,13 +277,6 @@ static int check_shape(const char* who, int64_t n, int32_t C, int32_t k, int32_t
   return BPR_OK;
 }
 
-template <bool VEC>
-static int launch(const DivArgs& a, const DiversifyPlan& p, hipStream_t stream) {
-  hipLaunchKernelGGL(k_diversify<VEC>, dim3((unsigned)p.grid), dim3(DIVERSIFY_THREADS), p.lds, stream, a);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
 }  // namespace dv
 }  // namespace bpr
 
@@ -326,8 +319,8 @@ extern "C" int bpr_diversify_rows(const float* Q, int64_t I, int32_t d, const in
   a.cosine = metric == BPR_SIM_COSINE; a.minmax = scale == BPR_SCALE_MINMAX;
   a.out_items = items_out; a.out_scores = scores_out; a.out_mmr = mmr_out;
   hipStream_t stream = (hipStream_t)hip_stream;
-  const bool vec = d % 4 == 0 && reinterpret_cast<uintptr_t>(Q) % 16 == 0;
-  return vec ? launch<true>(a, p, stream) : launch<false>(a, p, stream);
+  return launch_kernel(vec_path(d, Q) ? k_diversify<true> : k_diversify<false>, 0, dim3((unsigned)p.grid),
+                       dim3(DIVERSIFY_THREADS), p.lds, stream, a);
 }
 
 // Test hook, not API (tests/test_diversify_cpu.py sets its signature): the plan of a shape.  in = {n, C, k, layout};

@@ -39,8 +39,8 @@
 
 #include <string>
 
-#include "bpr_host.h"
 #include "bpr_neighbors_plan.h"
+#include "bpr_serving_host.h"
 #include "bpr_topk_shared.h"
 
 namespace bpr {
@@ -244,26 +244,14 @@ static int check_metric(const char* who, int32_t metric) {
   return BPR_OK;
 }
 
-template <bool VEC, bool COS>
-static int launch(const NeighborsArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
-  // one workgroup may ask for most of a CU's LDS: past 64 KiB that is a per-function attribute (set on every
-  // call: the process may hold several devices, and the call costs nothing next to a launch)
-  BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_neighbors<VEC, COS>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)neighbors_lds_bytes(TOPK_MAX)));
-  hipLaunchKernelGGL((k_neighbors<VEC, COS>), grid, dim3(256), lds, stream, a);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
 }  // namespace nbr
 }  // namespace bpr
 
 extern "C" int bpr_neighbors_workspace(int64_t n, int64_t N, int32_t d, int32_t k, int32_t metric,
                                        int32_t item_slices, int64_t* bytes_host) {
   using namespace bpr;
-  if (bytes_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_neighbors_workspace: bytes_host is NULL");
-  if (int rc = check_topk_shape("bpr_neighbors_workspace", n, N, d, k, item_slices, "N")) return rc;
+  if (int rc = check_out("bpr_neighbors_workspace", bytes_host, "bytes_host")) return rc;
+  if (int rc = check_topk_shape("bpr_neighbors_workspace", n, N, d, k, TOPK_MAX, item_slices, "N")) return rc;
   if (int rc = nbr::check_metric("bpr_neighbors_workspace", metric)) return rc;
   *bytes_host = neighbors_workspace_bytes(n, N, k, metric, item_slices);
   return BPR_OK;
@@ -272,8 +260,8 @@ extern "C" int bpr_neighbors_workspace(int64_t n, int64_t N, int32_t d, int32_t 
 extern "C" int bpr_neighbors_slices(int64_t n, int64_t N, int32_t d, int32_t k, int32_t item_slices,
                                     int32_t* slices_host) {
   using namespace bpr;
-  if (slices_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_neighbors_slices: slices_host is NULL");
-  if (int rc = check_topk_shape("bpr_neighbors_slices", n, N, d, k, item_slices, "N")) return rc;
+  if (int rc = check_out("bpr_neighbors_slices", slices_host, "slices_host")) return rc;
+  if (int rc = check_topk_shape("bpr_neighbors_slices", n, N, d, k, TOPK_MAX, item_slices, "N")) return rc;
   *slices_host = plan_neighbors(n, N, k, NBR_DOT, item_slices).t.slices;
   return BPR_OK;
 }
@@ -284,15 +272,13 @@ extern "C" int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int
                                   float* scores_out, void* hip_stream) {
   using namespace bpr;
   using namespace bpr::nbr;
-  if (int rc = check_topk_shape("bpr_neighbors_rows", n, N, d, k, item_slices, "N")) return rc;
+  if (int rc = check_topk_shape("bpr_neighbors_rows", n, N, d, k, TOPK_MAX, item_slices, "N")) return rc;
   if (int rc = check_metric("bpr_neighbors_rows", metric)) return rc;
   if (first < 0) return fail(BPR_ERR_INVALID, "bpr_neighbors_rows: first must be >= 0");
   if (n > 0 && (!X || !T || !rows || !ids_out || !scores_out))
     return fail(BPR_ERR_INVALID, "bpr_neighbors_rows: X, T, rows, ids_out or scores_out is NULL");
   const NeighborsPlan p = plan_neighbors(n, N, k, metric, item_slices);
-  if (p.ws_bytes > 0 && (workspace == nullptr || workspace_bytes < p.ws_bytes))
-    return fail(BPR_ERR_INVALID, "bpr_neighbors_rows: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                     std::to_string(p.ws_bytes) + " needed (bpr_neighbors_workspace)");
+  if (int rc = check_workspace("bpr_neighbors", workspace, workspace_bytes, p.ws_bytes)) return rc;
   if (n == 0) return BPR_OK;
 
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -301,30 +287,23 @@ extern "C" int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int
   a.X = X; a.T = T; a.N = N; a.d = d; a.rows = rows; a.n = n; a.exclude = exclude; a.first = first;
   a.k = k; a.slices = S; a.tiles = p.t.item_tiles;
   // workspace: the slices' partial scores, their ids, then (cosine) rn of the table rows and of the queries
-  float* part_s = reinterpret_cast<float*>(workspace);
-  int32_t* part_i = reinterpret_cast<int32_t*>(part_s + (S > 1 ? n * (int64_t)S * k : 0));
-  a.out_scores = S > 1 ? part_s : scores_out;
-  a.out_ids = S > 1 ? part_i : ids_out;
-  const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(T)) % 16 == 0;
-  if (metric == NBR_COSINE) {
+  slice_outputs(workspace, n, S, k, scores_out, ids_out, &a.out_scores, &a.out_ids);
+  const bool vec = vec_path(d, X, T), cosine = metric == NBR_COSINE;
+  if (cosine) {
     float* rn_t = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + p.partial_bytes);
     float* rn_x = rn_t + N;
     a.rn_t = rn_t;
     a.rn_x = rn_x;
     const int64_t blocks = (N + n + 255) / 256;  // < 2^24
-    if (vec) hipLaunchKernelGGL(k_neighbors_norms<true>, dim3((unsigned)blocks), dim3(256), 0, stream, T, N, X, rows, n,
-                                (int)d, rn_t, rn_x);
-    else hipLaunchKernelGGL(k_neighbors_norms<false>, dim3((unsigned)blocks), dim3(256), 0, stream, T, N, X, rows, n,
-                            (int)d, rn_t, rn_x);
-    BPR_HIP_CHECK(hipGetLastError());
+    if (int rc = launch_kernel(vec ? k_neighbors_norms<true> : k_neighbors_norms<false>, 0, dim3((unsigned)blocks),
+                               dim3(256), 0, stream, T, N, X, rows, n, (int)d, rn_t, rn_x))
+      return rc;
   }
+  const auto kernel = cosine ? (vec ? k_neighbors<true, true> : k_neighbors<false, true>)
+                             : (vec ? k_neighbors<true, false> : k_neighbors<false, false>);
   const dim3 grid((unsigned)p.t.user_tiles, (unsigned)S);
-  int rc;
-  if (metric == NBR_COSINE) rc = vec ? launch<true, true>(a, grid, p.lds, stream) : launch<false, true>(a, grid, p.lds, stream);
-  else rc = vec ? launch<true, false>(a, grid, p.lds, stream) : launch<false, false>(a, grid, p.lds, stream);
-  if (rc != BPR_OK) return rc;
-  if (S > 1) return launch_topk_merge(part_s, part_i, n, S, k, p.t.merge_lds, scores_out, ids_out, stream);
-  return BPR_OK;
+  if (int rc = launch_kernel(kernel, neighbors_lds_bytes(TOPK_MAX), grid, dim3(256), p.lds, stream, a)) return rc;
+  return launch_topk_merge(a.out_scores, a.out_ids, n, S, k, p.t.merge_lds, scores_out, ids_out, stream);
 }
 
 // Test hook, not API (tests/test_neighbors_cpu.py sets its signature): the plan of a shape.  in = {n, N, d, k,
@@ -333,7 +312,7 @@ extern "C" int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int
 // Needs no GPU.
 extern "C" int bpr_test_neighbors_plan(const int64_t* in, int64_t* out, int64_t* bounds) {
   using namespace bpr;
-  if (int rc = check_topk_shape("bpr_test_neighbors_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3],
+  if (int rc = check_topk_shape("bpr_test_neighbors_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3], TOPK_MAX,
                                 (int32_t)in[5], "N"))
     return rc;
   if (int rc = nbr::check_metric("bpr_test_neighbors_plan", (int32_t)in[4])) return rc;
@@ -342,6 +321,6 @@ extern "C" int bpr_test_neighbors_plan(const int64_t* in, int64_t* out, int64_t*
   const int64_t v[] = {p.t.slices, p.t.user_tiles, p.t.item_tiles, TOPK_TU, TOPK_TI, p.t.cap, (int64_t)p.lds,
                        (int64_t)NBR_LDS_LIMIT, (int64_t)p.t.merge_lds, p.partial_bytes, p.norm_bytes, p.ws_bytes};
   memcpy(out, v, sizeof(v));
-  for (int s = 0; s <= p.t.slices; ++s) bounds[s] = std::min<int64_t>(topk_slice_tile(p.t, s) * TOPK_TI, in[1]);
+  slice_bounds(p.t, topk_slice_tile, TOPK_TI, in[1], bounds);
   return BPR_OK;
 }

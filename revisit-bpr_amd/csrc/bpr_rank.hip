@@ -44,8 +44,8 @@
 #include <atomic>
 #include <string>
 
-#include "bpr_host.h"
 #include "bpr_rank_plan.h"
+#include "bpr_serving_host.h"
 #include "bpr_topk_shared.h"
 
 namespace bpr {
@@ -436,12 +436,8 @@ __device__ int32_t g_rank_check[RANK_CHECK_SLOTS * 2];
 static std::atomic<unsigned> g_rank_check_next{0};
 
 static int check_shape(const char* who, int64_t n, int64_t I, int32_t d, int32_t item_slices) {
-  if (n < 0 || I < 1 || I >= ((int64_t)1 << 31))
-    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be >= 0 and I in [1, 2^31)");
-  if (d < 1 || d > 1024) return fail(BPR_ERR_INVALID, std::string(who) + ": d must be in [1, 1024]");
-  if (item_slices < 0 || item_slices > RANK_MAX_SLICES)
-    return fail(BPR_ERR_INVALID, std::string(who) + ": item_slices must be 0 (choose) or in [1, " +
-                                     std::to_string(RANK_MAX_SLICES) + "]");
+  if (int rc = check_table_shape(who, n, I, d, "I")) return rc;
+  if (int rc = check_item_slices(who, item_slices, RANK_MAX_SLICES)) return rc;
   if (n > 0x7FFFFFFF / RANK_TMAX)  // (the finish kernel's grid: n * RANK_TMAX / 256 workgroups)
     return fail(BPR_ERR_INVALID, std::string(who) + ": n must be below 2^31 / " + std::to_string(RANK_TMAX));
   return BPR_OK;
@@ -449,26 +445,14 @@ static int check_shape(const char* who, int64_t n, int64_t I, int32_t d, int32_t
 
 template <bool PRE>
 static int launch_rank(const RankArgs& a, dim3 grid, size_t lds, bool vec, hipStream_t stream) {
-  // past 64 KiB the dynamic LDS of a workgroup is a per-function attribute (set on every call: bpr_topk.hip)
-  const int lds_max = (int)rank_lds_bytes();
-  if (vec) {
-    BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank<true, PRE>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    hipLaunchKernelGGL((k_rank<true, PRE>), grid, dim3(256), lds, stream, a);
-  } else {
-    BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank<false, PRE>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    hipLaunchKernelGGL((k_rank<false, PRE>), grid, dim3(256), lds, stream, a);
-  }
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
+  return launch_kernel(vec ? k_rank<true, PRE> : k_rank<false, PRE>, rank_lds_bytes(), grid, dim3(256), lds, stream, a);
 }
 
 }  // namespace bpr
 
 extern "C" int bpr_rank_workspace(int64_t n, int64_t I, int32_t d, int32_t item_slices, int64_t* bytes_host) {
   using namespace bpr;
-  if (bytes_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_rank_workspace: bytes_host is NULL");
+  if (int rc = check_out("bpr_rank_workspace", bytes_host, "bytes_host")) return rc;
   if (int rc = check_shape("bpr_rank_workspace", n, I, d, item_slices)) return rc;
   *bytes_host = rank_workspace_bytes(n, I, item_slices);
   return BPR_OK;
@@ -476,7 +460,7 @@ extern "C" int bpr_rank_workspace(int64_t n, int64_t I, int32_t d, int32_t item_
 
 extern "C" int bpr_rank_slices(int64_t n, int64_t I, int32_t d, int32_t item_slices, int32_t* slices_host) {
   using namespace bpr;
-  if (slices_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_rank_slices: slices_host is NULL");
+  if (int rc = check_out("bpr_rank_slices", slices_host, "slices_host")) return rc;
   if (int rc = check_shape("bpr_rank_slices", n, I, d, item_slices)) return rc;
   *slices_host = plan_rank(n, I, item_slices).slices;
   return BPR_OK;
@@ -492,9 +476,7 @@ extern "C" int bpr_rank_rows(const float* P, const float* Q, const float* item_b
   if (n > 0 && (!P || !Q || !users || !tgt_indptr))
     return fail(BPR_ERR_INVALID, "bpr_rank_rows: P, Q, users or tgt_indptr is NULL");
   const RankPlan p = plan_rank(n, I, item_slices);
-  if (p.ws_bytes > 0 && (workspace == nullptr || workspace_bytes < p.ws_bytes))
-    return fail(BPR_ERR_INVALID, "bpr_rank_rows: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                     std::to_string(p.ws_bytes) + " needed (bpr_rank_workspace)");
+  if (int rc = check_workspace("bpr_rank", workspace, workspace_bytes, p.ws_bytes)) return rc;
   if (n == 0) return BPR_OK;
 
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -525,7 +507,7 @@ extern "C" int bpr_rank_rows(const float* P, const float* Q, const float* item_b
   a.titems = tgt_items; a.indptr = seen_indptr; a.indices = seen_indices; a.slices = p.slices;
   a.item_tiles = p.item_tiles; a.rank = rank_out; a.not_below = not_below_out; a.score = score_out;
   a.ws = reinterpret_cast<int32_t*>(workspace);
-  const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Q)) % 16 == 0;
+  const bool vec = vec_path(d, P, Q);
   if (int rc = launch_rank<true>(a, dim3((unsigned)p.row_tiles), p.pre_lds, vec, stream)) return rc;
   if (p.slices > 1) {  // bins and tied after: 0; place in the list: -1
     const size_t third = (size_t)n * RANK_TMAX * sizeof(int32_t);
@@ -551,6 +533,6 @@ extern "C" int bpr_test_rank_plan(const int64_t* in, int64_t* out, int64_t* boun
   const int64_t v[] = {p.slices, p.row_tiles, p.item_tiles, RANK_TR, RANK_TI, RANK_TMAX, (int64_t)p.lds,
                        (int64_t)p.pre_lds, p.ws_bytes};
   memcpy(out, v, sizeof(v));
-  for (int s = 0; s <= p.slices; ++s) bounds[s] = std::min<int64_t>(rank_slice_tile(p, s) * RANK_TI, in[1]);
+  slice_bounds(p, rank_slice_tile, RANK_TI, in[1], bounds);
   return BPR_OK;
 }

@@ -36,8 +36,8 @@
 
 #include <string>
 
-#include "bpr_host.h"
 #include "bpr_rerank_plan.h"
+#include "bpr_serving_host.h"
 #include "bpr_topk_shared.h"
 
 namespace bpr {
@@ -253,14 +253,6 @@ static int check_shape(const char* who, int64_t n, int32_t d, int32_t k, int64_t
   return BPR_OK;
 }
 
-template <bool VEC, int TEAM>
-static int launch(const RerankArgs& a, const RerankPlan& p, hipStream_t stream) {
-  hipLaunchKernelGGL((k_rerank<VEC, TEAM>), dim3((unsigned)p.grid), dim3(RERANK_THREADS), p.lds, stream, a,
-                     (unsigned)p.team_lds);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
 }  // namespace rr
 }  // namespace bpr
 
@@ -303,9 +295,12 @@ extern "C" int bpr_rerank_rows(const float* P, const float* Q, const float* item
   a.indptr = seen_indptr; a.indices = seen_indices; a.k = k;
   a.cand_scores = cand_scores_out; a.out_items = items_out; a.out_scores = scores_out;
   hipStream_t stream = (hipStream_t)hip_stream;
-  const bool vec = d % 4 == 0 && reinterpret_cast<uintptr_t>(Q) % 16 == 0;
-  if (p.layout == RERANK_WAVE) return vec ? launch<true, 64>(a, p, stream) : launch<false, 64>(a, p, stream);
-  return vec ? launch<true, RERANK_THREADS>(a, p, stream) : launch<false, RERANK_THREADS>(a, p, stream);
+  const bool vec = vec_path(d, Q);
+  const auto kernel = p.layout == RERANK_WAVE
+                          ? (vec ? k_rerank<true, 64> : k_rerank<false, 64>)
+                          : (vec ? k_rerank<true, RERANK_THREADS> : k_rerank<false, RERANK_THREADS>);
+  return launch_kernel(kernel, 0, dim3((unsigned)p.grid), dim3(RERANK_THREADS), p.lds, stream, a,
+                       (unsigned)p.team_lds);
 }
 
 // Test hook, not API (tests/test_rerank_cpu.py sets its signature): the plan of a shape.  in = {n, d, k, row_len,

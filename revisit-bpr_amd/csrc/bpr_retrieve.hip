@@ -28,7 +28,7 @@
 // Persistent grid.  plan_retrieve bounds the workgroups (as many as stay resident, from TOPK_CUS); workgroup b
 // walks the (user tile, slice) pairs b, b + grid, ... and reuses its block, so the workspace is grid blocks plus the
 // slices' partial results whatever n is.  Item slices, their partial results and the merge are k_topk's
-// (launch_topk_merge), with slices x k <= 8,192.
+// (launch_topk_merge, bpr_serving_host.h), with slices x k <= 8,192.
 //
 // Measured (profiles/retrieve_probe.txt, ML-20M shape, d = 128; the composition is P[users] Q^T, the seen scatter and
 // torch.topk(k) per 4,096 users).  All 138,493 users: k = 128 31.5 ms against 58.8 (and against k_topk's 99.6: the
@@ -49,8 +49,8 @@
 
 #include <string>
 
-#include "bpr_host.h"
 #include "bpr_retrieve_plan.h"
+#include "bpr_serving_host.h"
 #include "bpr_topk_shared.h"
 
 namespace bpr {
@@ -296,38 +296,13 @@ __global__ __launch_bounds__(256) void k_retrieve(const RetrieveArgs a) {
   }
 }
 
-static int check_retrieve_shape(const char* who, int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices) {
-  if (n < 0 || I < 1 || I >= ((int64_t)1 << 31))
-    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be >= 0 and I in [1, 2^31)");
-  if (d < 1 || d > 1024) return fail(BPR_ERR_INVALID, std::string(who) + ": d must be in [1, 1024]");
-  if (k < 1 || k > RETRIEVE_MAX)
-    return fail(BPR_ERR_INVALID, std::string(who) + ": k must be in [1, " + std::to_string(RETRIEVE_MAX) + "]");
-  if (item_slices < 0 || item_slices > TOPK_MAX_SLICES)
-    return fail(BPR_ERR_INVALID, std::string(who) + ": item_slices must be 0 (choose) or in [1, " +
-                                     std::to_string(TOPK_MAX_SLICES) + "]");
-  if (n > 0x7FFFFFFF)  // (the merge kernel's grid is one workgroup per row)
-    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be below 2^31");
-  return BPR_OK;
-}
-
-template <bool VEC>
-static int launch(const RetrieveArgs& a, const RetrievePlan& p, hipStream_t stream) {
-  // past 64 KiB the dynamic LDS of a workgroup is a per-function attribute (set on every call, as k_topk's)
-  BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_retrieve<VEC>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)retrieve_lds_bytes(RETRIEVE_MAX)));
-  hipLaunchKernelGGL(k_retrieve<VEC>, dim3((unsigned)p.grid), dim3(256), p.lds, stream, a);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
 }  // namespace bpr
 
 extern "C" int bpr_retrieve_workspace(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices,
                                       int64_t* bytes_host) {
   using namespace bpr;
-  if (bytes_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_retrieve_workspace: bytes_host is NULL");
-  if (int rc = check_retrieve_shape("bpr_retrieve_workspace", n, I, d, k, item_slices)) return rc;
+  if (int rc = check_out("bpr_retrieve_workspace", bytes_host, "bytes_host")) return rc;
+  if (int rc = check_topk_shape("bpr_retrieve_workspace", n, I, d, k, RETRIEVE_MAX, item_slices, "I")) return rc;
   *bytes_host = retrieve_workspace_bytes(n, I, k, item_slices);
   return BPR_OK;
 }
@@ -335,8 +310,8 @@ extern "C" int bpr_retrieve_workspace(int64_t n, int64_t I, int32_t d, int32_t k
 extern "C" int bpr_retrieve_slices(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices,
                                    int32_t* slices_host) {
   using namespace bpr;
-  if (slices_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_retrieve_slices: slices_host is NULL");
-  if (int rc = check_retrieve_shape("bpr_retrieve_slices", n, I, d, k, item_slices)) return rc;
+  if (int rc = check_out("bpr_retrieve_slices", slices_host, "slices_host")) return rc;
+  if (int rc = check_topk_shape("bpr_retrieve_slices", n, I, d, k, RETRIEVE_MAX, item_slices, "I")) return rc;
   *slices_host = plan_retrieve(n, I, k, item_slices).slices;
   return BPR_OK;
 }
@@ -346,15 +321,11 @@ extern "C" int bpr_retrieve_rows(const float* P, const float* Q, const float* it
                                  const int32_t* seen_indices, int32_t k, int32_t item_slices, void* workspace,
                                  int64_t workspace_bytes, int32_t* items_out, float* scores_out, void* hip_stream) {
   using namespace bpr;
-  if (int rc = check_retrieve_shape("bpr_retrieve_rows", n, I, d, k, item_slices)) return rc;
+  if (int rc = check_topk_shape("bpr_retrieve_rows", n, I, d, k, RETRIEVE_MAX, item_slices, "I")) return rc;
   if (n > 0 && (!P || !Q || !users || !items_out || !scores_out))
     return fail(BPR_ERR_INVALID, "bpr_retrieve_rows: P, Q, users, items_out or scores_out is NULL");
   const RetrievePlan p = plan_retrieve(n, I, k, item_slices);
-  if (p.ws_bytes > 0 && (workspace == nullptr || workspace_bytes < p.ws_bytes))
-    return fail(BPR_ERR_INVALID, "bpr_retrieve_rows: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                     std::to_string(p.ws_bytes) + " needed (bpr_retrieve_workspace)");
-  if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-    return fail(BPR_ERR_INVALID, "bpr_retrieve_rows: workspace must be 8-byte aligned");
+  if (int rc = check_workspace("bpr_retrieve", workspace, workspace_bytes, p.ws_bytes, "workspace", true)) return rc;
   if (n == 0) return BPR_OK;
 
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -362,16 +333,13 @@ extern "C" int bpr_retrieve_rows(const float* P, const float* Q, const float* it
   a.P = P; a.Q = Q; a.bias = item_bias; a.I = I; a.d = d; a.users = users; a.n = n;
   a.indptr = seen_indptr; a.indices = seen_indices; a.k = k; a.slices = p.slices; a.cap = p.cap;
   a.item_tiles = p.item_tiles; a.units = p.units;
-  float* part_s = reinterpret_cast<float*>(workspace);
-  int32_t* part_i = reinterpret_cast<int32_t*>(part_s + (p.slices > 1 ? n * (int64_t)p.slices * k : 0));
+  // the rows' candidate buffers lie behind the slices' partial lists
   a.bufs = reinterpret_cast<Cand*>(reinterpret_cast<unsigned char*>(workspace) + p.part_bytes);
-  a.out_scores = p.slices > 1 ? part_s : scores_out;
-  a.out_items = p.slices > 1 ? part_i : items_out;
-  const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Q)) % 16 == 0;
-  if (int rc = vec ? launch<true>(a, p, stream) : launch<false>(a, p, stream)) return rc;
-  if (p.slices > 1)
-    return launch_topk_merge(part_s, part_i, n, p.slices, k, p.merge_lds, scores_out, items_out, stream);
-  return BPR_OK;
+  slice_outputs(workspace, n, p.slices, k, scores_out, items_out, &a.out_scores, &a.out_items);
+  if (int rc = launch_kernel(vec_path(d, P, Q) ? k_retrieve<true> : k_retrieve<false>,
+                             retrieve_lds_bytes(RETRIEVE_MAX), dim3((unsigned)p.grid), dim3(256), p.lds, stream, a))
+    return rc;
+  return launch_topk_merge(a.out_scores, a.out_items, n, p.slices, k, p.merge_lds, scores_out, items_out, stream);
 }
 
 // Test hook, not API (tests/test_retrieve_cpu.py sets its signature): the plan of a shape.  in = {n, I, d, k,
@@ -379,8 +347,8 @@ extern "C" int bpr_retrieve_rows(const float* P, const float* Q, const float* it
 // units, grid, grid_max, part_bytes, buf_bytes}; bounds[0 .. slices] = first item of each slice, then I.  No GPU.
 extern "C" int bpr_test_retrieve_plan(const int64_t* in, int64_t* out, int64_t* bounds) {
   using namespace bpr;
-  if (int rc = check_retrieve_shape("bpr_test_retrieve_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3],
-                                    (int32_t)in[4]))
+  if (int rc = check_topk_shape("bpr_test_retrieve_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3], RETRIEVE_MAX,
+                                (int32_t)in[4], "I"))
     return rc;
   const int cus = in[5] > 0 ? (int)in[5] : TOPK_CUS;
   const RetrievePlan p = plan_retrieve(in[0], in[1], (int)in[3], (int)in[4], cus);
@@ -388,6 +356,6 @@ extern "C" int bpr_test_retrieve_plan(const int64_t* in, int64_t* out, int64_t* 
                        (int64_t)p.merge_lds, p.ws_bytes, p.units, p.grid, retrieve_grid_max((int)in[3], cus),
                        p.part_bytes, p.buf_bytes};
   memcpy(out, v, sizeof(v));
-  for (int s = 0; s <= p.slices; ++s) bounds[s] = std::min<int64_t>(retrieve_slice_tile(p, s) * TOPK_TI, in[1]);
+  slice_bounds(p, retrieve_slice_tile, TOPK_TI, in[1], bounds);
   return BPR_OK;
 }

@@ -32,9 +32,9 @@
 #include <cmath>
 #include <string>
 
-#include "bpr_host.h"
 #include "bpr_sample_plan.h"
 #include "bpr_sample_shared.h"
+#include "bpr_serving_host.h"
 #include "bpr_topk_shared.h"
 
 namespace bpr {
@@ -360,35 +360,13 @@ __global__ __launch_bounds__(TOPK_MAX) void k_sample_finish(const FinishArgs a) 
   }
 }
 
-template <bool VEC>
-static int launch(const SampleArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
-  // one workgroup may ask for most of a CU's LDS: past 64 KiB that is a per-function attribute (set on every
-  // call: the process may hold several devices, and the call costs nothing next to a launch)
-  BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sample<VEC>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sample_lds_bytes(TOPK_MAX)));
-  hipLaunchKernelGGL(k_sample<VEC>, grid, dim3(256), lds, stream, a);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
-template <bool VEC>
-static int launch_finish(const FinishArgs& f, int64_t n, hipStream_t stream) {
-  hipLaunchKernelGGL(k_sample_finish<VEC>, dim3((unsigned)n), dim3(TOPK_MAX), 0, stream, f);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
-static int check_sample_shape(const char* who, int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices) {
-  return check_topk_shape(who, n, I, d, k, item_slices, "I");
-}
-
 }  // namespace bpr
 
 extern "C" int bpr_sample_workspace(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices,
                                     int32_t want_log_z, int64_t* bytes_host) {
   using namespace bpr;
-  if (bytes_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_sample_workspace: bytes_host is NULL");
-  if (int rc = check_sample_shape("bpr_sample_workspace", n, I, d, k, item_slices)) return rc;
+  if (int rc = check_out("bpr_sample_workspace", bytes_host, "bytes_host")) return rc;
+  if (int rc = check_topk_shape("bpr_sample_workspace", n, I, d, k, TOPK_MAX, item_slices, "I")) return rc;
   *bytes_host = sample_workspace_bytes(n, I, k, item_slices, want_log_z != 0);
   return BPR_OK;
 }
@@ -396,8 +374,8 @@ extern "C" int bpr_sample_workspace(int64_t n, int64_t I, int32_t d, int32_t k, 
 extern "C" int bpr_sample_slices(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices,
                                  int32_t* slices_host) {
   using namespace bpr;
-  if (slices_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_sample_slices: slices_host is NULL");
-  if (int rc = check_sample_shape("bpr_sample_slices", n, I, d, k, item_slices)) return rc;
+  if (int rc = check_out("bpr_sample_slices", slices_host, "slices_host")) return rc;
+  if (int rc = check_topk_shape("bpr_sample_slices", n, I, d, k, TOPK_MAX, item_slices, "I")) return rc;
   *slices_host = plan_topk(n, I, k, item_slices).slices;
   return BPR_OK;
 }
@@ -408,7 +386,7 @@ extern "C" int bpr_sample_rows(const float* P, const float* Q, const float* item
                                int32_t item_slices, void* workspace, int64_t workspace_bytes, int32_t* items_out,
                                float* scores_out, float* keys_out, float* log_z_out, void* hip_stream) {
   using namespace bpr;
-  if (int rc = check_sample_shape("bpr_sample_rows", n, I, d, k, item_slices)) return rc;
+  if (int rc = check_topk_shape("bpr_sample_rows", n, I, d, k, TOPK_MAX, item_slices, "I")) return rc;
   const float inv_temp = 1.0f / temperature;
   if (!(temperature > 0.f) || !std::isfinite(temperature) || !std::isfinite(inv_temp))
     return fail(BPR_ERR_INVALID, "bpr_sample_rows: temperature must be finite and > 0, and so must 1 / temperature");
@@ -416,35 +394,31 @@ extern "C" int bpr_sample_rows(const float* P, const float* Q, const float* item
     return fail(BPR_ERR_INVALID, "bpr_sample_rows: P, Q, users, items_out or scores_out is NULL");
   const bool want_lz = log_z_out != nullptr;
   const SamplePlan p = plan_sample(n, I, k, item_slices, want_lz);
-  if (p.ws_bytes > 0 && (workspace == nullptr || workspace_bytes < p.ws_bytes))
-    return fail(BPR_ERR_INVALID, "bpr_sample_rows: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                     std::to_string(p.ws_bytes) + " needed (bpr_sample_workspace)");
-  if (p.ws_bytes > 0 && reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-    return fail(BPR_ERR_INVALID, "bpr_sample_rows: the workspace must be 8-byte aligned");
+  if (int rc = check_workspace("bpr_sample", workspace, workspace_bytes, p.ws_bytes, "the workspace")) return rc;
   if (n == 0) return BPR_OK;
 
   hipStream_t stream = (hipStream_t)hip_stream;
   const int S = p.topk.slices;
   // the keys of the result: the caller's buffer, or scores_out until k_sample_finish writes the scores over them
   float* const keys = keys_out != nullptr ? keys_out : scores_out;
-  float* part_k = reinterpret_cast<float*>(workspace);
-  int32_t* part_i = reinterpret_cast<int32_t*>(part_k + (S > 1 ? n * (int64_t)S * k : 0));
   float2* lz = want_lz ? reinterpret_cast<float2*>(reinterpret_cast<unsigned char*>(workspace) + p.topk.ws_bytes)
                        : nullptr;
   SampleArgs a = {};
   a.P = P; a.Q = Q; a.bias = item_bias; a.I = I; a.d = d; a.users = users; a.draw_ids = draw_ids; a.n = n;
   a.indptr = seen_indptr; a.indices = seen_indices; a.k = k; a.slices = S; a.item_tiles = p.topk.item_tiles;
   a.inv_temp = inv_temp; a.seed = seed;
-  a.out_keys = S > 1 ? part_k : keys;
-  a.out_items = S > 1 ? part_i : items_out;
+  slice_outputs(workspace, n, S, k, keys, items_out, &a.out_keys, &a.out_items);
   a.out_lz = lz;
   FinishArgs f = {};
   f.P = P; f.Q = Q; f.bias = item_bias; f.d = d; f.users = users; f.k = k; f.slices = S; f.items = items_out;
   f.scores = scores_out; f.lz = lz; f.log_z = log_z_out;
-  const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Q)) % 16 == 0;
+  const bool vec = vec_path(d, P, Q);
   const dim3 grid((unsigned)p.topk.user_tiles, (unsigned)S);
-  if (int rc = vec ? launch<true>(a, grid, p.topk.lds, stream) : launch<false>(a, grid, p.topk.lds, stream)) return rc;
-  if (S > 1)
-    if (int rc = launch_topk_merge(part_k, part_i, n, S, k, p.topk.merge_lds, keys, items_out, stream)) return rc;
-  return vec ? launch_finish<true>(f, n, stream) : launch_finish<false>(f, n, stream);
+  if (int rc = launch_kernel(vec ? k_sample<true> : k_sample<false>, sample_lds_bytes(TOPK_MAX), grid, dim3(256),
+                             p.topk.lds, stream, a))
+    return rc;
+  if (int rc = launch_topk_merge(a.out_keys, a.out_items, n, S, k, p.topk.merge_lds, keys, items_out, stream))
+    return rc;
+  return launch_kernel(vec ? k_sample_finish<true> : k_sample_finish<false>, 0, dim3((unsigned)n), dim3(TOPK_MAX), 0,
+                       stream, f);
 }

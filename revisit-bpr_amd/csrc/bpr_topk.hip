@@ -31,7 +31,8 @@
 // into slices, grid = user tiles x slices, each slice writes its sorted top-k to the workspace and k_topk_merge
 // merges a row's slices (each entry's rank = its index + binary searches in the other slices).  Layout and sizes:
 // bpr_topk_plan.h.  What the other serving kernels use as well — staging, the chain, Cand / better / compact_row —
-// is bpr_topk_shared.h; its two host functions (check_topk_shape, launch_topk_merge) are defined here.
+// is bpr_topk_shared.h; the host prologue the serving entry points share is bpr_serving_host.h, whose
+// launch_topk_merge is defined here, beside its kernel.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -39,7 +40,7 @@
 
 #include <string>
 
-#include "bpr_host.h"
+#include "bpr_serving_host.h"
 #include "bpr_topk_plan.h"
 #include "bpr_topk_shared.h"
 
@@ -261,38 +262,11 @@ __global__ __launch_bounds__(256) void k_topk_merge(const float* __restrict__ ps
   }
 }
 
-int check_topk_shape(const char* who, int64_t n, int64_t rows, int32_t d, int32_t k, int32_t item_slices,
-                     const char* rows_name) {
-  if (n < 0 || rows < 1 || rows >= ((int64_t)1 << 31))
-    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be >= 0 and " + rows_name + " in [1, 2^31)");
-  if (d < 1 || d > 1024) return fail(BPR_ERR_INVALID, std::string(who) + ": d must be in [1, 1024]");
-  if (k < 1 || k > TOPK_MAX)
-    return fail(BPR_ERR_INVALID, std::string(who) + ": k must be in [1, " + std::to_string(TOPK_MAX) + "]");
-  if (item_slices < 0 || item_slices > TOPK_MAX_SLICES)
-    return fail(BPR_ERR_INVALID, std::string(who) + ": item_slices must be 0 (choose) or in [1, " +
-                                     std::to_string(TOPK_MAX_SLICES) + "]");
-  if (n > 0x7FFFFFFF)  // (the merge kernel's grid is one workgroup per row)
-    return fail(BPR_ERR_INVALID, std::string(who) + ": n must be below 2^31");
-  return BPR_OK;
-}
-
 int launch_topk_merge(const float* part_s, const int32_t* part_i, int64_t n, int S, int k, size_t merge_lds,
                       float* out_s, int32_t* out_i, hipStream_t stream) {
-  hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)n), dim3(256), merge_lds, stream, part_s, part_i, S, k, out_s,
-                     out_i);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
-template <bool VEC>
-static int launch(const TopkArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
-  // one workgroup may ask for most of a CU's LDS: past 64 KiB that is a per-function attribute (set on every
-  // call: the process may hold several devices, and the call costs nothing next to a launch)
-  BPR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk<VEC>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)topk_lds_bytes(TOPK_MAX)));
-  hipLaunchKernelGGL(k_topk<VEC>, grid, dim3(256), lds, stream, a);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
+  if (S <= 1) return BPR_OK;
+  return launch_kernel(k_topk_merge, 0, dim3((unsigned)n), dim3(256), merge_lds, stream, part_s, part_i, S, k, out_s,
+                       out_i);
 }
 
 }  // namespace bpr
@@ -300,16 +274,16 @@ static int launch(const TopkArgs& a, dim3 grid, size_t lds, hipStream_t stream) 
 extern "C" int bpr_topk_workspace(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices,
                                   int64_t* bytes_host) {
   using namespace bpr;
-  if (bytes_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_topk_workspace: bytes_host is NULL");
-  if (int rc = check_topk_shape("bpr_topk_workspace", n, I, d, k, item_slices, "I")) return rc;
+  if (int rc = check_out("bpr_topk_workspace", bytes_host, "bytes_host")) return rc;
+  if (int rc = check_topk_shape("bpr_topk_workspace", n, I, d, k, TOPK_MAX, item_slices, "I")) return rc;
   *bytes_host = topk_workspace_bytes(n, I, k, item_slices);
   return BPR_OK;
 }
 
 extern "C" int bpr_topk_slices(int64_t n, int64_t I, int32_t d, int32_t k, int32_t item_slices, int32_t* slices_host) {
   using namespace bpr;
-  if (slices_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_topk_slices: slices_host is NULL");
-  if (int rc = check_topk_shape("bpr_topk_slices", n, I, d, k, item_slices, "I")) return rc;
+  if (int rc = check_out("bpr_topk_slices", slices_host, "slices_host")) return rc;
+  if (int rc = check_topk_shape("bpr_topk_slices", n, I, d, k, TOPK_MAX, item_slices, "I")) return rc;
   *slices_host = plan_topk(n, I, k, item_slices).slices;
   return BPR_OK;
 }
@@ -319,29 +293,23 @@ extern "C" int bpr_topk_rows(const float* P, const float* Q, const float* item_b
                              int32_t k, int32_t item_slices, void* workspace, int64_t workspace_bytes,
                              int32_t* items_out, float* scores_out, void* hip_stream) {
   using namespace bpr;
-  if (int rc = check_topk_shape("bpr_topk_rows", n, I, d, k, item_slices, "I")) return rc;
+  if (int rc = check_topk_shape("bpr_topk_rows", n, I, d, k, TOPK_MAX, item_slices, "I")) return rc;
   if (n > 0 && (!P || !Q || !users || !items_out || !scores_out))
     return fail(BPR_ERR_INVALID, "bpr_topk_rows: P, Q, users, items_out or scores_out is NULL");
   const TopkPlan p = plan_topk(n, I, k, item_slices);
-  if (p.ws_bytes > 0 && (workspace == nullptr || workspace_bytes < p.ws_bytes))
-    return fail(BPR_ERR_INVALID, "bpr_topk_rows: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                     std::to_string(p.ws_bytes) + " needed (bpr_topk_workspace)");
+  if (int rc = check_workspace("bpr_topk", workspace, workspace_bytes, p.ws_bytes)) return rc;
   if (n == 0) return BPR_OK;
 
   hipStream_t stream = (hipStream_t)hip_stream;
   TopkArgs a = {};
   a.P = P; a.Q = Q; a.bias = item_bias; a.I = I; a.d = d; a.users = users; a.n = n;
   a.indptr = seen_indptr; a.indices = seen_indices; a.k = k; a.slices = p.slices; a.item_tiles = p.item_tiles;
-  float* part_s = reinterpret_cast<float*>(workspace);
-  int32_t* part_i = reinterpret_cast<int32_t*>(part_s + (p.slices > 1 ? n * (int64_t)p.slices * k : 0));
-  a.out_scores = p.slices > 1 ? part_s : scores_out;
-  a.out_items = p.slices > 1 ? part_i : items_out;
-  const bool vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Q)) % 16 == 0;
+  slice_outputs(workspace, n, p.slices, k, scores_out, items_out, &a.out_scores, &a.out_items);
   const dim3 grid((unsigned)p.user_tiles, (unsigned)p.slices);
-  if (int rc = vec ? launch<true>(a, grid, p.lds, stream) : launch<false>(a, grid, p.lds, stream)) return rc;
-  if (p.slices > 1)
-    return launch_topk_merge(part_s, part_i, n, p.slices, k, p.merge_lds, scores_out, items_out, stream);
-  return BPR_OK;
+  if (int rc = launch_kernel(vec_path(d, P, Q) ? k_topk<true> : k_topk<false>, topk_lds_bytes(TOPK_MAX), grid,
+                             dim3(256), p.lds, stream, a))
+    return rc;
+  return launch_topk_merge(a.out_scores, a.out_items, n, p.slices, k, p.merge_lds, scores_out, items_out, stream);
 }
 
 // Test hook, not API (tests/test_recommend_cpu.py sets its signature): the plan of a shape.  in = {n, I, d, k,
@@ -349,13 +317,13 @@ extern "C" int bpr_topk_rows(const float* P, const float* Q, const float* item_b
 // bounds[0 .. slices] = first item of each slice, then I.  Needs no GPU.
 extern "C" int bpr_test_topk_plan(const int64_t* in, int64_t* out, int64_t* bounds) {
   using namespace bpr;
-  if (int rc = check_topk_shape("bpr_test_topk_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3], (int32_t)in[4],
-                                "I"))
+  if (int rc = check_topk_shape("bpr_test_topk_plan", in[0], in[1], (int32_t)in[2], (int32_t)in[3], TOPK_MAX,
+                                (int32_t)in[4], "I"))
     return rc;
   const TopkPlan p = plan_topk(in[0], in[1], (int)in[3], (int)in[4], in[5] > 0 ? (int)in[5] : TOPK_CUS);
   const int64_t v[] = {p.slices, p.user_tiles, p.item_tiles, TOPK_TU, TOPK_TI, p.cap, (int64_t)p.lds,
                        (int64_t)p.merge_lds, p.ws_bytes};
   memcpy(out, v, sizeof(v));
-  for (int s = 0; s <= p.slices; ++s) bounds[s] = std::min<int64_t>(topk_slice_tile(p, s) * TOPK_TI, in[1]);
+  slice_bounds(p, topk_slice_tile, TOPK_TI, in[1], bounds);
   return BPR_OK;
 }

@@ -3,9 +3,9 @@
 // Device side: the guarded load of 4 features (load4), the registers -> LDS copy of a staged chunk (stash_piece,
 // BPR_STASH_CHUNK), the dot product's chain as MFMAs and as fmaf (mfma_chunk2, mfma_block1, fma_chain8), the result order (Cand,
 // better), rank-by-counting compaction of a candidate buffer (compact_row) and the selection step k_topk and
-// k_neighbors run alike (compact_overflowing_rows).  Host side: the shape check and the merge
-// launch of those two (defined in bpr_topk.hip).  What differs between the kernels — where a staged row comes from,
-// eligibility, what a score becomes — stays in their files.
+// k_neighbors run alike (compact_overflowing_rows).  Device code only: what the entry points' host sides share is
+// bpr_serving_host.h.  What differs between the kernels — where a staged row comes from, eligibility, what a score
+// becomes — stays in their files.
 //
 // Every piece here compiles to the instructions of the same statements written out in each kernel; the pieces that
 // did not in any form tried are still in the kernels' files (profiles/topk_shared_resources.md names them).  No division and no square root: the header means the same under the
@@ -171,14 +171,5 @@ __device__ __forceinline__ void compact_overflowing_rows(Cand* sBuf, int* sCnt, 
     if (c + sNeed[row] > cap) compact_row(sBuf + row * cap, c, k, lane, &sTau[row], &sCnt[row]);
   }
 }
-
-// ---- host side (defined in bpr_topk.hip).  `who`: the entry point's name, the head of every message.
-// the shape of a top-k call over a table of `rows` rows, which the messages call `rows_name` ("I", "N")
-int check_topk_shape(const char* who, int64_t n, int64_t rows, int32_t d, int32_t k, int32_t item_slices,
-                     const char* rows_name);
-// k_topk_merge on `stream`: per row, the S sorted lists of k in part_s / part_i ([n, S, k], padded with id -1 at the
-// end) -> the k best, sorted, in out_s / out_i ([n, k]).  merge_lds: TopkPlan::merge_lds.
-int launch_topk_merge(const float* part_s, const int32_t* part_i, int64_t n, int S, int k, size_t merge_lds,
-                      float* out_s, int32_t* out_i, hipStream_t stream);
 
 }  // namespace bpr

@@ -15,7 +15,8 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
-from revisit_bpr.recommend import TOPK_MAX, _table, recommend
+from revisit_bpr._serving import _table, need_rocm, ptr, query
+from revisit_bpr.recommend import TOPK_MAX, recommend
 
 METRICS = {"dot": 0, "cosine": 1}   # BPR_SIM_DOT, BPR_SIM_COSINE (include/bprcore.h)
 SCALES = {"none": 0, "minmax": 1}   # BPR_SCALE_NONE, BPR_SCALE_MINMAX
@@ -26,10 +27,7 @@ POOL_MAX = TOPK_MAX                 # longest pool, and largest k
 
 def layout_of(n: int, C: int, k: int, layout: int = 0):
     """`bpr_diversify_layout`: (layout, padded C, bytes of LDS a workgroup holds) a call of this shape runs with."""
-    lay, cpad, lds = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
-    native.check(native.load().bpr_diversify_layout(n, C, k, layout, ctypes.byref(lay), ctypes.byref(cpad),
-                                                    ctypes.byref(lds)))
-    return int(lay.value), int(cpad.value), int(lds.value)
+    return query("bpr_diversify_layout", n, C, k, layout, ctype=(ctypes.c_int32, ctypes.c_int32, ctypes.c_int64))
 
 
 @torch.no_grad()
@@ -85,11 +83,8 @@ def diversify(Q: torch.Tensor, cand_items: torch.Tensor, cand_scores: torch.Tens
         raise ValueError(f"C = {C}: a pool holds 1 to {POOL_MAX} candidates")
     cand_items, cand_scores = cand_items.contiguous(), cand_scores.detach().contiguous()
     # (the arguments are checked on any device; the work is not done on any)
-    if not (Q.is_cuda and cand_items.is_cuda and cand_scores.is_cuda):
-        raise RuntimeError("diversify needs the item table and the candidates on a ROCm device; there is no CPU path "
-                           "in libbprcore")
-    if cand_items.device != Q.device or cand_scores.device != Q.device:
-        raise RuntimeError("diversify needs every tensor on the device of Q")
+    need_rocm("diversify", "the item table and the candidates", (Q, cand_items, cand_scores),
+              (Q, cand_items, cand_scores), "Q")
     dev = Q.device
     items = torch.empty((n, k), dtype=torch.int32, device=dev)
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
@@ -98,7 +93,7 @@ def diversify(Q: torch.Tensor, cand_items: torch.Tensor, cand_scores: torch.Tens
         with torch.cuda.device(dev):
             native.check(native.load().bpr_diversify_rows(
                 Q.data_ptr(), I, d, cand_items.data_ptr(), cand_scores.data_ptr(), n, C, k, lam, METRICS[metric],
-                SCALES[scale], layout, items.data_ptr(), scores.data_ptr(), None if mmr is None else mmr.data_ptr(),
+                SCALES[scale], layout, items.data_ptr(), scores.data_ptr(), ptr(mmr),
                 torch.cuda.current_stream(dev).cuda_stream))
     if one:
         items, scores, mmr = items[0], scores[0], None if mmr is None else mmr[0]

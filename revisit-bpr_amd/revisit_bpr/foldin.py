@@ -16,20 +16,13 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
+from revisit_bpr._serving import _table
 
 
 def balance_order(lengths: torch.Tensor) -> torch.Tensor:
     """The order in which a fold-in launch hands out its rows: longest first (a stable descending
     argsort of the row lengths, int32), so that the rows that take longest start first."""
     return torch.argsort(lengths.reshape(-1), descending=True, stable=True).to(torch.int32)
-
-
-def _table(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32")
-    return t.detach().contiguous()
 
 
 def _check_csr(indptr: torch.Tensor, idx: torch.Tensor, idx_name: str, rows_name: str) -> None:

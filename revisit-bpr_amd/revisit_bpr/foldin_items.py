@@ -18,7 +18,8 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
-from revisit_bpr.foldin import _check_csr, _check_neg, _initial_rows, _neg_buffers, _rows_csr, _table, balance_order
+from revisit_bpr._serving import _table, seen_csr
+from revisit_bpr.foldin import _check_csr, _check_neg, _initial_rows, _neg_buffers, _rows_csr, balance_order
 
 
 @torch.no_grad()
@@ -73,14 +74,8 @@ def fold_in_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Te
     if item_bias is not None and item_bias.numel() != I:
         raise ValueError("item_bias must have one entry per item row")
     _check_csr(indptr, users, "users", "m")
-    if (seen_indptr is None) != (seen_indices is None):
-        raise ValueError("seen_indptr and seen_indices must both be given or both be None")
-    if seen_indptr is not None:
-        if seen_indptr.dtype != torch.int64 or seen_indices.dtype != torch.int32:
-            raise ValueError("seen_indptr must be int64 and seen_indices int32")
-        if seen_indptr.dim() != 1 or seen_indptr.numel() != U + 1:
-            raise ValueError("seen_indptr must have U+1 entries")
-        seen_indptr, seen_indices = seen_indptr.contiguous(), seen_indices.reshape(-1).contiguous()
+    seen_indptr, seen_indices = seen_csr(seen_indptr, seen_indices, U, flat=True,
+                                         together="seen_indptr and seen_indices must both be given or both be None")
     indptr, users, m, nnz = _rows_csr(indptr, users, "users")
     dev = Q.device
     if init is not None and (init.dtype != torch.float32 or tuple(init.shape) != (m, d)):

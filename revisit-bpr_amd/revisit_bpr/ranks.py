@@ -13,30 +13,19 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
+from revisit_bpr._serving import int32_ids, need_rocm, ptr, query, seen_csr, sliced_workspace, tables
 
 RANK_TMAX = 112  # bpr_rank_rows: targets of one kernel row (csrc/bpr_rank_plan.h); longer rows are split here
 
 
 def workspace_bytes(n: int, num_items: int, d: int, item_slices: int = 0) -> int:
     """`bpr_rank_workspace`: bytes of device workspace a call of this shape needs."""
-    out = ctypes.c_int64()
-    native.check(native.load().bpr_rank_workspace(n, num_items, d, item_slices, ctypes.byref(out)))
-    return int(out.value)
+    return query("bpr_rank_workspace", n, num_items, d, item_slices, ctype=ctypes.c_int64)
 
 
 def slices(n: int, num_items: int, d: int, item_slices: int = 0) -> int:
     """`bpr_rank_slices`: the slice count a call of this shape runs with."""
-    out = ctypes.c_int32()
-    native.check(native.load().bpr_rank_slices(n, num_items, d, item_slices, ctypes.byref(out)))
-    return int(out.value)
-
-
-def _table(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32")
-    return t.detach().contiguous()
+    return query("bpr_rank_slices", n, num_items, d, item_slices)
 
 
 def split_rows(users: torch.Tensor, tgt_indptr: torch.Tensor, tmax: int = RANK_TMAX):
@@ -74,40 +63,20 @@ def rank_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tenso
     them again for its own bound).  The kernel reads P[user] and the user's CSR row unchecked, so the
     ids are range-checked here first; `check_users=False` leaves that out.
     """
-    P, Q, item_bias = _table(P, "P"), _table(Q, "Q"), _table(item_bias, "item_bias")
-    if P.dim() != 2 or Q.dim() != 2 or P.shape[1] != Q.shape[1]:
-        raise ValueError("P [U, d] and Q [I, d] must share the embedding dim")
-    (U, d), I = P.shape, Q.shape[0]
-    if item_bias is not None and item_bias.numel() != I:
-        raise ValueError("item_bias must have one entry per item row")
-    users = users.reshape(-1)
+    P, Q, item_bias, U, I, d = tables(P, Q, item_bias)
+    users = int32_ids(users, strict=True)
     n = users.numel()
-    if users.dtype not in (torch.int32, torch.int64):
-        raise ValueError("users must be int32 or int64")
     if tgt_indptr.dtype != torch.int64 or tgt_items.dtype != torch.int32:
         raise ValueError("tgt_indptr must be int64 and tgt_items int32")
     if tgt_indptr.dim() != 1 or tgt_indptr.numel() != n + 1:
         raise ValueError("tgt_indptr must have n+1 entries")
-    if (seen_indptr is None) != (seen_indices is None):
-        raise ValueError("seen_indptr and seen_indices go together")
-    if seen_indptr is not None:
-        if seen_indptr.dtype != torch.int64 or seen_indices.dtype != torch.int32:
-            raise ValueError("seen_indptr must be int64 and seen_indices int32")
-        if seen_indptr.numel() != U + 1:
-            raise ValueError("seen_indptr must have U+1 entries")
+    seen_indptr, seen_indices = seen_csr(seen_indptr, seen_indices, U)
     # (the shapes are checked on any device; the work is not done on any)
-    if not (P.is_cuda and Q.is_cuda and users.is_cuda and tgt_indptr.is_cuda and tgt_items.is_cuda):
-        raise RuntimeError("rank_items needs the tables, the rows and the targets on a ROCm device; there is no "
-                           "CPU path in libbprcore")
-    if any(t is not None and t.device != P.device
-           for t in (Q, item_bias, users, tgt_indptr, tgt_items, seen_indptr, seen_indices)):
-        raise RuntimeError("rank_items needs every tensor on the device of P")
+    need_rocm("rank_items", "the tables, the rows and the targets", (P, Q, users, tgt_indptr, tgt_items),
+              (P, Q, item_bias, users, tgt_indptr, tgt_items, seen_indptr, seen_indices), "P")
     lib = native.load()
     dev = P.device
-    users = users.to(torch.int32).contiguous()
     tgt_indptr, tgt_items = tgt_indptr.contiguous(), tgt_items.reshape(-1).contiguous()
-    if seen_indptr is not None:
-        seen_indptr, seen_indices = seen_indptr.contiguous(), seen_indices.contiguous()
     total = tgt_items.numel()
     rank = torch.full((total,), -1, dtype=torch.int32, device=dev)
     not_below = torch.full((total,), -1, dtype=torch.int32, device=dev)
@@ -127,15 +96,10 @@ def rank_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tenso
     if longest > RANK_TMAX:
         users, tgt_indptr = split_rows(users, tgt_indptr)
         n = users.numel()
-    item_slices = slices(n, I, d, item_slices)  # the count this call runs with: the workspace is its own need
-    ws_bytes = workspace_bytes(n, I, d, item_slices)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    item_slices, ws, ws_bytes = sliced_workspace("rank", (n, I, d), item_slices, dev)
     with torch.cuda.device(dev):
         native.check(lib.bpr_rank_rows(
-            P.data_ptr(), Q.data_ptr(), None if item_bias is None else item_bias.data_ptr(), I, d,
-            users.data_ptr(), n, tgt_indptr.data_ptr(), tgt_items.data_ptr(),
-            None if seen_indptr is None else seen_indptr.data_ptr(),
-            None if seen_indices is None else seen_indices.data_ptr(), item_slices,
-            None if ws is None else ws.data_ptr(), ws_bytes, rank.data_ptr(), not_below.data_ptr(),
-            score.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, tgt_indptr.data_ptr(),
+            tgt_items.data_ptr(), ptr(seen_indptr), ptr(seen_indices), item_slices, ptr(ws), ws_bytes,
+            rank.data_ptr(), not_below.data_ptr(), score.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
     return rank, not_below, score

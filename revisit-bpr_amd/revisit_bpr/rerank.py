@@ -14,7 +14,8 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
-from revisit_bpr.recommend import TOPK_MAX, _table
+from revisit_bpr._serving import int32_ids, need_rocm, ptr, query, seen_csr, tables
+from revisit_bpr.recommend import TOPK_MAX
 
 LAYOUT_AUTO, LAYOUT_WAVE, LAYOUT_WG = 0, 1, 2  # `layout`: the library chooses / a wave per row / a workgroup per row
 LAYOUTS = (LAYOUT_WAVE, LAYOUT_WG)
@@ -24,9 +25,7 @@ RERANK_TILE = 256  # csrc/bpr_rerank_plan.h: candidates the workgroup layout sta
 def layout_of(n: int, d: int, k: int, row_len: int, layout: int = 0):
     """`bpr_rerank_layout`: (layout, tile) a call of this shape runs with; `row_len` is the length of the shared
     list or the mean length of the CSR rows."""
-    lay, tile = ctypes.c_int32(), ctypes.c_int32()
-    native.check(native.load().bpr_rerank_layout(n, d, k, row_len, layout, ctypes.byref(lay), ctypes.byref(tile)))
-    return int(lay.value), int(tile.value)
+    return query("bpr_rerank_layout", n, d, k, row_len, layout, ctype=(ctypes.c_int32, ctypes.c_int32))
 
 
 @torch.no_grad()
@@ -62,16 +61,8 @@ def rerank(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor], 
         raise ValueError("k = 0 returns nothing without return_scores (score_candidates)")
     if layout not in (LAYOUT_AUTO,) + LAYOUTS:
         raise ValueError(f"layout must be 0 (choose), {LAYOUT_WAVE} (wave per row) or {LAYOUT_WG} (workgroup per row)")
-    P, Q, item_bias = _table(P, "P"), _table(Q, "Q"), _table(item_bias, "item_bias")
-    if P.dim() != 2 or Q.dim() != 2 or P.shape[1] != Q.shape[1]:
-        raise ValueError("P [U, d] and Q [I, d] must share the embedding dim")
-    (U, d), I = P.shape, Q.shape[0]
-    if item_bias is not None and item_bias.numel() != I:
-        raise ValueError("item_bias must have one entry per item row")
-    users = users.reshape(-1)
-    if users.dtype not in (torch.int32, torch.int64):
-        raise ValueError("users must be int32 or int64")
-    users = users.to(torch.int32).contiguous()
+    P, Q, item_bias, U, I, d = tables(P, Q, item_bias)
+    users = int32_ids(users, strict=True)
     n = users.numel()
     if cand_items.dtype != torch.int32:
         raise ValueError("cand_items must be int32")
@@ -87,22 +78,10 @@ def rerank(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor], 
         cand_indptr = cand_indptr.contiguous()
     cand_items = cand_items.reshape(-1).contiguous()
     nnz = cand_items.numel()
-    if (seen_indptr is None) != (seen_indices is None):
-        raise ValueError("seen_indptr and seen_indices go together")
-    if seen_indptr is not None:
-        if seen_indptr.dtype != torch.int64 or seen_indices.dtype != torch.int32:
-            raise ValueError("seen_indptr must be int64 and seen_indices int32")
-        if seen_indptr.numel() != U + 1:
-            raise ValueError("seen_indptr must have U+1 entries")
-        seen_indptr, seen_indices = seen_indptr.contiguous(), seen_indices.contiguous()
+    seen_indptr, seen_indices = seen_csr(seen_indptr, seen_indices, U)
     # (the arguments are checked on any device; the work is not done on any)
-    if not (P.is_cuda and Q.is_cuda and users.is_cuda and cand_items.is_cuda
-            and (item_bias is None or item_bias.is_cuda)):
-        raise RuntimeError("rerank needs the tables, the user list and the candidates on a ROCm device; there is no "
-                           "CPU path in libbprcore")
-    if any(t is not None and t.device != P.device
-           for t in (Q, item_bias, users, cand_items, cand_indptr, seen_indptr, seen_indices)):
-        raise RuntimeError("rerank needs every tensor on the device of P")
+    need_rocm("rerank", "the tables, the user list and the candidates", (P, Q, users, cand_items, item_bias),
+              (P, Q, item_bias, users, cand_items, cand_indptr, seen_indptr, seen_indices), "P")
     lib = native.load()
     dev = P.device
     if check_users and n:
@@ -131,10 +110,8 @@ def rerank(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor], 
         cand_ptr = cand_items.data_ptr()
     with torch.cuda.device(dev):
         native.check(lib.bpr_rerank_rows(
-            P.data_ptr(), Q.data_ptr(), None if item_bias is None else item_bias.data_ptr(), I, d,
-            users.data_ptr(), n, None if shared else cand_indptr.data_ptr(), cand_ptr, row_len,
-            None if seen_indptr is None else seen_indptr.data_ptr(),
-            None if seen_indices is None else seen_indices.data_ptr(), k, layout,
+            P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(cand_indptr), cand_ptr, row_len,
+            ptr(seen_indptr), ptr(seen_indices), k, layout,
             None if cand_scores is None or not cand_scores.numel() else cand_scores.data_ptr(),
             items.data_ptr() if k else None, scores.data_ptr() if k else None,
             torch.cuda.current_stream(dev).cuda_stream))

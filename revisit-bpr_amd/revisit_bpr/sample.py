@@ -16,24 +16,19 @@ import numpy as np
 import torch
 
 from revisit_bpr import native
-from revisit_bpr.recommend import _table
+from revisit_bpr._serving import int32_ids, need_rocm, ptr, query, seen_csr, sliced_workspace, tables
 
 SAMPLE_MAX = 128  # bpr_sample_rows: largest k
 
 
 def workspace_bytes(n: int, num_items: int, d: int, k: int, item_slices: int = 0, want_log_z: bool = False) -> int:
     """`bpr_sample_workspace`: bytes of device workspace a call of this shape needs."""
-    out = ctypes.c_int64()
-    native.check(native.load().bpr_sample_workspace(n, num_items, d, k, item_slices, int(bool(want_log_z)),
-                                                    ctypes.byref(out)))
-    return int(out.value)
+    return query("bpr_sample_workspace", n, num_items, d, k, item_slices, int(bool(want_log_z)), ctype=ctypes.c_int64)
 
 
 def slices(n: int, num_items: int, d: int, k: int, item_slices: int = 0) -> int:
     """`bpr_sample_slices`: the slice count a call of this shape runs with."""
-    out = ctypes.c_int32()
-    native.check(native.load().bpr_sample_slices(n, num_items, d, k, item_slices, ctypes.byref(out)))
-    return int(out.value)
+    return query("bpr_sample_slices", n, num_items, d, k, item_slices)
 
 
 @torch.no_grad()
@@ -72,26 +67,12 @@ def sample_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Ten
     seed = int(seed)
     if not 0 <= seed < 2 ** 64:
         raise ValueError("seed must be in [0, 2^64)")
-    if not (P.is_cuda and Q.is_cuda and users.is_cuda and (item_bias is None or item_bias.is_cuda)):
-        raise RuntimeError("sample_items needs the tables and the user list on a ROCm device; there is no "
-                           "CPU path in libbprcore")
-    if any(t is not None and t.device != P.device
-           for t in (Q, item_bias, users, seen_indptr, seen_indices, draw_ids)):
-        raise RuntimeError("sample_items needs every tensor on the device of P")
+    need_rocm("sample_items", "the tables and the user list", (P, Q, users, item_bias),
+              (P, Q, item_bias, users, seen_indptr, seen_indices, draw_ids), "P")
     lib = native.load()
-    P, Q, item_bias = _table(P, "P"), _table(Q, "Q"), _table(item_bias, "item_bias")
-    if P.dim() != 2 or Q.dim() != 2 or P.shape[1] != Q.shape[1]:
-        raise ValueError("P [U, d] and Q [I, d] must share the embedding dim")
-    (U, d), I = P.shape, Q.shape[0]
-    if item_bias is not None and item_bias.numel() != I:
-        raise ValueError("item_bias must have one entry per item row")
+    P, Q, item_bias, U, I, d = tables(P, Q, item_bias)
     dev = P.device
-    if users.dtype not in (torch.int32, torch.int64):
-        raise ValueError("users must be int32 or int64")
-    users = users.reshape(-1)
-    if users.dtype != torch.int32:
-        users = users.to(torch.int32)
-    users = users.contiguous()
+    users = int32_ids(users, strict=True)
     n = users.numel()
     if draw_ids is not None:
         if draw_ids.dtype != torch.int64:
@@ -99,31 +80,20 @@ def sample_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Ten
         draw_ids = draw_ids.reshape(-1).contiguous()
         if draw_ids.numel() != n:
             raise ValueError("draw_ids must have one entry per row of users")
-    if (seen_indptr is None) != (seen_indices is None):
-        raise ValueError("seen_indptr and seen_indices go together")
-    if seen_indptr is not None:
-        if seen_indptr.dtype != torch.int64 or seen_indices.dtype != torch.int32:
-            raise ValueError("seen_indptr must be int64 and seen_indices int32")
-        if seen_indptr.numel() != U + 1:
-            raise ValueError("seen_indptr must have U+1 entries")
-        seen_indptr, seen_indices = seen_indptr.contiguous(), seen_indices.contiguous()
+    seen_indptr, seen_indices = seen_csr(seen_indptr, seen_indices, U)
     if check_users and n and bool(((users < 0) | (users >= U)).any()):
         raise ValueError("user id out of range")
     items = torch.empty((n, k), dtype=torch.int32, device=dev)
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
     keys = torch.empty((n, k), dtype=torch.float32, device=dev) if return_keys else None
     log_z = torch.empty(n, dtype=torch.float32, device=dev) if return_log_z else None
-    item_slices = slices(n, I, d, k, item_slices)  # the count this call runs with: the workspace is its own need
-    ws_bytes = workspace_bytes(n, I, d, k, item_slices, return_log_z)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev) if ws_bytes else None
+    item_slices, ws, ws_bytes = sliced_workspace("sample", (n, I, d, k), item_slices, dev,
+                                                 post=(int(bool(return_log_z)),), words=True)
     with torch.cuda.device(dev):
         native.check(lib.bpr_sample_rows(
-            P.data_ptr(), Q.data_ptr(), None if item_bias is None else item_bias.data_ptr(), I, d,
-            users.data_ptr(), n, None if draw_ids is None else draw_ids.data_ptr(),
-            None if seen_indptr is None else seen_indptr.data_ptr(),
-            None if seen_indices is None else seen_indices.data_ptr(), k, temperature, seed, item_slices,
-            None if ws is None else ws.data_ptr(), ws_bytes, items.data_ptr(), scores.data_ptr(),
-            None if keys is None else keys.data_ptr(), None if log_z is None else log_z.data_ptr(),
+            P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(draw_ids), ptr(seen_indptr),
+            ptr(seen_indices), k, temperature, seed, item_slices, ptr(ws), ws_bytes, items.data_ptr(),
+            scores.data_ptr(), ptr(keys), ptr(log_z),
             torch.cuda.current_stream(dev).cuda_stream))
     out = (items, scores)
     if return_keys:

@@ -13,7 +13,8 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
-from revisit_bpr.recommend import TOPK_MAX, _table
+from revisit_bpr._serving import _table, int32_ids, need_rocm, ptr, query, sliced_workspace
+from revisit_bpr.recommend import TOPK_MAX
 
 METRICS = {"dot": native.SIM_DOT, "cosine": native.SIM_COSINE}
 
@@ -26,24 +27,12 @@ def _metric(metric: str) -> int:
 
 def workspace_bytes(n: int, num_rows: int, d: int, k: int, metric: str = "cosine", item_slices: int = 0) -> int:
     """`bpr_neighbors_workspace`: bytes of device workspace a call of this shape needs."""
-    out = ctypes.c_int64()
-    native.check(native.load().bpr_neighbors_workspace(n, num_rows, d, k, _metric(metric), item_slices,
-                                                       ctypes.byref(out)))
-    return int(out.value)
+    return query("bpr_neighbors_workspace", n, num_rows, d, k, _metric(metric), item_slices, ctype=ctypes.c_int64)
 
 
 def slices(n: int, num_rows: int, d: int, k: int, item_slices: int = 0) -> int:
     """`bpr_neighbors_slices`: the slice count a call of this shape runs with."""
-    out = ctypes.c_int32()
-    native.check(native.load().bpr_neighbors_slices(n, num_rows, d, k, item_slices, ctypes.byref(out)))
-    return int(out.value)
-
-
-def _ids(t: torch.Tensor) -> torch.Tensor:
-    t = t.reshape(-1)
-    if t.dtype != torch.int32:
-        t = t.to(torch.int32)
-    return t.contiguous()
+    return query("bpr_neighbors_slices", n, num_rows, d, k, item_slices)
 
 
 @torch.no_grad()
@@ -78,11 +67,7 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
     first = int(first)
     if first < 0:
         raise ValueError("first must be at least 0")
-    if not (X.is_cuda and T.is_cuda and rows.is_cuda and (exclude is None or exclude.is_cuda)):
-        raise RuntimeError("neighbors needs the tables and the row list on a ROCm device; there is no CPU path "
-                           "in libbprcore")
-    if any(t is not None and t.device != X.device for t in (T, rows, exclude)):
-        raise RuntimeError("neighbors needs every tensor on the device of X")
+    need_rocm("neighbors", "the tables and the row list", (X, T, rows, exclude), (X, T, rows, exclude), "X")
     lib = native.load()
     same = X is T
     T = _table(T, "T")
@@ -90,10 +75,10 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
     if X.dim() != 2 or T.dim() != 2 or X.shape[1] != T.shape[1]:
         raise ValueError("X [*, d] and T [N, d] must share the embedding dim")
     (N, d), dev = T.shape, X.device
-    rows = _ids(rows)
+    rows = int32_ids(rows, strict=False)
     n = rows.numel()
     if exclude is not None:
-        exclude = _ids(exclude)
+        exclude = int32_ids(exclude, strict=False)
         if exclude.numel() != n:
             raise ValueError("exclude must have one entry per query")
     if check_rows and n:
@@ -103,14 +88,11 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
             raise ValueError("exclude id out of range")
     ids = torch.empty((n, k), dtype=torch.int32, device=dev)
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-    item_slices = slices(n, N, d, k, item_slices)  # the count this call runs with: the workspace is its own need
-    ws_bytes = workspace_bytes(n, N, d, k, metric, item_slices)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    item_slices, ws, ws_bytes = sliced_workspace("neighbors", (n, N, d, k), item_slices, dev, pre=(code,))
     with torch.cuda.device(dev):
         native.check(lib.bpr_neighbors_rows(
-            X.data_ptr(), T.data_ptr(), N, d, rows.data_ptr(), n,
-            None if exclude is None else exclude.data_ptr(), first, code, k, item_slices,
-            None if ws is None else ws.data_ptr(), ws_bytes, ids.data_ptr(), scores.data_ptr(),
+            X.data_ptr(), T.data_ptr(), N, d, rows.data_ptr(), n, ptr(exclude), first, code, k, item_slices,
+            ptr(ws), ws_bytes, ids.data_ptr(), scores.data_ptr(),
             torch.cuda.current_stream(dev).cuda_stream))
     return ids, scores
 
