@@ -91,8 +91,8 @@ typedef enum bpr_sampler_kind {
   /* Dynamic negative sampling (extension; Zhang et al., SIGIR 2013): the highest-scoring of M unseen uniform
    * candidates under the model as it is now (bpr_set_dynamic, bpr_sample_dynamic).  Accepted by bpr_train_stream /
    * _cut (plain SGD); bpr_train_stream_acut, bpr_train_strict, bpr_train_stream_batched, the STRICT mode of bpr_step
-   * and the fold-in entry points return BPR_ERR_UNSUPPORTED for it before the device is touched: draw with
-   * bpr_sample_dynamic and pass the picks as BPR_NEG_GIVEN there. */
+   * and the other fold-in entry points return BPR_ERR_UNSUPPORTED for it before the device is touched: draw with
+   * bpr_sample_dynamic and pass the picks as BPR_NEG_GIVEN there.  bpr_fold_in_rows_scored folds users in with it. */
   BPR_NEG_DYNAMIC = 3,
   /* The WARP objective (extension; Weston, Bengio, Usunier, IJCAI 2011 — LightFM's default loss): not a sampler of
    * negatives for BPR's log-sigmoid loss but another pairwise loss, chosen here because it replaces the draw AND the
@@ -100,7 +100,8 @@ typedef enum bpr_sampler_kind {
    * step weighted by log(estimated rank), no step when nothing violates (bpr_set_warp, bpr_sample_warp).  Accepted
    * and refused exactly where BPR_NEG_DYNAMIC is: bpr_train_stream / _cut and STREAM-mode bpr_step (plain SGD) run
    * it; bpr_train_stream_acut, bpr_train_strict, bpr_train_stream_batched, the STRICT mode of bpr_step and the
-   * fold-in entry points return BPR_ERR_UNSUPPORTED for it before the device is touched. */
+   * other fold-in entry points return BPR_ERR_UNSUPPORTED for it before the device is touched;
+   * bpr_fold_in_rows_scored folds users in with it. */
   BPR_NEG_WARP = 4
 } bpr_sampler_kind;
 
@@ -833,6 +834,41 @@ int bpr_fold_in_rows_adaptive(const float* Q, const float* item_bias /* or NULL 
                               int32_t* neg_out, int32_t* factor_out, int32_t* rank_out /* [epochs*nnz] or NULL */,
                               uint64_t seed, uint64_t offset,
                               float* P_new /* [n,d] in/out */, void* hip_stream);
+
+/* bpr_fold_in_rows with SCORED negatives (csrc/bpr_foldin_scored.hip): dynamic negatives under BPR's loss, or the WARP
+ * objective — fold new users in with the sampler the table was trained with.  The CSR contract, the triple index
+ * t = e * nnz + CSR position, the counter offset + t, row_order, the bounds, the one host read of indptr's ends, n == 0
+ * and "validated before the device is touched; Q and item_bias are never written" are bpr_fold_in_rows_adaptive's, and
+ * so is the purity: the bits of every output do not depend on row_order, on n, on the launch or on the seen structure
+ * the kernel chooses.  The triple t of the user whose row is p as it stands just before t and whose seen items are
+ * its CSR row:
+ *     candidates     a_1 .. a_m of bpr_sample_dynamic / bpr_sample_warp for (seed, counter offset + t, this seen row,
+ *                    I, `candidates`): sample_uniform's stream, the first min(candidates, accepted) unseen ones, the
+ *                    exact pick by rank when none is accepted.  No item weights: a context-free call has none.
+ *     scores         x_a = <p, Q[a]> (+ item_bias[a]), fp32, by the same device code with the (G, E)
+ *                    bpr_sample_dynamic dispatches for this d: picks, tries and scores agree with it exactly.
+ *     BPR_NEG_DYNAMIC  the pick is bpr_sample_dynamic's (the best of a_1 .. a_m; NaN rules included), the step is
+ *                    bpr_fold_in_rows': passing the picks to it as BPR_NEG_GIVEN reproduces the rows bit for bit.
+ *                    A pick 0 (nothing unseen) skips the triple.  tries_out receives 0.  `margin` is ignored.
+ *     BPR_NEG_WARP   violator: the smallest k with x_k > x_i - margin, tries = k;
+ *                    L = log(max(1, floor(n_unseen / tries))), n_unseen = (I - 1) - row length;
+ *                    p <- p - lr (-L (q_i - q_j) + alpha_user p)   (L where bpr_fold_in_rows has sigma(-x));
+ *                    no violator among a_1 .. a_m, or a NaN x_i: the triple is SKIPPED — no step, not even the L2
+ *                    term; neg_out[t] = -1, tries_out[t] = 0 (the rule of the fused STREAM path).  L = 0: the L2 term
+ *                    alone.  A violator 0 (nothing unseen) is reported and not applied.
+ * neg_out / tries_out [epochs * nnz] (each may be NULL) receive the pick and the tries at index t.  A positive or a
+ * pick outside [1, I) skips its triple.  candidates outside 1 .. 32, and under BPR_NEG_WARP a margin that is not
+ * finite and > 0: BPR_ERR_INVALID.  Any other kind: BPR_ERR_UNSUPPORTED (BPR_NEG_GIVEN, BPR_NEG_UNIFORM:
+ * bpr_fold_in_rows; BPR_NEG_ADAPTIVE: bpr_fold_in_rows_adaptive).  NaN lr or alpha_user, the d and I bounds, NULLs: as
+ * bpr_fold_in_rows_adaptive.  Context-free: runs on `hip_stream` of the current device. */
+int bpr_fold_in_rows_scored(const float* Q, const float* item_bias /* or NULL */, int64_t I, int32_t d,
+                            const int64_t* indptr /* [n+1] */, const int32_t* items, int64_t n,
+                            const int32_t* row_order /* [n] or NULL */,
+                            int32_t epochs, float lr, float alpha_user,
+                            int32_t kind /* BPR_NEG_DYNAMIC | BPR_NEG_WARP */, int32_t candidates, float margin,
+                            int32_t* neg_out /* [epochs*nnz] or NULL */, int32_t* tries_out /* [epochs*nnz] or NULL */,
+                            uint64_t seed, uint64_t offset,
+                            float* P_new /* [n,d] in/out */, void* hip_stream);
 
 /* ---- item fold-in: item rows (and biases) for ITEMS that enter the catalogue after training, learnt against the
  * FROZEN user table, item table and item bias (the reference has no such step: its time-split and user-split

@@ -15,11 +15,12 @@
 // total + PF steps.  The triples of a row are consumed in triple order by one group and each sees the row as the
 // previous one left it, so the result does not depend on PF, on the grid or on which group takes which row.
 //
-// Seen structure (bpr_foldin_adaptive_plan.h): a per-group I-bit bitmap in LDS built ONCE per row (zeroed, the row
-// ORed in, a wave-level sync), or the row's CSR slice.  A group's bitmap is touched by its own lanes only: the two
-// groups of a G = 32 wave have disjoint words, and the build runs under the group's own predicate, so neither a
-// build nor a walk of one group can race with the other's.  LDS operations of one wave execute in program order,
-// which is all the ordering a group needs; the fence + wave barrier keep the compiler from reordering them.
+// Seen structure (bpr_foldin_adaptive_plan.h; the predicates and the build: bpr_foldin_seen.h): a per-group I-bit
+// bitmap in LDS built ONCE per row (zeroed, the row ORed in, a wave-level sync), or the row's CSR slice.  A group's
+// bitmap is touched by its own lanes only: the two groups of a G = 32 wave have disjoint words, and the build runs
+// under the group's own predicate, so neither a build nor a walk of one group can race with the other's.  LDS
+// operations of one wave execute in program order, which is all the ordering a group needs; the fence + wave
+// barrier keep the compiler from reordering them.
 //
 // Wave-uniform control.  The two groups of a G = 32 wave hold different rows of different lengths, and every
 // ballot, scan and broadcast inside sample_adaptive / adaptive_walk / foldin_update must run with the whole wave
@@ -45,6 +46,7 @@
 
 #include "bpr_device.h"
 #include "bpr_foldin_adaptive_plan.h"
+#include "bpr_foldin_seen.h"
 #include "bpr_foldin_shared.h"
 #include "bpr_host.h"
 
@@ -73,50 +75,7 @@ struct FoldinAdaptiveArgs {
   int32_t bm_words;
 };
 
-// "has the row's user seen item c?" — an id outside [0, I) counts as seen, which is what the walk does with item 0:
-// never a candidate.  `on` false: the empty row of a dummy draw.
-struct SeenRowBits {
-  const uint32_t* bm;
-  int32_t I;
-  bool on;
-  __device__ __forceinline__ bool operator()(int32_t c) const {
-    if ((uint32_t)c >= (uint32_t)I) return true;
-    return on && ((bm[c >> 5] >> (c & 31)) & 1u) != 0u;
-  }
-};
-struct SeenRowCsr {
-  SeenCsr row;  // lo == hi: the empty row of a dummy draw
-  int32_t I;
-  __device__ __forceinline__ bool operator()(int32_t c) const {
-    if ((uint32_t)c >= (uint32_t)I) return true;
-    return row(c);
-  }
-};
-
 extern __shared__ uint4 foldin_adaptive_smem[];
-
-// orders the LDS operations of one wave for the compiler (the hardware executes them in program order)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// The group's bitmap BM of the row it has just taken (items [lo, lo + m) of ITEMS), built once for the row's
-// epochs * m walks.  A macro for the reason FOLDIN_NEXT_ROWS is one (a function changes the kernel's schedule); it
-// names the kernel's `lo`, `m` and `gl`, and runs under the group's own predicate.
-#define FOLDIN_BUILD_BITMAP(LANES, BM, WORDS, ITEMS, NUM_ITEMS)                                                   \
-  do {                                                                                                            \
-    uint4* bm4 = reinterpret_cast<uint4*>(BM);                                                                    \
-    for (int k = gl; k < ((WORDS) >> 2); k += (LANES)) bm4[k] = make_uint4(0u, 0u, 0u, 0u);                       \
-    wave_lds_sync();                                                                                              \
-    for (int32_t k = gl; k < m; k += 8 * (LANES)) {                                                               \
-      int32_t it[8];                                                                                              \
-      _Pragma("unroll") for (int q = 0; q < 8; ++q) it[q] = k + q * (LANES) < m ? (ITEMS)[lo + k + q * (LANES)] : -1; \
-      _Pragma("unroll") for (int q = 0; q < 8; ++q)                                                               \
-        if ((uint32_t)it[q] < (uint32_t)(NUM_ITEMS)) atomicOr(&(BM)[it[q] >> 5], 1u << (it[q] & 31));             \
-    }                                                                                                             \
-    wave_lds_sync();                                                                                              \
-  } while (0)
 
 template <int G, int E, bool BM, int PF>
 __global__ __launch_bounds__(FOLDIN_BLOCK) void k_foldin_adaptive(const FoldinAdaptiveArgs a) {

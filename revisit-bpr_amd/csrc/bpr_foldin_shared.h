@@ -1,9 +1,11 @@
-// bpr_foldin_shared.h — the skeleton the three fold-in kernels are built on (k_foldin, bpr_foldin.hip;
-// k_foldin_adaptive, bpr_foldin_adaptive.hip; k_foldin_items, bpr_foldin_items.hip).  Device side: the row a group
-// holds (FOLDIN_ROW_STATE), the loop in which groups hand rows back and take the next by ticket (FOLDIN_NEXT_ROWS),
-// the cursor a pipeline stage walks a row's triples with (FOLDIN_TRIPLE, FOLDIN_ADVANCE), and the user-row update of
-// the two user kernels (foldin_update; the item kernel has an update of its own).  Host side: the checks and the
-// launch prologue the three entry points share.  What differs between the kernels, their pipeline stages, stays in
+// bpr_foldin_shared.h — the skeleton the fold-in kernels are built on (k_foldin, bpr_foldin.hip;
+// k_foldin_adaptive, bpr_foldin_adaptive.hip; k_foldin_scored, bpr_foldin_scored.hip; k_foldin_items,
+// bpr_foldin_items.hip).  Device side: the row a group holds (FOLDIN_ROW_STATE), the loop in which groups hand rows
+// back and take the next by ticket (FOLDIN_NEXT_ROWS), the cursor a pipeline stage walks a row's triples with
+// (FOLDIN_TRIPLE, FOLDIN_ADVANCE), and the user-row updates of the three user kernels: foldin_update (BPR's step) and
+// its sibling foldin_update_warp (the WARP objective's step, k_foldin_scored alone); the item kernels have an update
+// of their own.  Host side: the checks and the launch prologue every fold-in entry point runs (bpr_fold_in_rows,
+// _adaptive, _scored, bpr_fold_in_item_rows).  What differs between the kernels, their pipeline stages, stays in
 // their files.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -112,6 +114,20 @@ __device__ __forceinline__ void foldin_update(float (&p)[E], const float (&qi)[E
   for (int e = 0; e < E; ++e) {
     const float pe = p[e];
     const float du = -lr * (-w * (qi[e] - qj[e]) + au * pe);
+    p[e] = upd ? pe + du : pe;
+  }
+}
+
+// The step of the WARP objective (bpr_scored.h) on the row a group holds: foldin_update with the rank weight L in the
+// place of sigma(-x) —  p <- p - lr (-L (q_i - q_j) + alpha_user p)  where `upd`.  L = 0 leaves the L2 term alone.  No
+// reduction: the scores were the draw's business.
+template <int G, int E>
+__device__ __forceinline__ void foldin_update_warp(float (&p)[E], const float (&qi)[E], const float (&qj)[E], float L,
+                                                   bool upd, float lr, float au) {
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const float pe = p[e];
+    const float du = -lr * (-L * (qi[e] - qj[e]) + au * pe);
     p[e] = upd ? pe + du : pe;
   }
 }

@@ -354,7 +354,12 @@ class Engine:
         fold and the flush, so the snapshot is the item table's as it stands — and it REPLACES the snapshot the
         training samplers read: a training loop that folds users in mid-epoch should pass `refresh=False`, or
         refresh on its own schedule.  `refresh=False` needs an existing snapshot, and the caller vouches for its
-        age: the kernel cannot tell a stale order from a fresh one."""
+        age: the kernel cannot tell a stale order from a fresh one.
+
+        `sampler="dynamic"` (`candidates`) and `sampler="warp"` (`max_sampled`, `margin`) fold in with the sampler
+        the table was trained with (`bpr_fold_in_rows_scored`); the keywords go through to foldin.fold_in as they
+        are — the values given to `set_dynamic` / `set_warp` are the training launches' and are not read here.  No
+        snapshot is involved, and `refresh` is ignored."""
         from revisit_bpr import foldin
 
         self._refuse_foldin_adagrad("fold_in", "revisit_bpr.foldin.fold_in")

@@ -1,6 +1,7 @@
 """Fold new users into a trained model on the HIP engine: learn p_u from a new user's history against
 the FROZEN item table (`bpr_fold_in_rows`, csrc/bpr_foldin.hip; with adaptive negatives
-`bpr_fold_in_rows_adaptive`, csrc/bpr_foldin_adaptive.hip).  The result is a [n, d] user table for
+`bpr_fold_in_rows_adaptive`, csrc/bpr_foldin_adaptive.hip; with dynamic negatives or the WARP objective
+`bpr_fold_in_rows_scored`, csrc/bpr_foldin_scored.hip).  The result is a [n, d] user table for
 `recommend`, `evaluate_topk` and `evaluate_fused`, which take any such table plus a seen CSR.
 
 The reference has no such step (its held-out users' histories are part of the training file,
@@ -11,6 +12,7 @@ There is no CPU path: tensors must live on a ROCm device.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -114,7 +116,8 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
             epochs: int, lr: float, reg_user: float = 0.0, init: Optional[torch.Tensor] = None,
             init_std: float = 0.0, seed: int = 0, offset: int = 0, neg: Optional[torch.Tensor] = None,
             return_neg: bool = False, balance: bool = True, sampler: str = "uniform", adaptive_p: float = 0.01,
-            snapshot: Optional[tuple] = None, return_draws: bool = False, _seen_mode: int = 0):
+            snapshot: Optional[tuple] = None, return_draws: bool = False, candidates: int = 4,
+            max_sampled: int = 10, margin: float = 1.0, _seen_mode: int = 0, _states: bool = False):
     """User rows P_new [n, d] for the n new users whose histories are the rows of the CSR (`indptr`
     int64 [n+1], `items` int32, sorted per row, no duplicates, ids in [1, I)), learnt by `epochs`
     sequential BPR-SGD passes over each history against the frozen `Q` [I, d] (+ `item_bias` [I]):
@@ -136,19 +139,39 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
     just before that triple's update and whose seen items are this history, from `snapshot` = (order [d, I]
     int32, sigma [d] float32) of the item table; None: `snapshot_of(Q)`.  `return_draws=True` appends the
     (factor, rank) pairs: (P_new[, negatives], factors, ranks), int32 [epochs * nnz] each.
+
+    `sampler="dynamic"` / `sampler="warp"` (`neg` must be None; `bpr_fold_in_rows_scored`): fold in with the sampler
+    the table was trained with.  The draw of a triple is `Engine.sample_dynamic`'s (the highest-scoring of the first
+    `candidates` unseen candidates, 1 .. 32) or `Engine.sample_warp`'s (the first of at most `max_sampled`, 1 .. 32,
+    that scores above the positive's score less `margin`, finite and > 0) for counter `offset` + that index under
+    `seed`, for a user whose row is the row as it stands just before that triple's update and whose seen items are
+    this history.  "dynamic" takes the step above with the pick.  "warp" takes the step of the WARP objective,
+    p <- p - lr (-L (q_i - q_j) + reg_user p) with L = log(max(1, floor(n_unseen / tries))), n_unseen = (I - 1) - the
+    history's length, and SKIPS a triple without a violator (no step, not even the L2 term): its negative is -1.
+    `return_neg=True` returns the picks; `return_draws=True` appends `tries`, int32 [epochs * nnz]: under "warp" the
+    number of the candidate that violated (0 = skipped), under "dynamic" zeros (that draw looks at all its
+    candidates and counts nothing).  `snapshot` and `adaptive_p` stay adaptive-only.
     """
     epochs = int(epochs)
     if epochs < 1:
         raise ValueError("epochs must be at least 1")
-    if sampler not in ("uniform", "adaptive"):
-        raise ValueError("sampler must be 'uniform' or 'adaptive'")
-    adaptive = sampler == "adaptive"
-    if adaptive and neg is not None:
-        raise ValueError("given negatives (`neg`) and sampler='adaptive' exclude each other")
+    if sampler not in ("uniform", "adaptive", "dynamic", "warp"):
+        raise ValueError("sampler must be 'uniform', 'adaptive', 'dynamic' or 'warp'")
+    adaptive, scored = sampler == "adaptive", sampler in ("dynamic", "warp")
+    if (adaptive or scored) and neg is not None:
+        raise ValueError(f"given negatives (`neg`) and sampler='{sampler}' exclude each other")
     if adaptive and not 0.0 < float(adaptive_p) < 1.0:
         raise ValueError("adaptive_p must be in (0, 1)")
-    if return_draws and not adaptive:
-        raise ValueError("return_draws needs sampler='adaptive'")
+    if sampler == "dynamic" and not 1 <= int(candidates) <= 32:
+        raise ValueError("candidates must be in [1, 32]")
+    if sampler == "warp" and not 1 <= int(max_sampled) <= 32:
+        raise ValueError("max_sampled must be in [1, 32]")
+    if sampler == "warp" and not (math.isfinite(float(margin)) and float(margin) > 0.0):
+        raise ValueError("margin must be finite and > 0")
+    if return_draws and not (adaptive or scored):
+        raise ValueError("return_draws needs sampler='adaptive', 'dynamic' or 'warp'")
+    if _states and not scored:
+        raise ValueError("_states needs sampler='dynamic' or 'warp'")
     if snapshot is not None and not adaptive:
         raise ValueError("snapshot needs sampler='adaptive'")
     Q, item_bias = _table(Q, "Q"), _table(item_bias, "item_bias")
@@ -183,8 +206,13 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
     lib = native.load()
     P_new = _initial_rows(init, init_std, seed, n, d, dev)
     neg, used = _neg_buffers(neg, epochs, nnz, return_neg, dev)
-    fac = rnk = None
-    if return_draws:
+    fac = rnk = tries = states = None
+    if scored:
+        if return_draws:
+            tries = torch.zeros(epochs * nnz, dtype=torch.int32, device=dev)
+        if _states:
+            states = torch.zeros((epochs * nnz, d), dtype=torch.float32, device=dev)
+    elif return_draws:
         fac = torch.zeros(epochs * nnz, dtype=torch.int32, device=dev)
         rnk = torch.zeros(epochs * nnz, dtype=torch.int32, device=dev)
     if adaptive and n and nnz:
@@ -205,6 +233,23 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
                 epochs, float(lr), float(reg_user), float(adaptive_p), None if used is None else used.data_ptr(),
                 None if fac is None else fac.data_ptr(), None if rnk is None else rnk.data_ptr(), int(seed),
                 int(offset), P_new.data_ptr(), torch.cuda.current_stream(dev).cuda_stream, *tail))
+    elif scored and n and nnz:
+        rows = balance_order(indptr[1:] - indptr[:-1]) if balance else None
+        warp = sampler == "warp"
+        fn, tail = lib.bpr_fold_in_rows_scored, ()
+        if _seen_mode or _states:  # tests: the seen structure forced (1 CSR, 2 bitmap), the row each draw saw
+            fn = lib.bpr_test_fold_in_rows_scored
+            tail = (int(_seen_mode), None if states is None else states.data_ptr())
+            fn.restype = ctypes.c_int
+            fn.argtypes = native.SIGNATURES["bpr_fold_in_rows_scored"][1] + [ctypes.c_int32, ctypes.c_void_p]
+        with torch.cuda.device(dev):
+            native.check(fn(
+                Q.data_ptr(), None if item_bias is None else item_bias.data_ptr(), I, d, indptr.data_ptr(),
+                items.data_ptr(), n, None if rows is None else rows.data_ptr(), epochs, float(lr), float(reg_user),
+                native.NEG_WARP if warp else native.NEG_DYNAMIC, int(max_sampled if warp else candidates),
+                float(margin), None if used is None else used.data_ptr(),
+                None if tries is None else tries.data_ptr(), int(seed), int(offset), P_new.data_ptr(),
+                torch.cuda.current_stream(dev).cuda_stream, *tail))
     elif n and nnz:
         order = balance_order(indptr[1:] - indptr[:-1]) if balance else None
         with torch.cuda.device(dev):
@@ -215,5 +260,6 @@ def fold_in(Q: torch.Tensor, item_bias: Optional[torch.Tensor], indptr: torch.Te
                 None if neg is None else neg.data_ptr(),
                 None if (neg is not None or used is None) else used.data_ptr(), int(seed), int(offset),
                 P_new.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-    out = (P_new,) + ((used,) if return_neg else ()) + ((fac, rnk) if return_draws else ())
+    draws = ((tries,) if scored else (fac, rnk)) if return_draws else ()
+    out = (P_new,) + ((used,) if return_neg else ()) + draws + ((states,) if _states else ())
     return out if len(out) > 1 else P_new

@@ -656,7 +656,8 @@ class Model(torch.nn.Module):
         are returned, ready for `revisit_bpr.recommend.recommend` or `evaluate_topk`.  Rows behind the optimizer
         step are replayed first (`sync()`).  Only the MF scorer has a fused form.  `sampler="adaptive"`,
         `adaptive_p` and `refresh` are `Engine.fold_in`'s: adaptive negatives from the engine's snapshot, which
-        `refresh=True` (the default) replaces with one of the item table as it stands."""
+        `refresh=True` (the default) replaces with one of the item table as it stands.  `sampler="dynamic"`
+        (`candidates`) and `sampler="warp"` (`max_sampled`, `margin`) go through the same way."""
         if not self._fusable():
             raise NotImplementedError("fold_in needs the MF logits model in float32: other scorers have no "
                                       "fold-in kernel")

@@ -158,6 +158,9 @@ SIGNATURES = {
     "bpr_fold_in_rows_adaptive": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_int64, c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p,
                                           c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "bpr_fold_in_rows_scored": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p,
+                                        c_int32, c_float, c_float, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                        c_uint64, c_uint64, c_void_p, c_void_p]),
     "bpr_fold_in_item_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_float, c_float, c_int32,
                                       c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
