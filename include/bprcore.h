@@ -92,7 +92,8 @@ typedef enum bpr_sampler_kind {
    * candidates under the model as it is now (bpr_set_dynamic, bpr_sample_dynamic).  Accepted by bpr_train_stream /
    * _cut (plain SGD); bpr_train_stream_acut, bpr_train_strict, bpr_train_stream_batched, the STRICT mode of bpr_step
    * and the other fold-in entry points return BPR_ERR_UNSUPPORTED for it before the device is touched: draw with
-   * bpr_sample_dynamic and pass the picks as BPR_NEG_GIVEN there.  bpr_fold_in_rows_scored folds users in with it. */
+   * bpr_sample_dynamic and pass the picks as BPR_NEG_GIVEN there.  bpr_fold_in_rows_scored folds users in with it;
+   * bpr_train_stream_batched_scored is the batched STREAM launch with it, under any optimizer kind. */
   BPR_NEG_DYNAMIC = 3,
   /* The WARP objective (extension; Weston, Bengio, Usunier, IJCAI 2011 — LightFM's default loss): not a sampler of
    * negatives for BPR's log-sigmoid loss but another pairwise loss, chosen here because it replaces the draw AND the
@@ -101,7 +102,8 @@ typedef enum bpr_sampler_kind {
    * and refused exactly where BPR_NEG_DYNAMIC is: bpr_train_stream / _cut and STREAM-mode bpr_step (plain SGD) run
    * it; bpr_train_stream_acut, bpr_train_strict, bpr_train_stream_batched, the STRICT mode of bpr_step and the
    * other fold-in entry points return BPR_ERR_UNSUPPORTED for it before the device is touched;
-   * bpr_fold_in_rows_scored folds users in with it. */
+   * bpr_fold_in_rows_scored folds users in with it, bpr_train_stream_batched_scored is the batched STREAM launch with
+   * it, under any optimizer kind. */
   BPR_NEG_WARP = 4
 } bpr_sampler_kind;
 
@@ -447,11 +449,39 @@ int bpr_hot_fold(bpr_ctx* ctx);
  * the gradient for the row's next visitor (same arithmetic, bit-identical in the max_inflight = 1
  * limit).  On by default except for Adam on a model with item_bias;
  * bpr_set_tuning(ctx, "vs_direct", 0 / 1) forces it off / on (a measurement and test aid).
- * BPR_NEG_DYNAMIC, BPR_NEG_WARP: BPR_ERR_UNSUPPORTED, checked before the device is touched. */
+ * BPR_NEG_DYNAMIC, BPR_NEG_WARP: BPR_ERR_UNSUPPORTED, checked before the device is touched
+ * (bpr_train_stream_batched_scored, below, is this launch with them). */
 int bpr_train_stream_batched(bpr_ctx* ctx, const int32_t* users, const int32_t* pos, int32_t* neg,
                              int64_t n, int64_t B, int32_t sampler, float adaptive_p,
                              uint64_t seed, uint64_t offset, int64_t max_inflight,
                              float* out_scalars);
+/* BATCHED STREAM with the scored samplers: bpr_train_stream_batched's launch — the same virtual mini-batches, one
+ * torch.optim step per row and batch under any optimizer kind, the same max_inflight, vs_direct and step counter —
+ * with sampler = BPR_NEG_DYNAMIC or BPR_NEG_WARP (any other kind: BPR_ERR_INVALID).  The draw is the one stated at
+ * bpr_sample_dynamic and bpr_sample_warp above, with the ctx's bpr_set_dynamic / bpr_set_warp values, for counter
+ * offset + k of triple k (the uniform sampler's candidate stream, item weights, the rank fallback, duplicates kept;
+ * the pick rules and NaN rules as stated there).  Two rules are this entry point's own:
+ *   views      every row the draw reads — p_u, q_i and each candidate's item row and bias — is the row AS OF STEP
+ *              t - 1 of the triple's virtual batch t (its pending step applied, the zero-gradient steps since
+ *              replayed), as every gradient of the batch is; nothing is written by the draw.  On rows that do not
+ *              move the picks and tries are bpr_sample_dynamic's and bpr_sample_warp's bit for bit (the same
+ *              reduction at every width); with max_inflight = 1 that holds for the launch's first virtual batch on
+ *              flushed tables, and later batches draw on the tables the earlier batches left.
+ *   skipped    a BPR_NEG_WARP triple without a violator contributes to no row (it parks no gradient, closes no step,
+ *              takes no lock) and to no scalar, yet it belongs to virtual batch k / B: the launch advances the step
+ *              counter by ceil(n / B) whatever was skipped, and a row touched by skipped triples only is an
+ *              untouched row — it catches up lazily with zero gradient, as a dense torch.optim step does.
+ * The step: BPR_NEG_DYNAMIC as bpr_train_stream_batched's on the pick; BPR_NEG_WARP with L = log(max(1,
+ * floor(n_unseen / tries))) in the place of sigma(-x) in the three rows' gradients and the bias gradients, the L2
+ * terms as they are.  neg [n] or NULL receives the picks (-1: skipped); tries [n] or NULL receives BPR_NEG_WARP's
+ * tries (0: skipped) and 1 for every BPR_NEG_DYNAMIC triple.  out_scalars (+=): BPR_NEG_DYNAMIC as
+ * bpr_train_stream_batched; BPR_NEG_WARP as bpr_train_stream's, over the stepped triples: sum L (margin - x_i + x_k),
+ * the L2 term, sum |x_i - x_k|, the stepped count.  No seen CSR, users or pos NULL, B < 1, unapplied STRICT
+ * gradients: BPR_ERR_INVALID, nothing launched.  STRICT (bpr_train_strict, bpr_step) keeps refusing both kinds. */
+int bpr_train_stream_batched_scored(bpr_ctx* ctx, const int32_t* users, const int32_t* pos,
+                                    int32_t* neg /* or NULL */, int32_t* tries /* or NULL */, int64_t n, int64_t B,
+                                    int32_t sampler, uint64_t seed, uint64_t offset, int64_t max_inflight,
+                                    float* out_scalars);
 /* DataLoader(shuffle=True, generator=manual_seed(seed)) stand-in (example.py:307-321,
  * experiments/bpr/exp.py:109-118) without the by-user grouping of bpr_plan_epoch: a seeded
  * pseudo-random permutation of the n training triples, computed on device.  Outputs must not alias

@@ -63,6 +63,10 @@ struct ScoredShape;
 struct ScoredWarpArgs;
 int launch_sample_scored(bpr_ctx* c, const char* who, ScoredShape s, ScoredWarpArgs a);
 
+// bpr_vstream_scored.hip: k_vstream with dynamic negatives or the WARP objective, in the launch bpr_vstream.hip laid out
+struct VStreamArgs;
+int launch_vstream_scored(bpr_ctx* c, const VStreamArgs& a, int sampler, unsigned grid, unsigned block, size_t shmem);
+
 struct Timer {
   bpr_ctx* c;
   size_t slot = 0;

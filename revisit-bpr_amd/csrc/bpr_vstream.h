@@ -49,6 +49,7 @@
 
 #include "bpr_device.h"
 #include "bpr_opt.h"
+#include "bpr_scored.h"
 
 namespace bpr {
 
@@ -618,6 +619,11 @@ struct VStreamArgs {
   float au, ai, an, inv_log1mp;
   ItemWeights iw;
   VOpt o;
+  // the scored kinds (NEG_DYNAMIC, NEG_WARP: bpr_train_stream_batched_scored), behind everything the other kinds
+  // read, whose kernel arguments keep their offsets
+  int32_t* tries;   // [n] or NULL: NEG_WARP's tries (0 = skipped), 1 for every NEG_DYNAMIC triple
+  int32_t K;        // candidates (bpr_set_dynamic) / max_sampled (bpr_set_warp)
+  float margin;     // NEG_WARP (bpr_set_warp)
 };
 
 // rows of the triple as of step t-1 are staged in LDS ([3][G*E] floats per group: p_u, q_i, q_j),
@@ -632,9 +638,22 @@ struct VStreamArgs {
 // BIAS = false: a model without item_bias — the scalar copies of the optimizer math that serve the
 // riding scalar are compiled out (a fifth of the Adam kernel's code, and code size is what this
 // kernel is sensitive to: profiles/r04_vstream_direct.md).
+//
+// SCORED (NEG_DYNAMIC, NEG_WARP; instantiated in bpr_vstream_scored.hip only): the negative is bpr_scored.h's draw on
+// VIEWS.  With p_u and q_i as of t-1 in the group's LDS rows, the candidates a_1 .. a_m (accepted_candidates: the
+// uniform sampler's stream at counter offset + k, item weights, the rank fallback, duplicates kept) are viewed one
+// after the other — a read-only vs_view of the candidate's item row as of t-1, lazy replay and pending step like
+// every other row of the triple — and scored by sample_scored's reduction, group_sum(dot(p, q)) + bias.  The pick
+// rules are sample_scored's; the chosen candidate's view is kept as row 2 (it is not taken again).  The three rows
+// and the candidates go through ONE vs_view call site (a loop over "row 0, row 1, candidate 0, 1, ..."): the replay
+// is the kernel's largest block and the kernel waits for instruction fetch.  NEG_WARP: x_i is the score of rows 0
+// and 1, the step weight is L = warp_weight in the place of sigma(-x), and a triple without a violator is SKIPPED —
+// it contributes to no row (parks nothing, closes nothing, takes no lock) and to no scalar.
 template <int G, int E, int SAMPLER, int SEEN, int KIND, bool DIRECT, bool BIAS>
 __global__ __launch_bounds__(256, (E <= 4 ? VS_BLOCKS_E4 : (E <= 8 ? 2 : 1))) void k_vstream(const VStreamArgs a) {
   constexpr int DP = G * E;
+  constexpr bool SCORED = SAMPLER == NEG_DYNAMIC || SAMPLER == NEG_WARP;
+  constexpr bool WARP = SAMPLER == NEG_WARP;
   const int lane = threadIdx.x & 63;
   const int gl = lane & (G - 1);
   const int gw = lane / G;
@@ -674,52 +693,120 @@ __global__ __launch_bounds__(256, (E <= 4 ? VS_BLOCKS_E4 : (E <= 8 ? 2 : 1))) vo
     int32_t j = 0;
     float bi = 0.f, bj = 0.f;
     uint64_t hu = 0, hi_ = 0, hj = 0;  // headers the three views were taken under
+    float x_pos = 0.f, x_neg = 0.f, L = 0.f;  // SCORED: the two scores the pick was decided by; NEG_WARP's weight
+    if constexpr (SCORED) {
+      static_assert(SEEN == SEEN_LIST, "the scored kinds are launched with the staged seen list");
+      int32_t mine = 0, n_unseen = 0, tries = 0;
+      int cnt = 1, c = 0;
+      bool found = false;
+      [[maybe_unused]] float bound = 0.f;
+      j = WARP ? -1 : 0;
+      int r = 0;
 #pragma unroll 1
-    for (int r = 0; r < 3; ++r) {
-      if (r == 2) {  // the negative: drawn from the user's row as of t-1, like the reference
-        if constexpr (SAMPLER == NEG_GIVEN) {
-          j = a.neg[kk];
-        } else {
+      while (r < 3) {
+        if (r == 2 && c == 0) {  // rows 0 and 1 are in LDS: the candidates, and NEG_WARP's x_i
           const int64_t lo = a.indptr[u], hi = a.indptr[u + 1];
-          using Seen = typename std::conditional<
-              SEEN == SEEN_BITMAP, SeenBitmap,
-              typename std::conditional<SEEN == SEEN_LIST, SeenList, SeenCsr>::type>::type;
-          Seen seen;
-          if constexpr (SEEN == SEEN_BITMAP) {
-            seen_bitmap_build<G>(lds, a.bm_words, a.indices, lo, hi, gl);
-            seen = SeenBitmap{lds};
-          } else if constexpr (SEEN == SEEN_LIST) {
-            const int32_t ln = seen_list_build<G>(lds, a.bm_words, a.indices, lo, hi, gl);
-            seen = SeenList{reinterpret_cast<const int32_t*>(lds), ln, a.indices, lo, hi, nullptr,
-                            NOT_HEAVY};
-          } else {
-            seen = SeenCsr{a.indices, lo, hi};
-          }
-          const uint64_t ctr = a.offset + (uint64_t)kk;
-          if constexpr (SAMPLER == NEG_UNIFORM) {
-            j = sample_uniform<G>(seen, hi - lo, a.indices + lo, a.I, a.seed, ctr, lane, a.iw);
-          } else {
-            float p[E], sg[E];
+          const int32_t ln = seen_list_build<G>(lds, a.bm_words, a.indices, lo, hi, gl);
+          const SeenList seen{reinterpret_cast<const int32_t*>(lds), ln, a.indices, lo, hi, nullptr, NOT_HEAVY};
+          cnt = accepted_candidates<G>(mine, seen, hi - lo, a.indices + lo, a.I, a.seed, a.offset + (uint64_t)kk,
+                                       a.K, lane, a.iw);
+          n_unseen = (int32_t)(((int64_t)a.I - 1) - (hi - lo));
+          if constexpr (WARP) {
+            float s = 0.f;
 #pragma unroll
-            for (int e = 0; e < E; ++e) p[e] = rows[e * G + gl];
-            load_row<G, E>(sg, a.sigma, d, gl);
-            const AdaptiveRandoms rnd =
-                adaptive_randoms(a.seed, ctr, a.inv_log1mp, (int64_t)(a.I - 1) - (hi - lo));
-            j = sample_adaptive<G, E>(p, d, sg, a.order, a.I, seen, hi - lo, rnd, lane).item;
+            for (int e = 0; e < E; ++e) s = fmaf(rows[e * G + gl], rows[DP + e * G + gl], s);
+            x_pos = group_sum<G>(s, lane) + bi;
+            bound = x_pos - a.margin;
           }
-          if (a.neg != nullptr && act && gl == 0) a.neg[k] = j;
+        }
+        // (a group past its last candidate, or with its violator, views one of its candidates again and takes nothing:
+        // the loop is wave-uniform)
+        const int32_t cand = group_bcast<G>(mine, min(c, cnt - 1), lane);
+        const uint32_t row = r == 0 ? u : (r == 1 ? i : (uint32_t)cand);
+        float w[E], wb;
+        const uint64_t hr = vs_view<G, E, KIND>(w, wb, table(r), row, d, gl, t, a.o);
+        if (r < 2) {
+          hu = r == 0 ? hr : hu;
+          hi_ = r == 1 ? hr : hi_;
+#pragma unroll
+          for (int e = 0; e < E; ++e) rows[r * DP + e * G + gl] = w[e];
+          bi = r == 1 ? wb : bi;
+          ++r;
+        } else {
+          float s = 0.f;  // sample_scored's reduction: dot<E>(p, q), group_sum, + bias
+#pragma unroll
+          for (int e = 0; e < E; ++e) s = fmaf(rows[e * G + gl], w[e], s);
+          const float x = group_sum<G>(s, lane) + wb;
+          bool take;
+          if constexpr (WARP) take = !found && c < cnt && x > bound;
+          else take = c < cnt && (c == 0 || x > x_neg || (x_neg != x_neg && x == x));
+          if constexpr (WARP) found = found || take;
+          if (take) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) rows[2 * DP + e * G + gl] = w[e];
+          }
+          j = take ? cand : j;
+          tries = take ? c + 1 : tries;
+          x_neg = take ? x : x_neg;
+          bj = take ? wb : bj;
+          hj = take ? hr : hj;
+          ++c;
+          if (!__any(c < cnt && !(WARP && found))) r = 3;
         }
       }
-      const uint32_t row = r == 0 ? u : (r == 1 ? i : (uint32_t)j);
-      float w[E], wb;
-      const uint64_t hr = vs_view<G, E, KIND>(w, wb, table(r), row, d, gl, t, a.o);
-      hu = r == 0 ? hr : hu;
-      hi_ = r == 1 ? hr : hi_;
-      hj = r == 2 ? hr : hj;
+      if constexpr (WARP) L = found ? warp_weight((int64_t)n_unseen, tries) : 0.f;
+      if (act && gl == 0) {
+        if (a.neg != nullptr) a.neg[k] = j;
+        if (a.tries != nullptr) a.tries[k] = WARP ? tries : 1;
+      }
+    } else {
+#pragma unroll 1
+      for (int r = 0; r < 3; ++r) {
+        if (r == 2) {  // the negative: drawn from the user's row as of t-1, like the reference
+          if constexpr (SAMPLER == NEG_GIVEN) {
+            j = a.neg[kk];
+          } else {
+            const int64_t lo = a.indptr[u], hi = a.indptr[u + 1];
+            using Seen = typename std::conditional<
+                SEEN == SEEN_BITMAP, SeenBitmap,
+                typename std::conditional<SEEN == SEEN_LIST, SeenList, SeenCsr>::type>::type;
+            Seen seen;
+            if constexpr (SEEN == SEEN_BITMAP) {
+              seen_bitmap_build<G>(lds, a.bm_words, a.indices, lo, hi, gl);
+              seen = SeenBitmap{lds};
+            } else if constexpr (SEEN == SEEN_LIST) {
+              const int32_t ln = seen_list_build<G>(lds, a.bm_words, a.indices, lo, hi, gl);
+              seen = SeenList{reinterpret_cast<const int32_t*>(lds), ln, a.indices, lo, hi, nullptr,
+                              NOT_HEAVY};
+            } else {
+              seen = SeenCsr{a.indices, lo, hi};
+            }
+            const uint64_t ctr = a.offset + (uint64_t)kk;
+            if constexpr (SAMPLER == NEG_UNIFORM) {
+              j = sample_uniform<G>(seen, hi - lo, a.indices + lo, a.I, a.seed, ctr, lane, a.iw);
+            } else {
+              float p[E], sg[E];
 #pragma unroll
-      for (int e = 0; e < E; ++e) rows[r * DP + e * G + gl] = w[e];
-      bi = r == 1 ? wb : bi;
-      bj = r == 2 ? wb : bj;
+              for (int e = 0; e < E; ++e) p[e] = rows[e * G + gl];
+              load_row<G, E>(sg, a.sigma, d, gl);
+              const AdaptiveRandoms rnd =
+                  adaptive_randoms(a.seed, ctr, a.inv_log1mp, (int64_t)(a.I - 1) - (hi - lo));
+              j = sample_adaptive<G, E>(p, d, sg, a.order, a.I, seen, hi - lo, rnd, lane).item;
+            }
+            if (a.neg != nullptr && act && gl == 0) a.neg[k] = j;
+          }
+        }
+        const uint32_t row = r == 0 ? u : (r == 1 ? i : (uint32_t)j);
+        float w[E], wb;
+        const uint64_t hr = vs_view<G, E, KIND>(w, wb, table(r), row, d, gl, t, a.o);
+        hu = r == 0 ? hr : hu;
+        hi_ = r == 1 ? hr : hi_;
+        hj = r == 2 ? hr : hj;
+#pragma unroll
+        for (int e = 0; e < E; ++e) rows[r * DP + e * G + gl] = w[e];
+        bi = r == 1 ? wb : bi;
+        bj = r == 2 ? wb : bj;
+      }
     }
     // x_uij = <p_u, q_i - q_j> + b_i - b_j   (model.py:48-64, 131-145)
     float xl = 0.f, reg = 0.f;
@@ -729,11 +816,13 @@ __global__ __launch_bounds__(256, (E <= 4 ? VS_BLOCKS_E4 : (E <= 8 ? 2 : 1))) vo
       xl = fmaf(pe, qie - qje, xl);
       reg += a.ai * qie * qie + a.an * qje * qje + a.au * pe * pe;
     }
-    const float x = group_sum<G>(xl, lane) + (bi - bj);
-    if (stats && act) {
+    // NEG_WARP: the two scores the violator was found by; a skipped triple steps no row and counts nowhere
+    const float x = WARP ? x_pos - x_neg : group_sum<G>(xl, lane) + (bi - bj);
+    const bool upd = WARP ? act && j >= 0 : act;
+    if (stats && upd) {
       s_reg += 0.5f * reg;
       if (gl == 0) {
-        s_loss += neg_logsigmoid(x);
+        s_loss += WARP ? L * (a.margin - x) : neg_logsigmoid(x);  // NEG_WARP: L (margin - x_i + x_k)
         s_abs += fabsf(x);
         s_cnt += 1.f;
       }
@@ -741,7 +830,7 @@ __global__ __launch_bounds__(256, (E <= 4 ? VS_BLOCKS_E4 : (E <= 8 ? 2 : 1))) vo
     // per-triple gradients, w = sigma(-x): row r gets c_p p + c_i q_i + c_j q_j.
     // padding_idx drops the gradient of the pad EMBEDDING row (torch's embedding backward); the
     // pad item's bias is an ordinary parameter and keeps its gradient.
-    const float w = 1.0f / (1.0f + expf(x));
+    const float w = WARP ? L : 1.0f / (1.0f + expf(x));  // (NEG_WARP: the rank weight in the place of sigma(-x))
     const bool has_bias = BIAS && a.Q.b != nullptr;
 #pragma unroll 1
     for (int r = 0; r < 3; ++r) {
@@ -756,7 +845,7 @@ __global__ __launch_bounds__(256, (E <= 4 ? VS_BLOCKS_E4 : (E <= 8 ? 2 : 1))) vo
         g[e] = cp * rows[e * G + gl] + ci * rows[DP + e * G + gl] + cj * rows[2 * DP + e * G + gl];
       const float gb = r == 0 ? 0.f : (r == 1 ? -w : w);
       vs_contribute<G, E, KIND>(table(r), row, d, gl, lane, t, g, gb,
-                                act && (!pad || (r != 0 && has_bias)), a.o,
+                                upd && (!pad || (r != 0 && has_bias)), a.o,
                                 r == 0 ? hu : (r == 1 ? hi_ : hj), DIRECT && r == 0,
                                 DIRECT && r == 0 && alone);
     }
@@ -859,6 +948,9 @@ __global__ __launch_bounds__(256) void k_vflush(const VFlushArgs a) {
   }
 }
 
+// ---- the launch's helper kernels: not templates, so they are compiled into bpr_vstream.o alone — a second
+// translation unit that wants k_vstream only (bpr_vstream_scored.hip) defines BPR_VSTREAM_KERNEL_ONLY
+#ifndef BPR_VSTREAM_KERNEL_ONLY
 __global__ __launch_bounds__(256) void k_vfill_hdr(uint64_t* __restrict__ H, int64_t rows,
                                                    uint64_t value) {
   for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < rows;
@@ -956,5 +1048,6 @@ __global__ void k_shuffle_scatter(const int32_t* __restrict__ users_in,
     pos_out[x] = pos_in[t];
   }
 }
+#endif  // BPR_VSTREAM_KERNEL_ONLY
 
 }  // namespace bpr

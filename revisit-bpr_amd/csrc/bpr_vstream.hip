@@ -9,6 +9,7 @@
 #include <string>
 
 #include "bpr_host.h"
+#include "bpr_scored_plan.h"
 #include "bpr_vstream.h"
 
 namespace bpr {
@@ -230,7 +231,9 @@ static int launch_vstream(bpr_ctx* c, VStreamArgs a, int sampler, int64_t cap_gr
       };
       if (sampler == NEG_GIVEN) with_kind(integral_constant<int, NEG_GIVEN>{});
       else if (sampler == NEG_UNIFORM) with_kind(integral_constant<int, NEG_UNIFORM>{});
-      else with_kind(integral_constant<int, NEG_ADAPTIVE>{});
+      else if (sampler_scored(sampler)) {  // the same launch, the kernels of bpr_vstream_scored.hip
+        if (int rc = launch_vstream_scored(c, a, sampler, grid, block, shmem)) return rc;
+      } else with_kind(integral_constant<int, NEG_ADAPTIVE>{});
     }
     if (out_scalars != nullptr)
       hipLaunchKernelGGL(k_vsum_partials, dim3(1), dim3(256), 0, c->stream, a.partials, (int)grid,
@@ -240,29 +243,24 @@ static int launch_vstream(bpr_ctx* c, VStreamArgs a, int sampler, int64_t cap_gr
   });
 }
 
-}  // namespace bpr
-
-using namespace bpr;
-
-extern "C" {
-
-int bpr_train_stream_batched(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg,
-                             int64_t n, int64_t B, int32_t sampler, float adaptive_p,
-                             uint64_t seed, uint64_t offset, int64_t max_inflight,
-                             float* out_scalars) {
-  if (int rc = refuse_scored("bpr_train_stream_batched", sampler)) return rc;
+// What bpr_train_stream_batched and bpr_train_stream_batched_scored share: the checks, vs_enter, the DIRECT decision,
+// k_valone's marking and the launch.  `who` names the entry point in the messages; tries: the scored entry's output.
+static int train_stream_batched_impl(bpr_ctx* c, const char* who, const int32_t* users, const int32_t* pos,
+                                     int32_t* neg, int32_t* tries, int64_t n, int64_t B, int32_t sampler,
+                                     float adaptive_p, uint64_t seed, uint64_t offset, int64_t max_inflight,
+                                     float* out_scalars) {
   if (c != nullptr) c->keys_cut = false;
-  if (int rc = check_triples(c, "bpr_train_stream_batched", users, pos, n)) return rc;
-  if (int rc = check_sampler(c, "bpr_train_stream_batched", sampler, adaptive_p, neg, n)) return rc;
-  if (B < 1) return fail(BPR_ERR_INVALID, "bpr_train_stream_batched: B must be >= 1");
-  if (int rc = check_opt_state(c, "bpr_train_stream_batched")) return rc;
+  if (int rc = check_triples(c, who, users, pos, n)) return rc;
+  if (int rc = check_sampler(c, who, sampler, adaptive_p, neg, n)) return rc;
+  if (B < 1) return fail(BPR_ERR_INVALID, std::string(who) + ": B must be >= 1");
+  if (int rc = check_opt_state(c, who)) return rc;
   if (c->pending != 0)
-    return fail(BPR_ERR_INVALID, "bpr_train_stream_batched: unapplied STRICT gradients pending");
+    return fail(BPR_ERR_INVALID, std::string(who) + ": unapplied STRICT gradients pending");
   if (n == 0) return BPR_OK;
   const int64_t steps = (n + B - 1) / B;
   if (n >= ((int64_t)1 << 31) || B >= ((int64_t)1 << 31) || c->step + steps >= VSTEP_MAX)
     return fail(BPR_ERR_UNSUPPORTED,
-                "bpr_train_stream_batched: n, B and the optimizer step count must be < 2^31");
+                std::string(who) + ": n, B and the optimizer step count must be < 2^31");
   BPR_HIP_CHECK(hipSetDevice(c->device));
   if (int rc = vs_enter(c)) return rc;
   VStreamArgs a;
@@ -282,6 +280,9 @@ int bpr_train_stream_batched(bpr_ctx* c, const int32_t* users, const int32_t* po
   a.inv_log1mp = sampler == BPR_NEG_ADAPTIVE ? inv_log1mp(adaptive_p) : 0.f;
   a.iw = ItemWeights{c->w_accept, c->w_alias};
   a.o = vopt(c);
+  a.tries = tries;
+  a.K = sampler == BPR_NEG_WARP ? c->warp_N : c->dyn_M;  // bpr_set_warp / bpr_set_dynamic
+  a.margin = c->warp_margin;
   // DIRECT launches: user rows are owned, and alone in their virtual batch they take their step at
   // once (bpr_vstream.h, vs_contribute): +20 / +5 / +6 % for SGD / momentum / RMSprop on the Yelp
   // shape, +2 % for Adam without item_bias.  Off for Adam WITH item_bias, whose kernel is at the
@@ -306,6 +307,30 @@ int bpr_train_stream_batched(bpr_ctx* c, const int32_t* users, const int32_t* po
   if (int rc = launch_vstream(c, a, sampler, max_inflight, out_scalars)) return rc;
   c->step += steps;
   return BPR_OK;
+}
+
+}  // namespace bpr
+
+using namespace bpr;
+
+extern "C" {
+
+int bpr_train_stream_batched(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg,
+                             int64_t n, int64_t B, int32_t sampler, float adaptive_p,
+                             uint64_t seed, uint64_t offset, int64_t max_inflight,
+                             float* out_scalars) {
+  if (int rc = refuse_scored("bpr_train_stream_batched", sampler)) return rc;
+  return train_stream_batched_impl(c, "bpr_train_stream_batched", users, pos, neg, nullptr, n, B, sampler, adaptive_p,
+                                   seed, offset, max_inflight, out_scalars);
+}
+
+int bpr_train_stream_batched_scored(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg,
+                                    int32_t* tries, int64_t n, int64_t B, int32_t sampler, uint64_t seed,
+                                    uint64_t offset, int64_t max_inflight, float* out_scalars) {
+  if (!sampler_scored(sampler))
+    return fail(BPR_ERR_INVALID, "bpr_train_stream_batched_scored: sampler must be BPR_NEG_DYNAMIC or BPR_NEG_WARP");
+  return train_stream_batched_impl(c, "bpr_train_stream_batched_scored", users, pos, neg, tries, n, B, sampler, 0.f,
+                                   seed, offset, max_inflight, out_scalars);
 }
 
 int bpr_shuffle_epoch(bpr_ctx* c, const int32_t* users_in, const int32_t* pos_in, int64_t n,

@@ -77,10 +77,12 @@ def strict_epoch(model, optimizer, sampler, users, items, seen_pad, batch_size, 
 @click.option("--sampling-prob", type=float, default=1 / 700, show_default=True)
 @click.option("--sampler", "sampler_name", type=click.Choice(["adaptive", "dynamic", "warp"]), default="adaptive",
               show_default=True, help="adaptive: the reference's adaptive oversampling; dynamic: the highest-scoring of "
-                                      "--candidates unseen uniform candidates under the live model (stream: fused; "
-                                      "strict on one GPU: drawn per batch, any --optimizer); warp: the WARP objective "
-                                      "in BPR's place — the first of --max-sampled unseen candidates within --margin "
-                                      "of the positive, the step weighted by log(estimated rank) (--mode stream only)")
+                                      "--candidates unseen uniform candidates under the live model (stream: fused, "
+                                      "plain SGD; batched: fused, any --optimizer; strict on one GPU: drawn per "
+                                      "batch, any --optimizer); warp: the WARP objective in BPR's place — the first "
+                                      "of --max-sampled unseen candidates within --margin of the positive, the step "
+                                      "weighted by log(estimated rank) (--mode stream: plain SGD; --mode batched: any "
+                                      "--optimizer)")
 @click.option("--candidates", type=click.IntRange(1, 32), default=4, show_default=True,
               help="--sampler dynamic: candidates scored per triple")
 @click.option("--max-sampled", type=click.IntRange(1, 32), default=10, show_default=True,
@@ -144,12 +146,12 @@ def main(dataset_path, synthetic_name, num_users, num_items, embedding_dim, batc
 
     if mode == "stream" and opt_name != "sgd":
         raise SystemExit("--mode stream is the fused SGD kernel; use --mode batched for --optimizer " + opt_name)
-    if sampler_name == "dynamic" and (mode == "batched" or (mode == "strict" and world > 1)):
-        raise SystemExit("--sampler dynamic runs with --mode stream, or --mode strict on one GPU")
-    if sampler_name == "warp" and mode != "stream":
-        raise SystemExit("--sampler warp runs with --mode stream: the objective is fused into the plain-SGD kernel only")
+    if sampler_name == "dynamic" and mode == "strict" and world > 1:
+        raise SystemExit("--sampler dynamic runs with --mode stream or --mode batched, or --mode strict on one GPU")
+    if sampler_name == "warp" and mode == "strict":
+        raise SystemExit("--sampler warp runs with --mode stream (plain SGD) or --mode batched (any --optimizer)")
     if mode == "batched":
-        from revisit_bpr.fast import BatchedStreamTrainer
+        from revisit_bpr.fast import BatchedStreamTrainer, ScoredBatchedStreamTrainer
 
         users_t, items_t, sync = t["users"], t["items"], None
         if world > 1:
@@ -160,9 +162,15 @@ def main(dataset_path, synthetic_name, num_users, num_items, embedding_dim, batc
             users_t, items_t = users_t[mine].contiguous(), items_t[mine].contiguous()
             f = model.logits_model.get_features()
             sync = ItemSync([f["item"].data] + ([f["item_bias"].data] if f["item_bias"] is not None else []))
-        trainer = BatchedStreamTrainer(model, make_optimizer(), users_t, items_t, t["indptr"], t["indices"],
-                                       sampler="adaptive", adaptive_p=sampling_prob, batch_size=batch_size,
-                                       seed=seed, rank=rank, item_sync=sync)
+        if sampler_name in ("dynamic", "warp"):  # the scored samplers under any optimizer, in the same launches
+            trainer = ScoredBatchedStreamTrainer(model, make_optimizer(), users_t, items_t, t["indptr"], t["indices"],
+                                                 sampler=sampler_name, candidates=candidates, max_sampled=max_sampled,
+                                                 margin=margin, batch_size=batch_size, seed=seed, rank=rank,
+                                                 item_sync=sync)
+        else:
+            trainer = BatchedStreamTrainer(model, make_optimizer(), users_t, items_t, t["indptr"], t["indices"],
+                                           sampler="adaptive", adaptive_p=sampling_prob, batch_size=batch_size,
+                                           seed=seed, rank=rank, item_sync=sync)
         run_epoch = trainer.train_epoch
     elif mode == "stream":
         users_t, items_t, sync = t["users"], t["items"], None

@@ -826,6 +826,25 @@ class Engine:
             self._ctx, users.data_ptr(), pos.data_ptr(), _ptr(neg), users.numel(), batch_size,
             sampler, adaptive_p, seed, offset, max_inflight, _ptr(scalars)))
 
+    def train_stream_batched_scored(self, users, pos, batch_size: int, sampler: int,
+                                    neg: Optional[torch.Tensor] = None, tries: Optional[torch.Tensor] = None,
+                                    seed: int = 0, offset: int = 0, max_inflight: int = 0,
+                                    scalars: Optional[torch.Tensor] = None) -> None:
+        """`train_stream_batched` with sampler NEG_DYNAMIC or NEG_WARP (``bpr_train_stream_batched_scored``), any
+        optimizer: the draw of `sample_dynamic` / `sample_warp` on every row's view as of the previous virtual step,
+        with `set_dynamic` / `set_warp`'s values.  neg / tries (int32 [n], optional) receive the picks (-1: a triple
+        WARP skips) and WARP's tries (0: skipped; 1 for every dynamic triple).  scalars for NEG_WARP: the WARP loss,
+        the L2 term, sum |x_i - x_k| and the count, over the stepped triples."""
+        self._sync_stream()
+        if users.dtype != torch.int32 or pos.dtype != torch.int32:
+            raise ValueError("train_stream_batched_scored takes int32 id tensors")
+        for name, t in (("neg", neg), ("tries", tries)):
+            if t is not None and (t.dtype != torch.int32 or t.numel() < users.numel() or not t.is_contiguous()):
+                raise ValueError(f"train_stream_batched_scored: {name} must be a contiguous int32 tensor of n entries")
+        native.check(self._lib.bpr_train_stream_batched_scored(
+            self._ctx, users.data_ptr(), pos.data_ptr(), _ptr(neg), _ptr(tries), users.numel(), batch_size,
+            sampler, seed, offset, max_inflight, _ptr(scalars)))
+
     def shuffle_epoch(self, users: torch.Tensor, pos: torch.Tensor, seed: int,
                       out: Optional[tuple[torch.Tensor, torch.Tensor]] = None):
         """Seeded pseudo-random permutation of the training triples (on device)."""

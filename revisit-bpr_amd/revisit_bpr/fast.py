@@ -600,14 +600,15 @@ def _refuse_dynamic(sampler: str, who: str) -> None:
     if sampler == "dynamic":
         raise ValueError(f"{who}: dynamic negatives run fused in StreamTrainer(sampler='dynamic') (plain SGD); with "
                          "another optimizer draw them per batch with revisit_bpr.modules.DynamicSampler and step on "
-                         "the picks as given negatives")
+                         "the picks as given negatives, or train with ScoredBatchedStreamTrainer(sampler='dynamic')")
 
 
 def _refuse_warp(sampler: str, who: str) -> None:
     if sampler == "warp":
         raise ValueError(f"{who}: the WARP objective is fused into the plain-SGD STREAM kernel only "
                          "(StreamTrainer(sampler='warp')): its draw and its step weight are one computation on the "
-                         "live rows, and no other trainer has a kernel for it")
+                         "live rows, and no other trainer has a kernel for it but ScoredBatchedStreamTrainer"
+                         "(sampler='warp'), the batched STREAM launch with any optimizer")
 
 
 class StrictTrainer:
@@ -719,9 +720,7 @@ class BatchedStreamTrainer:
         self.users, self.items = users.contiguous(), items.contiguous()
         self.n = users.numel()
         model.bind_seen_csr(seen_indptr, seen_indices)
-        _refuse_dynamic(sampler, type(self).__name__)
-        _refuse_warp(sampler, type(self).__name__)
-        self.sampler = {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM}[sampler]
+        self.sampler = self._sampler_kind(sampler)
         self.adaptive_p, self.batch = adaptive_p, batch_size
         I, U = self.engine.I, self.engine.U
         every = max(1, int(I * math.log(I) / batch_size))  # example.py:302
@@ -748,6 +747,18 @@ class BatchedStreamTrainer:
         if item_sync is not None:
             self.rounds = item_sync.max_over_ranks(self.rounds)
 
+    def _sampler_kind(self, sampler: str) -> int:
+        _refuse_dynamic(sampler, type(self).__name__)
+        _refuse_warp(sampler, type(self).__name__)
+        return {"adaptive": eng.NEG_ADAPTIVE, "uniform": eng.NEG_UNIFORM}[sampler]
+
+    def _launch(self, lo: int, hi: int) -> None:
+        """One launch over the shuffled triples [lo, hi): the piece a subclass replaces."""
+        self.model.train_stream_batched(self.optimizer, self._pu[lo:hi], self._pi[lo:hi],
+                                        self.batch, self.sampler, adaptive_p=self.adaptive_p,
+                                        seed=self.seed, offset=(self.rank << 40) + self.drawn,
+                                        max_inflight=self.max_inflight, scalars=self._scalars)
+
     def train_epoch(self) -> dict:
         model, e = self.model, self.engine
         model.train()
@@ -761,10 +772,7 @@ class BatchedStreamTrainer:
             if lo < hi:
                 if adaptive:
                     e.adaptive_refresh()  # brings the item rows to "now" first
-                model.train_stream_batched(self.optimizer, self._pu[lo:hi], self._pi[lo:hi],
-                                           self.batch, self.sampler, adaptive_p=self.adaptive_p,
-                                           seed=self.seed, offset=(self.rank << 40) + self.drawn,
-                                           max_inflight=self.max_inflight, scalars=self._scalars)
+                self._launch(lo, hi)
                 self.drawn += hi - lo
             if self.item_sync is not None:
                 e.flush_items()
@@ -776,3 +784,39 @@ class BatchedStreamTrainer:
         cnt = max(sc[3], 1.0)
         return {"bpr_loss": sc[0] / cnt, "l2_reg": sc[1] / cnt, "logits_diff": sc[2] / cnt,
                 "loss": (sc[0] + sc[1]) / cnt, "triples": int(sc[3])}
+
+
+class ScoredBatchedStreamTrainer(BatchedStreamTrainer):
+    """`BatchedStreamTrainer`'s epochs — the shuffle, the chunks, the staleness budget, `item_sync` — with the scored
+    samplers under ANY optimizer the engine mirrors: ``sampler="dynamic"`` trains on the hardest of `candidates` unseen
+    candidates, ``sampler="warp"`` on the first of at most `max_sampled` that comes within `margin` of the positive,
+    the step weighted by log(estimated rank) (`bpr_train_stream_batched_scored`: the draw of `Engine.sample_dynamic` /
+    `sample_warp`, on every row as of the previous virtual step).  Nothing is refreshed: the draw reads the model.
+
+    WARP: `train_epoch()` returns the WARP loss in ``bpr_loss`` and the STEPPED triples in ``triples`` (a triple
+    without a violator is skipped, as in `StreamTrainer`); the optimizer still takes ceil(n / batch_size) steps."""
+
+    def __init__(self, model, optimizer, users: torch.Tensor, items: torch.Tensor,
+                 seen_indptr: torch.Tensor, seen_indices: torch.Tensor, sampler: str = "dynamic",
+                 candidates: int = 4, max_sampled: int = 10, margin: float = 1.0, batch_size: int = 256,
+                 seed: int = 13, max_inflight: Optional[int] = None, rank: int = 0, item_sync=None,
+                 world: Optional[int] = None) -> None:
+        super().__init__(model, optimizer, users, items, seen_indptr, seen_indices, sampler=sampler,
+                         batch_size=batch_size, seed=seed, max_inflight=max_inflight, rank=rank,
+                         item_sync=item_sync, world=world)
+        if self.sampler == eng.NEG_DYNAMIC:
+            self.engine.set_dynamic(candidates)
+        else:
+            self.engine.set_warp(max_sampled, margin)
+
+    def _sampler_kind(self, sampler: str) -> int:
+        if sampler not in ("dynamic", "warp"):
+            raise ValueError(f"{type(self).__name__}: sampler must be 'dynamic' or 'warp' (uniform and adaptive "
+                             "negatives: BatchedStreamTrainer)")
+        return eng.NEG_DYNAMIC if sampler == "dynamic" else eng.NEG_WARP
+
+    def _launch(self, lo: int, hi: int) -> None:
+        self.model.train_stream_batched_scored(self.optimizer, self._pu[lo:hi], self._pi[lo:hi], self.batch,
+                                               self.sampler, seed=self.seed,
+                                               offset=(self.rank << 40) + self.drawn,
+                                               max_inflight=self.max_inflight, scalars=self._scalars)

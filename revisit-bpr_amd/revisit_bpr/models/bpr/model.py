@@ -368,6 +368,22 @@ class Model(torch.nn.Module):
         triples, one torch.optim step per batch — as ONE fused launch (`bpr_train_stream_batched`,
         any optimizer): triples of neighbouring batches run concurrently, so a gradient may see
         rows that are a few steps stale (bounded by `max_inflight`).  Returns the steps taken."""
+        return self._batched_launch(optimizer, users, batch_size, lambda eng: eng.train_stream_batched(
+            users, items, batch_size, sampler=sampler, adaptive_p=adaptive_p, seed=seed, offset=offset,
+            max_inflight=max_inflight, scalars=scalars))
+
+    def train_stream_batched_scored(self, optimizer, users: torch.Tensor, items: torch.Tensor,
+                                    batch_size: int, sampler: int, seed: int = 0, offset: int = 0,
+                                    max_inflight: int = 0, scalars: Optional[torch.Tensor] = None) -> int:
+        """`train_stream_batched` with dynamic negatives or the WARP objective (`bpr_train_stream_batched_scored`;
+        sampler NEG_DYNAMIC / NEG_WARP, parameters from Engine.set_dynamic / set_warp).  Returns the steps taken:
+        ceil(n / batch_size), whatever WARP skipped."""
+        return self._batched_launch(optimizer, users, batch_size, lambda eng: eng.train_stream_batched_scored(
+            users, items, batch_size, sampler, seed=seed, offset=offset, max_inflight=max_inflight, scalars=scalars))
+
+    def _batched_launch(self, optimizer, users: torch.Tensor, batch_size: int, launch) -> int:
+        """What the batched STREAM launches share: the optimizer handed to the engine, `launch(engine)`, and torch's
+        state["step"] advanced by the steps the launch took."""
         eng = self.engine()
         self._reset_reg()
         if self._pending:
@@ -377,9 +393,7 @@ class Model(torch.nn.Module):
         if len(groups) != 1:
             raise ValueError("the fused tables must sit in exactly one param group")
         kind = self._configure_optimizer(optimizer, groups[0])
-        eng.train_stream_batched(users, items, batch_size, sampler=sampler, adaptive_p=adaptive_p,
-                                 seed=seed, offset=offset, max_inflight=max_inflight,
-                                 scalars=scalars)
+        launch(eng)
         steps = (users.numel() + batch_size - 1) // batch_size
         if kind != 0:
             for prm in self._fused_params():

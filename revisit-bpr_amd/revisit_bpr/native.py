@@ -113,6 +113,8 @@ SIGNATURES = {
     "bpr_hot_fold": (c_int, [c_void_p]),
     "bpr_train_stream_batched": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                          c_int32, c_float, c_uint64, c_uint64, c_int64, c_void_p]),
+    "bpr_train_stream_batched_scored": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                                c_int32, c_uint64, c_uint64, c_int64, c_void_p]),
     "bpr_shuffle_epoch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_uint64, c_void_p,
                                   c_void_p]),
     "bpr_train_strict": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,

@@ -1,0 +1,289 @@
+"""A numpy model of bpr_train_stream_batched_scored in its sequential limit (max_inflight = 1): the reference's exact
+mini-batch loop with the scored draws, composed from the models the project already has.
+
+  the draw       tests/dynamic_model.py (the candidate stream, acceptance, the rank fallback, `choose`) and
+                 tests/warp_model.py (`weight`), imported unchanged.  `draw` restates their `pick` / `draw` with the
+                 score's precision as a parameter (float64: theirs, which tests/test_vstream_scored_cpu.py pins; float32:
+                 what a kernel may decide differently) and returns the DECIDING GAP beside the pick.
+  the view       every row the draw and the gradient read is the row as of the previous step: in the sequential limit,
+                 the tables before the batch's optimizer step.
+  the gradient   per triple the BPR gradient with weight w in the place of sigma(-x) — w = sigma(-x) for dynamic
+                 negatives, w = L = warp_model.weight(n_unseen, tries) for WARP — summed over the STEPPED triples of the
+                 batch in float64 and rounded once; the pad embedding rows' gradients dropped (oracle.dense_grad's rules).
+  the step       one dense optimizer step per batch: `oracle.opt_dense` (SGD, momentum / Nesterov, Adam, RMSprop; the
+                 optimizer the sequential-limit tests of tests/test_gpu_vstream.py hold the uniform kind to) on the whole
+                 tables — a row outside the batch, or touched by skipped triples only, takes its zero-gradient step —
+                 and `adagrad_model.update` on the touched rows for Adagrad (whose zero-gradient step moves nothing).
+  a skipped      WARP triple (no violator) adds to no gradient and to no scalar; its batch still takes step t: an
+                 all-skipped batch advances Adam's bias correction and decays every row by one zero-gradient step.
+
+The deciding gap: dynamic — best score less the best score of any OTHER item (inf when there is none); WARP — the
+smallest |x_k - (x_i - margin)| over the candidates up to and including the violator (all of them when skipped).  Two
+sets of tables that agree to tol * max(1, |w|) per element give scores within tol * (|p|_1 + |q|_1 + 1) of each other, so
+a pick can differ only where the gap is below `gap_bound`: twice that, plus the fp32 rounding margin of the two models.
+"""
+import math
+
+import numpy as np
+
+import adagrad_model as am
+import dynamic_model as dm
+import oracle
+import warp_model as wm
+
+F = np.float32
+DYNAMIC, WARP = 3, 4  # BPR_NEG_DYNAMIC, BPR_NEG_WARP
+ADAGRAD = 4           # BPR_OPT_ADAGRAD
+
+
+def scores(p, Q, bias, items, dtype=np.float64):
+    """(score, sum|p q| + |b|) per item; float64 is dynamic_model.scores, float32 sums in the table's own precision."""
+    if dtype == np.float64:
+        return dm.scores(p, Q, bias, items)
+    rows = Q[items].astype(dtype)
+    prod = rows * p.astype(dtype)
+    b = np.zeros(len(items), dtype) if bias is None else bias[items].astype(dtype)
+    with np.errstate(invalid="ignore"):
+        return (prod.sum(1, dtype=dtype) + b).astype(np.float64), (np.abs(prod).sum(1) + np.abs(b)).astype(np.float64)
+
+
+def draw(kind, seed, t, u, i, K, margin, P, Q, bias, seen, dtype=np.float64):
+    """One triple's draw on the tables as given.  dict: item (-1: skipped), tries (0: skipped; 1 for dynamic), weight
+    (WARP's L; None for dynamic), x_pos, x_neg, cands, accepted, gap, mags (the largest sum|p q| + |b| looked at)."""
+    I = Q.shape[0]
+    a = dm.accepted(seed, t, seen, I, K)
+    n_acc = len(a)
+    if not a:
+        a = [dm.rank_pick(seed, t, seen, I)]
+    items = np.asarray(a, np.int64)
+    if kind == DYNAMIC:
+        s, mags = scores(P[u], Q, bias, items, dtype)
+        k = dm.choose(s)
+        others = s[(items != items[k]) & ~np.isnan(s)]
+        gap = float(s[k] - others.max()) if others.size and not np.isnan(s[k]) else math.inf
+        return dict(item=int(items[k]), tries=1, weight=None, x_pos=0.0, x_neg=float(s[k]), cands=a, accepted=n_acc,
+                    gap=gap, mags=float(mags.max()))
+    s, mags = scores(P[u], Q, bias, np.concatenate([[i], items]), dtype)
+    x_i = s[0]
+    out = dict(item=-1, tries=0, weight=0.0, x_pos=float(x_i), x_neg=0.0, cands=a, accepted=n_acc, gap=math.inf,
+               mags=float(mags.max()))
+    for k in range(1, len(a) + 1):
+        if np.isnan(s[k]) or np.isnan(x_i):
+            continue  # compares false
+        g = float(s[k] - (x_i - margin))
+        out["gap"] = min(out["gap"], abs(g))
+        if g > 0:
+            out.update(item=int(a[k - 1]), tries=k, x_neg=float(s[k]), weight=wm.weight((I - 1) - len(seen), k))
+            break
+    return out
+
+
+def gap_bound(tol, d, p, Q, bias, items, mags):
+    """Below this deciding gap two models whose tables agree to tol * max(1, |w|) may pick differently (see above)."""
+    l1q = np.abs(Q[items].astype(np.float64)).sum(1).max()
+    table = 2.0 * tol * (np.abs(p.astype(np.float64)).sum() + l1q + 1.0)
+    return table + 2.0 * (2.0 * (d + 1) * 2.0 ** -24 * mags)
+
+
+def batch_grad(P, Q, bias, users, pos, neg, w, alphas, pad_user=0, pad_item=0):
+    """Dense gradient of one batch, triple k weighted by w[k] in the place of sigma(-x) (None: sigma(-x) itself), over
+    the triples with neg >= 0.  Returns (gP, gQ, gb or None, touched user rows, item rows, bias entries, x)."""
+    gP, gQ = np.zeros(P.shape, np.float64), np.zeros(Q.shape, np.float64)
+    gb = None if bias is None else np.zeros(bias.shape, np.float64)
+    au, ai, an = (float(F(a)) for a in alphas)
+    tu, ti, tb = set(), set(), set()
+    xs = np.zeros(len(users))
+    for k in range(len(users)):
+        u, i, j = int(users[k]), int(pos[k]), int(neg[k])
+        if j < 0:
+            continue
+        p, qi, qj = (r.astype(np.float64) for r in (P[u], Q[i], Q[j]))
+        x = p @ (qi - qj) + (0.0 if bias is None else float(bias[i]) - float(bias[j]))
+        xs[k] = x
+        wk = 1.0 / (1.0 + math.exp(x)) if w is None else float(w[k])
+        if u != pad_user:
+            gP[u] += -wk * (qi - qj) + au * p
+            tu.add(u)
+        if i != pad_item:
+            gQ[i] += -wk * p + ai * qi
+            ti.add(i)
+        if j != pad_item:
+            gQ[j] += wk * p + an * qj
+            ti.add(j)
+        if gb is not None:
+            gb[i] -= wk
+            gb[j] += wk
+            tb.update((i, j))
+    return (gP.astype(F), gQ.astype(F), None if gb is None else gb.astype(F),
+            np.array(sorted(tu), np.int64), np.array(sorted(ti), np.int64), np.array(sorted(tb), np.int64), xs)
+
+
+def new_state(P, Q, bias, cfg, iav=0.0):
+    """Optimizer state as the engine allocates it: zeros; Adagrad's sums at initial_accumulator_value."""
+    fill = iav if cfg["kind"] == ADAGRAD else 0.0
+    st = {"mP": np.zeros_like(P), "vP": np.full_like(P, fill), "mQ": np.zeros_like(Q), "vQ": np.full_like(Q, fill)}
+    if bias is not None:
+        st["mb"], st["vb"] = np.zeros_like(bias), np.full_like(bias, fill)
+    return st
+
+
+def opt_step(P, Q, bias, st, g, rows, cfg, t):
+    """One dense optimizer step t on the three tables, in place."""
+    gP, gQ, gb = g
+    if cfg["kind"] == ADAGRAD:
+        c = am.clr(cfg["lr"], cfg.get("lr_decay", 0.0), t, abi=True)
+        eps = cfg.get("eps", 1e-10)
+        am.update(P, st["vP"], gP, rows[0], c, eps)
+        am.update(Q, st["vQ"], gQ, rows[1], c, eps)
+        if bias is not None:
+            am.update(bias, st["vb"], gb, rows[2], c, eps)
+        return
+    opt = oracle.make_opt(cfg["kind"], **{k: v for k, v in cfg.items() if k != "kind"})
+    oracle.opt_dense(opt, t, P, gP, st["mP"], st["vP"])
+    oracle.opt_dense(opt, t, Q, gQ, st["mQ"], st["vQ"])
+    if bias is not None:
+        oracle.opt_dense(opt, t, bias, gb, st["mb"], st["vb"])
+
+
+def run(P, Q, bias, indptr, indices, users, pos, B, kind, K, margin, cfg, alphas, seed, offset=0, t0=0, state=None,
+        given=None, tol=0.0, also=None):
+    """The mini-batch loop over users / pos in batches of B, steps t0 + 1 ..., in place on P, Q, bias and `state`.
+    Every triple is drawn on the model's own pre-step tables; the step takes the model's picks, or — given = (neg,
+    tries) — the reported ones (the model then follows whoever reported them, and its own picks are what that one should
+    have drawn).  also: a second precision for the scores (np.float32); its picks go to neg_also / tries_also.
+    Returns dict(neg, tries, gap, bound, scalars [4] float64, state, rows = three sets of touched rows, steps)."""
+    n, d = len(users), P.shape[1]
+    st = state if state is not None else new_state(P, Q, bias, cfg)
+    out = dict(neg=np.zeros(n, np.int32), tries=np.zeros(n, np.int32), gap=np.full(n, math.inf), bound=np.zeros(n),
+               neg_also=np.zeros(n, np.int32), tries_also=np.zeros(n, np.int32), scalars=np.zeros(4), state=st,
+               rows=[set(), set(), set()])
+    seen_of = {}
+    au, ai, an = (float(F(a)) for a in alphas)
+    for b_idx, lo in enumerate(range(0, n, B)):
+        hi = min(lo + B, n)
+        L = np.zeros(hi - lo)
+        for k in range(lo, hi):
+            u, i = int(users[k]), int(pos[k])
+            if u not in seen_of:
+                seen_of[u] = set(indices[indptr[u]:indptr[u + 1]].tolist())
+            r = draw(kind, seed, offset + k, u, i, K, margin, P, Q, bias, seen_of[u])
+            out["neg"][k], out["tries"][k], out["gap"][k] = r["item"], r["tries"], r["gap"]
+            items = np.asarray(r["cands"] + [i], np.int64)
+            out["bound"][k] = gap_bound(tol, d, P[u], Q, bias, items, r["mags"])
+            if also is not None:
+                r2 = draw(kind, seed, offset + k, u, i, K, margin, P, Q, bias, seen_of[u], also)
+                out["neg_also"][k], out["tries_also"][k] = r2["item"], r2["tries"]
+        neg = out["neg"][lo:hi] if given is None else given[0][lo:hi]
+        tries = out["tries"][lo:hi] if given is None else given[1][lo:hi]
+        w = None
+        if kind == WARP:
+            for k in range(lo, hi):
+                if neg[k - lo] >= 0:
+                    n_unseen = (Q.shape[0] - 1) - len(seen_of[int(users[k])])
+                    L[k - lo] = wm.weight(n_unseen, int(tries[k - lo]))
+            w = L
+        gP, gQ, gb, ru, ri, rb, xs = batch_grad(P, Q, bias, users[lo:hi], pos[lo:hi], neg, w, alphas)
+        for k in range(lo, hi):  # the scalars, on the pre-step rows
+            j = int(neg[k - lo])
+            if j < 0:
+                continue
+            u, i = int(users[k]), int(pos[k])
+            p, qi, qj = (r_.astype(np.float64) for r_ in (P[u], Q[i], Q[j]))
+            x = xs[k - lo]
+            loss = L[k - lo] * (margin - x) if kind == WARP else max(-x, 0.0) + math.log1p(math.exp(-abs(x)))
+            out["scalars"] += (loss, 0.5 * (ai * qi @ qi + an * qj @ qj + au * p @ p), abs(x), 1.0)
+        opt_step(P, Q, bias, st, (gP, gQ, gb), (ru, ri, rb), cfg, t0 + b_idx + 1)
+        for s, rws in zip(out["rows"], (ru, ri, rb)):
+            s.update(int(x) for x in rws)
+    out["steps"] = -(-n // B)
+    return out
+
+
+def uniform_loop(P, Q, bias, indptr, indices, users, pos, B, cfg, alphas, seed, offset=0):
+    """The uniform mini-batch loop the sequential-limit tests hold bpr_train_stream_batched to: oracle.sample_uniform,
+    then the same gradient and optimizer step.  What M = 1 must degenerate to."""
+    st = new_state(P, Q, bias, cfg)
+    negs = np.zeros(len(users), np.int32)
+    for b_idx, lo in enumerate(range(0, len(users), B)):
+        sl = slice(lo, lo + B)
+        neg = oracle.sample_uniform(indptr, indices, Q.shape[0], users[sl], seed, offset + lo)
+        negs[sl] = neg
+        gP, gQ, gb, ru, ri, rb, _ = batch_grad(P, Q, bias, users[sl], pos[sl], neg, None, alphas)
+        opt_step(P, Q, bias, st, (gP, gQ, gb), (ru, ri, rb), cfg, b_idx + 1)
+    return negs, st
+
+
+def problem(U, I, d, bias, seed, scale=1.0):
+    """Tables uniform in +-scale/2 (pad rows zero), a seen CSR in which user U-1 has seen all but ONE item (the rank
+    fallback) and user U-2 all but THREE, and the (user, seen item) pairs as the triple pool."""
+    rng = np.random.default_rng(seed)
+    P = ((rng.random((U, d)) - 0.5) * scale).astype(F)
+    Q = ((rng.random((I, d)) - 0.5) * scale).astype(F)
+    P[0] = 0
+    Q[0] = 0
+    b = np.linspace(-0.1, 0.1, I).astype(F) if bias else None
+    rows = [np.zeros(0, np.int32)]
+    for u in range(1, U):
+        if u == U - 1:
+            s = np.setdiff1d(np.arange(1, I), [I // 2])
+        elif u == U - 2:
+            s = np.setdiff1d(np.arange(1, I), [3, I // 3, I - 2])
+        else:
+            s = np.sort(rng.choice(np.arange(1, I), size=int(rng.integers(3, 11)), replace=False))
+        rows.append(s.astype(np.int32))
+    indptr = np.zeros(U + 1, np.int64)
+    indptr[1:] = np.cumsum([len(r) for r in rows])
+    indices = np.concatenate(rows).astype(np.int32)
+    return P, Q, b, indptr, indices
+
+
+def triples(indptr, indices, n, seed, heavy=4):
+    """n shuffled (user, positive) pairs from the seen CSR, the two nearly-saturated users `heavy` times each."""
+    rng = np.random.default_rng(seed)
+    U = len(indptr) - 1
+    us = np.repeat(np.arange(U), np.diff(indptr)).astype(np.int32)
+    light = np.flatnonzero(us < U - 2)
+    pick = rng.choice(light, size=n - 2 * heavy, replace=len(light) < n)
+    extra = np.concatenate([rng.choice(np.flatnonzero(us == U - 1), heavy), rng.choice(np.flatnonzero(us == U - 2), heavy)])
+    sel = rng.permutation(np.concatenate([pick, extra]))
+    return us[sel].copy(), indices[sel].astype(np.int32).copy()
+
+
+# ---- what tests/test_vstream_scored_cpu.py and tests/test_gpu_vstream_scored.py share ------------------------------------
+REG = (0.0016, 0.0001, 0.00375)
+U, I, N = 40, 64, 200
+SCALE = 1.0   # tables uniform in +-0.5: scores spread as scale^2, the gap bound as scale
+TOL = 2e-5    # tests/test_gpu_vstream.py `agree` and tests/test_gpu_adagrad.py TOL: the sequential-limit tolerance
+CAP = 0.02    # share of triples a later batch's pick may be excused on
+# the optimizers of tests/test_gpu_vstream.py OPTS (one per kind) and tests/test_gpu_adagrad.py's Adagrad
+OPTS = {
+    "sgd": dict(kind=0, lr=0.05),
+    "nesterov": dict(kind=1, lr=0.01, momentum=0.9, nesterov=True),
+    "adam_09": dict(kind=2, lr=0.003, betas=(0.9, 0.999)),
+    "rmsprop": dict(kind=3, lr=0.0005, alpha=0.9),
+    "adagrad": dict(kind=4, lr=0.05, eps=1e-10, lr_decay=0.05),
+}
+# later batches' picks (GPU test 4; the CPU file holds fp32 against fp64 scoring to the same cap on the same seeds):
+# (d, bias, optimizer, sampler kind, K, B, seed)
+PICK_CASES = [
+    (32, True, "adam_09", DYNAMIC, 4, 32, 11),
+    (128, False, "adagrad", DYNAMIC, 32, 4, 12),
+    (256, True, "nesterov", DYNAMIC, 4, 32, 13),
+    (32, False, "adagrad", WARP, 10, 32, 14),
+    (128, True, "adam_09", WARP, 32, 4, 15),
+    (256, False, "rmsprop", WARP, 10, 32, 16),
+]
+
+
+def warp_margin(d):
+    """The margin of the WARP cases at width d, an exact float32: the scores spread as sqrt(d) / 12, the margin is a
+    quarter of that, so about two candidates in five do not violate — tries > 1 is common, and a triple is skipped
+    mostly at max_sampled = 1 and for the nearly saturated users, whose candidates are one item over and over."""
+    return float(F(0.02 * math.sqrt(d)))
+
+
+def excused(got_neg, got_tries, res):
+    """(disagreeing triples, those of them with the deciding gap NOT below the bound) of reported picks against a
+    `run` result."""
+    diff = (got_neg != res["neg"]) | (got_tries != res["tries"])
+    return int(diff.sum()), int((diff & ~(res["gap"] < res["bound"])).sum())
