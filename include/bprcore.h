@@ -700,6 +700,29 @@ int bpr_topk_rows(const float* P, const float* Q, const float* item_bias /* or N
                   void* workspace, int64_t workspace_bytes,
                   int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
 
+/* ---- the item filter of the first-stage calls: "only these items" (in stock, of a category, licensed, not on a
+ * block list) as one more eligibility rule inside the kernel, beside "not item 0" and "not in the seen row".
+ * item_filter is a device bitmap of uint32 words, bit (i & 31) of word (i >> 5) set = item i is eligible;
+ * 4 * ceil(I / 128) words long (a whole number of the kernels' item tiles), its start 16-byte aligned (else
+ * BPR_ERR_INVALID under the _filtered entry's name), bits at or past I zero (and never read as items if they are not).
+ * Item 0 stays out whatever its bit says; the seen CSR and the NaN rule apply as before.  csrc/bpr_item_filter.h
+ * states the layout for host and device.  NULL: the call IS its unfiltered parent — the same kernel instantiation,
+ * the same bits.  Each _filtered entry has its parent's signature with item_filter behind seen_indices, its parent's
+ * refusals in its parent's order under its own name, and its parent's _workspace / _slices queries (the plan does not
+ * look at the filter).
+ * Scores are untouched: a filtered result is, bit for bit, the unfiltered ranking restricted to the eligible items,
+ * cut to k and padded with -1 / -inf — whatever n, the rows' order, item_slices, and however many tiles held no
+ * eligible item and were skipped (a narrow filter costs in proportion to the tiles it touches).
+ * bpr_sample_rows_filtered: the k draws are over the eligible items, and log_z_out is the normaliser over the
+ * eligible, unseen, non-NaN items only (-inf when there is none), under bpr_sample_rows' tolerance contract. */
+int bpr_topk_rows_filtered(const float* P, const float* Q, const float* item_bias /* or NULL */, int64_t I, int32_t d,
+                           const int32_t* users, int64_t n,
+                           const int64_t* seen_indptr /* or NULL */, const int32_t* seen_indices,
+                           const uint32_t* item_filter /* [4 * ceil(I / 128)] or NULL */,
+                           int32_t k, int32_t item_slices /* 0 = choose */,
+                           void* workspace, int64_t workspace_bytes,
+                           int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
+
 /* ---- deep retrieval: bpr_topk_rows for 1 <= k <= 1024, the first stage of a two-stage recommender (candidates for
  * bpr_rerank_rows, a downstream ranker or a business-rule filter).  Its own fused kernel (csrc/bpr_retrieve.hip):
  * the rows' candidate buffers live in the device workspace and are compacted by a sort in LDS, and a bounded number
@@ -727,6 +750,14 @@ int bpr_retrieve_rows(const float* P, const float* Q, const float* item_bias /* 
                       int32_t k, int32_t item_slices /* 0 = choose */,
                       void* workspace, int64_t workspace_bytes,
                       int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
+/* bpr_retrieve_rows over the eligible items of an item filter (see bpr_topk_rows_filtered) */
+int bpr_retrieve_rows_filtered(const float* P, const float* Q, const float* item_bias /* or NULL */, int64_t I,
+                               int32_t d, const int32_t* users, int64_t n,
+                               const int64_t* seen_indptr /* or NULL */, const int32_t* seen_indices,
+                               const uint32_t* item_filter /* [4 * ceil(I / 128)] or NULL */,
+                               int32_t k, int32_t item_slices /* 0 = choose */,
+                               void* workspace, int64_t workspace_bytes,
+                               int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
 
 /* ---- sampling: k unseen items per user drawn WITHOUT replacement from softmax(s(u, .) / temperature) over the
  * user's eligible items (the Plackett-Luce model) — exploration, and logs that off-policy evaluation can use.  The
@@ -769,6 +800,17 @@ int bpr_sample_rows(const float* P, const float* Q, const float* item_bias /* or
                     void* workspace, int64_t workspace_bytes,
                     int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, float* keys_out /* [n,k] or NULL */,
                     float* log_z_out /* [n] or NULL */, void* hip_stream);
+/* bpr_sample_rows over the eligible items of an item filter (see bpr_topk_rows_filtered) */
+int bpr_sample_rows_filtered(const float* P, const float* Q, const float* item_bias /* or NULL */, int64_t I,
+                             int32_t d, const int32_t* users, int64_t n,
+                             const int64_t* draw_ids /* [n] or NULL = the user id */,
+                             const int64_t* seen_indptr /* or NULL */, const int32_t* seen_indices,
+                             const uint32_t* item_filter /* [4 * ceil(I / 128)] or NULL */,
+                             int32_t k, float temperature, uint64_t seed, int32_t item_slices /* 0 = choose */,
+                             void* workspace, int64_t workspace_bytes,
+                             int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */,
+                             float* keys_out /* [n,k] or NULL */, float* log_z_out /* [n] or NULL */,
+                             void* hip_stream);
 
 /* ---- ranking of held-out items: where each target of a row stands among the user's eligible items (the reference
  * measures through full logits: example.py:195-230 and experiments/bpr/exp.py:369-374, an argsort of I scores per

@@ -49,6 +49,7 @@
 
 #include <string>
 
+#include "bpr_item_filter.h"
 #include "bpr_retrieve_plan.h"
 #include "bpr_serving_host.h"
 #include "bpr_topk_shared.h"
@@ -116,8 +117,10 @@ __device__ __forceinline__ int sort_row(const Cand* buf, int c, int checked, con
 }
 
 // VEC: d % 4 == 0 and 16-byte aligned tables (16-byte global loads); else element loads.
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_retrieve(const RetrieveArgs a) {
+// FILT: an item filter (bpr_item_filter.h) lies behind the arguments: an item whose bit is clear is not eligible, and
+// the loop walks the unit's non-empty tiles only.  Without it the kernel is what it was before there were filters.
+template <bool VEC, bool FILT>
+__global__ __launch_bounds__(256) void k_retrieve(const MaybeFiltered<FILT, RetrieveArgs> a) {
   constexpr int TU = TOPK_TU, TI = TOPK_TI, KC = TOPK_KC, LD = TOPK_LD;
   extern __shared__ __align__(16) unsigned char smem[];
   const int cap = a.cap;
@@ -194,8 +197,19 @@ __global__ __launch_bounds__(256) void k_retrieve(const RetrieveArgs a) {
                       sSeenLen[row], scratch, lane);
     };
 
-    if (t0 < t1) fetch(t0, 0);
-    for (int64_t t = t0; t < t1; ++t) {
+    // The walk.  FILT: the unit's non-empty tiles only — tile_from(t) is the first of them at or after t, or t1,
+    // and tn the one after the current tile, found once a tile for the prefetch and the step.  (Written so that
+    // without a filter the loop is `for (t = t0; t < t1; ++t)` to the compiler: profiles/item_filter_resources.md.)
+    auto tile_from = [&](int64_t t) -> int64_t {
+      if constexpr (FILT) return filter_next_tile(a.filter, a.I, t, t1);
+      else return t;
+    };
+    int64_t tn = 0;
+    auto next = [&](int64_t t) -> int64_t { return FILT ? tn : t + 1; };
+    const int64_t first = tile_from(t0);
+    if (first < t1) fetch(first, 0);
+    for (int64_t t = first; t < t1; t = next(t)) {
+      if constexpr (FILT) tn = tile_from(t + 1);
       f32x16 acc0 = {0.f}, acc1 = {0.f};
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.f;
@@ -204,7 +218,7 @@ __global__ __launch_bounds__(256) void k_retrieve(const RetrieveArgs a) {
         stash();
         __syncthreads();
         if (c + 1 < nch) fetch(t, c + 1);
-        else if (t + 1 < t1) fetch(t + 1, 0);
+        else if (next(t) < t1) fetch(next(t), 0);
         mfma_chunk2(qa, pb0, pb1, acc0, acc1);
       }
 
@@ -216,6 +230,9 @@ __global__ __launch_bounds__(256) void k_retrieve(const RetrieveArgs a) {
         const int64_t item = ibase + (q & 3) + 8 * (q >> 2);
         bv[q] = has_bias && item < a.I ? a.bias[item] : 0.f;
       }
+      // the wave's word of the filter: bit j is item t * TI + 32 w + j
+      uint32_t fw = 0;
+      if constexpr (FILT) fw = filter_wave_word(a.filter, a.I, t, __builtin_amdgcn_readfirstlane(w));
       // (A) how many scores beat the row's threshold
       unsigned m0 = 0, m1 = 0;
       {
@@ -223,7 +240,7 @@ __global__ __launch_bounds__(256) void k_retrieve(const RetrieveArgs a) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
           const int64_t item = ibase + (q & 3) + 8 * (q >> 2);
-          const bool ok = item > 0 && item < a.I;
+          const bool ok = item > 0 && item < a.I && (!FILT || ((fw >> (4 * h + (q & 3) + 8 * (q >> 2))) & 1u));
           const float s0 = has_bias ? acc0[q] + bv[q] : acc0[q];
           const float s1 = has_bias ? acc1[q] + bv[q] : acc1[q];
           if (ok && better(s0, (int)item, tau0.s, tau0.i)) m0 |= 1u << q;
@@ -316,16 +333,23 @@ extern "C" int bpr_retrieve_slices(int64_t n, int64_t I, int32_t d, int32_t k, i
   return BPR_OK;
 }
 
-extern "C" int bpr_retrieve_rows(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
-                                 const int32_t* users, int64_t n, const int64_t* seen_indptr,
-                                 const int32_t* seen_indices, int32_t k, int32_t item_slices, void* workspace,
-                                 int64_t workspace_bytes, int32_t* items_out, float* scores_out, void* hip_stream) {
-  using namespace bpr;
-  if (int rc = check_topk_shape("bpr_retrieve_rows", n, I, d, k, RETRIEVE_MAX, item_slices, "I")) return rc;
+namespace bpr {
+namespace {
+
+// bpr_retrieve_rows (rows = "_rows", no filter) and bpr_retrieve_rows_filtered (rows = "_rows_filtered"): one body,
+// the messages under the entry point's own name.  The plan does not look at the filter.
+int retrieve_rows(const char* rows, const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                  const int32_t* users, int64_t n, const int64_t* seen_indptr, const int32_t* seen_indices,
+                  const uint32_t* item_filter, int32_t k, int32_t item_slices, void* workspace,
+                  int64_t workspace_bytes, int32_t* items_out, float* scores_out, void* hip_stream) {
+  const std::string who = std::string("bpr_retrieve") + rows;
+  if (int rc = check_topk_shape(who.c_str(), n, I, d, k, RETRIEVE_MAX, item_slices, "I")) return rc;
   if (n > 0 && (!P || !Q || !users || !items_out || !scores_out))
-    return fail(BPR_ERR_INVALID, "bpr_retrieve_rows: P, Q, users, items_out or scores_out is NULL");
+    return fail(BPR_ERR_INVALID, who + ": P, Q, users, items_out or scores_out is NULL");
+  if (int rc = check_item_filter(who.c_str(), item_filter)) return rc;
   const RetrievePlan p = plan_retrieve(n, I, k, item_slices);
-  if (int rc = check_workspace("bpr_retrieve", workspace, workspace_bytes, p.ws_bytes, "workspace", true)) return rc;
+  if (int rc = check_workspace("bpr_retrieve", workspace, workspace_bytes, p.ws_bytes, "workspace", true, rows))
+    return rc;
   if (n == 0) return BPR_OK;
 
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -336,10 +360,40 @@ extern "C" int bpr_retrieve_rows(const float* P, const float* Q, const float* it
   // the rows' candidate buffers lie behind the slices' partial lists
   a.bufs = reinterpret_cast<Cand*>(reinterpret_cast<unsigned char*>(workspace) + p.part_bytes);
   slice_outputs(workspace, n, p.slices, k, scores_out, items_out, &a.out_scores, &a.out_items);
-  if (int rc = launch_kernel(vec_path(d, P, Q) ? k_retrieve<true> : k_retrieve<false>,
-                             retrieve_lds_bytes(RETRIEVE_MAX), dim3((unsigned)p.grid), dim3(256), p.lds, stream, a))
+  const bool vec = vec_path(d, P, Q);
+  if (item_filter != nullptr) {
+    Filtered<RetrieveArgs> f = {};
+    static_cast<RetrieveArgs&>(f) = a;
+    f.filter = item_filter;
+    if (int rc = launch_kernel(vec ? k_retrieve<true, true> : k_retrieve<false, true>,
+                               retrieve_lds_bytes(RETRIEVE_MAX), dim3((unsigned)p.grid), dim3(256), p.lds, stream, f))
+      return rc;
+  } else if (int rc = launch_kernel(vec ? k_retrieve<true, false> : k_retrieve<false, false>,
+                                    retrieve_lds_bytes(RETRIEVE_MAX), dim3((unsigned)p.grid), dim3(256), p.lds,
+                                    stream, a)) {
     return rc;
+  }
   return launch_topk_merge(a.out_scores, a.out_items, n, p.slices, k, p.merge_lds, scores_out, items_out, stream);
+}
+
+}  // namespace
+}  // namespace bpr
+
+extern "C" int bpr_retrieve_rows(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                                 const int32_t* users, int64_t n, const int64_t* seen_indptr,
+                                 const int32_t* seen_indices, int32_t k, int32_t item_slices, void* workspace,
+                                 int64_t workspace_bytes, int32_t* items_out, float* scores_out, void* hip_stream) {
+  return bpr::retrieve_rows("_rows", P, Q, item_bias, I, d, users, n, seen_indptr, seen_indices, nullptr, k,
+                            item_slices, workspace, workspace_bytes, items_out, scores_out, hip_stream);
+}
+
+extern "C" int bpr_retrieve_rows_filtered(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                                          const int32_t* users, int64_t n, const int64_t* seen_indptr,
+                                          const int32_t* seen_indices, const uint32_t* item_filter, int32_t k,
+                                          int32_t item_slices, void* workspace, int64_t workspace_bytes,
+                                          int32_t* items_out, float* scores_out, void* hip_stream) {
+  return bpr::retrieve_rows("_rows_filtered", P, Q, item_bias, I, d, users, n, seen_indptr, seen_indices, item_filter,
+                            k, item_slices, workspace, workspace_bytes, items_out, scores_out, hip_stream);
 }
 
 // Test hook, not API (tests/test_retrieve_cpu.py sets its signature): the plan of a shape.  in = {n, I, d, k,

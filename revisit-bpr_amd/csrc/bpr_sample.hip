@@ -32,6 +32,7 @@
 #include <cmath>
 #include <string>
 
+#include "bpr_item_filter.h"
 #include "bpr_sample_plan.h"
 #include "bpr_sample_shared.h"
 #include "bpr_serving_host.h"
@@ -69,8 +70,11 @@ __device__ __forceinline__ float2 lse_combine(const float2 a, const float2 b) {
 }
 
 // VEC: d % 4 == 0 and 16-byte aligned tables (16-byte global loads); else element loads.
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
+// FILT: an item filter (bpr_item_filter.h) lies behind the arguments: an item whose bit is clear is not eligible, and
+// the loop walks the slice's non-empty tiles only.  Without it the kernel is what it was before there were filters.
+// log_z is then the normaliser over the eligible items: the same bit gates its mask.
+template <bool VEC, bool FILT>
+__global__ __launch_bounds__(256) void k_sample(const MaybeFiltered<FILT, SampleArgs> a) {
   constexpr int TU = TOPK_TU, TI = TOPK_TI, KC = TOPK_KC, LD = TOPK_LD;
   extern __shared__ __align__(16) unsigned char smem[];
   const int cap = a.k + TI;
@@ -160,8 +164,19 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
   const float* const qa = sQ + (32 * w + r) * LD + 4 * h;
   const float* const pb0 = sP + r * LD + 4 * h;
   const float* const pb1 = sP + (32 + r) * LD + 4 * h;
-  if (t0 < t1) fetch(t0, 0);
-  for (int64_t t = t0; t < t1; ++t) {
+  // The walk.  FILT: the slice's non-empty tiles only — tile_from(t) is the first of them at or after t, or t1,
+  // and tn the one after the current tile, found once a tile for the prefetch and the step.  (Written so that
+  // without a filter the loop is `for (t = t0; t < t1; ++t)` to the compiler: profiles/item_filter_resources.md.)
+  auto tile_from = [&](int64_t t) -> int64_t {
+    if constexpr (FILT) return filter_next_tile(a.filter, a.I, t, t1);
+    else return t;
+  };
+  int64_t tn = 0;
+  auto next = [&](int64_t t) -> int64_t { return FILT ? tn : t + 1; };
+  const int64_t first = tile_from(t0);
+  if (first < t1) fetch(first, 0);
+  for (int64_t t = first; t < t1; t = next(t)) {
+    if constexpr (FILT) tn = tile_from(t + 1);
     f32x16 acc0 = {0.f}, acc1 = {0.f};
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.f;
@@ -170,7 +185,7 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
       stash();
       __syncthreads();
       if (c + 1 < nch) fetch(t, c + 1);
-      else if (t + 1 < t1) fetch(t + 1, 0);
+      else if (next(t) < t1) fetch(next(t), 0);
       mfma_chunk2(qa, pb0, pb1, acc0, acc1);
     }
 
@@ -201,6 +216,9 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
     // ---- epilogue of the item tile: register q of the lane is item ibase + (q & 3) + 8 (q >> 2) of users r, 32 + r
     const int64_t ibase = t * TI + 32 * w + 4 * h;
     const bool has_bias = a.bias != nullptr;
+    // the wave's word of the filter: bit j is item t * TI + 32 w + j
+    uint32_t fw = 0;
+    if constexpr (FILT) fw = filter_wave_word(a.filter, a.I, t, __builtin_amdgcn_readfirstlane(w));
     // scores -> keys, in place; log_z's per-lane (max, sum) of the tile on the way
     {
       float x0[16], x1[16];  // score * inv_temp (log_z only)
@@ -231,7 +249,7 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
         for (int q = 0; q < 16; ++q) {
           const int bit = 4 * h + (q & 3) + 8 * (q >> 2);
           const int64_t item = ibase + (q & 3) + 8 * (q >> 2);
-          const bool ok = item > 0 && item < a.I;
+          const bool ok = item > 0 && item < a.I && (!FILT || ((fw >> bit) & 1u));
           if (ok && !((seen0 >> bit) & 1u) && x0[q] == x0[q]) { e0 |= 1u << q; m0 = fmaxf(m0, x0[q]); }
           if (ok && !((seen1 >> bit) & 1u) && x1[q] == x1[q]) { e1 |= 1u << q; m1 = fmaxf(m1, x1[q]); }
         }
@@ -257,7 +275,7 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int64_t item = ibase + (q & 3) + 8 * (q >> 2);
-        const bool ok = item > 0 && item < a.I;
+        const bool ok = item > 0 && item < a.I && (!FILT || ((fw >> (4 * h + (q & 3) + 8 * (q >> 2))) & 1u));
         if (ok && better(acc0[q], (int)item, tau0.s, tau0.i)) m0 |= 1u << q;
         if (ok && better(acc1[q], (int)item, tau1.s, tau1.i)) m1 |= 1u << q;
       }
@@ -380,21 +398,28 @@ extern "C" int bpr_sample_slices(int64_t n, int64_t I, int32_t d, int32_t k, int
   return BPR_OK;
 }
 
-extern "C" int bpr_sample_rows(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
-                               const int32_t* users, int64_t n, const int64_t* draw_ids, const int64_t* seen_indptr,
-                               const int32_t* seen_indices, int32_t k, float temperature, uint64_t seed,
-                               int32_t item_slices, void* workspace, int64_t workspace_bytes, int32_t* items_out,
-                               float* scores_out, float* keys_out, float* log_z_out, void* hip_stream) {
-  using namespace bpr;
-  if (int rc = check_topk_shape("bpr_sample_rows", n, I, d, k, TOPK_MAX, item_slices, "I")) return rc;
+namespace bpr {
+namespace {
+
+// bpr_sample_rows (rows = "_rows", no filter) and bpr_sample_rows_filtered (rows = "_rows_filtered"): one body, the
+// messages under the entry point's own name.  The plan does not look at the filter.
+int sample_rows(const char* rows, const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                const int32_t* users, int64_t n, const int64_t* draw_ids, const int64_t* seen_indptr,
+                const int32_t* seen_indices, const uint32_t* item_filter, int32_t k, float temperature, uint64_t seed,
+                int32_t item_slices, void* workspace, int64_t workspace_bytes, int32_t* items_out, float* scores_out,
+                float* keys_out, float* log_z_out, void* hip_stream) {
+  const std::string who = std::string("bpr_sample") + rows;
+  if (int rc = check_topk_shape(who.c_str(), n, I, d, k, TOPK_MAX, item_slices, "I")) return rc;
   const float inv_temp = 1.0f / temperature;
   if (!(temperature > 0.f) || !std::isfinite(temperature) || !std::isfinite(inv_temp))
-    return fail(BPR_ERR_INVALID, "bpr_sample_rows: temperature must be finite and > 0, and so must 1 / temperature");
+    return fail(BPR_ERR_INVALID, who + ": temperature must be finite and > 0, and so must 1 / temperature");
   if (n > 0 && (!P || !Q || !users || !items_out || !scores_out))
-    return fail(BPR_ERR_INVALID, "bpr_sample_rows: P, Q, users, items_out or scores_out is NULL");
+    return fail(BPR_ERR_INVALID, who + ": P, Q, users, items_out or scores_out is NULL");
+  if (int rc = check_item_filter(who.c_str(), item_filter)) return rc;
   const bool want_lz = log_z_out != nullptr;
   const SamplePlan p = plan_sample(n, I, k, item_slices, want_lz);
-  if (int rc = check_workspace("bpr_sample", workspace, workspace_bytes, p.ws_bytes, "the workspace")) return rc;
+  if (int rc = check_workspace("bpr_sample", workspace, workspace_bytes, p.ws_bytes, "the workspace", false, rows))
+    return rc;
   if (n == 0) return BPR_OK;
 
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -414,11 +439,44 @@ extern "C" int bpr_sample_rows(const float* P, const float* Q, const float* item
   f.scores = scores_out; f.lz = lz; f.log_z = log_z_out;
   const bool vec = vec_path(d, P, Q);
   const dim3 grid((unsigned)p.topk.user_tiles, (unsigned)S);
-  if (int rc = launch_kernel(vec ? k_sample<true> : k_sample<false>, sample_lds_bytes(TOPK_MAX), grid, dim3(256),
-                             p.topk.lds, stream, a))
+  if (item_filter != nullptr) {
+    Filtered<SampleArgs> fa = {};
+    static_cast<SampleArgs&>(fa) = a;
+    fa.filter = item_filter;
+    if (int rc = launch_kernel(vec ? k_sample<true, true> : k_sample<false, true>, sample_lds_bytes(TOPK_MAX), grid,
+                               dim3(256), p.topk.lds, stream, fa))
+      return rc;
+  } else if (int rc = launch_kernel(vec ? k_sample<true, false> : k_sample<false, false>, sample_lds_bytes(TOPK_MAX),
+                                    grid, dim3(256), p.topk.lds, stream, a)) {
     return rc;
+  }
   if (int rc = launch_topk_merge(a.out_keys, a.out_items, n, S, k, p.topk.merge_lds, keys, items_out, stream))
     return rc;
   return launch_kernel(vec ? k_sample_finish<true> : k_sample_finish<false>, 0, dim3((unsigned)n), dim3(TOPK_MAX), 0,
                        stream, f);
+}
+
+}  // namespace
+}  // namespace bpr
+
+extern "C" int bpr_sample_rows(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                               const int32_t* users, int64_t n, const int64_t* draw_ids, const int64_t* seen_indptr,
+                               const int32_t* seen_indices, int32_t k, float temperature, uint64_t seed,
+                               int32_t item_slices, void* workspace, int64_t workspace_bytes, int32_t* items_out,
+                               float* scores_out, float* keys_out, float* log_z_out, void* hip_stream) {
+  return bpr::sample_rows("_rows", P, Q, item_bias, I, d, users, n, draw_ids, seen_indptr, seen_indices, nullptr, k,
+                          temperature, seed, item_slices, workspace, workspace_bytes, items_out, scores_out, keys_out,
+                          log_z_out, hip_stream);
+}
+
+extern "C" int bpr_sample_rows_filtered(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                                        const int32_t* users, int64_t n, const int64_t* draw_ids,
+                                        const int64_t* seen_indptr, const int32_t* seen_indices,
+                                        const uint32_t* item_filter, int32_t k, float temperature, uint64_t seed,
+                                        int32_t item_slices, void* workspace, int64_t workspace_bytes,
+                                        int32_t* items_out, float* scores_out, float* keys_out, float* log_z_out,
+                                        void* hip_stream) {
+  return bpr::sample_rows("_rows_filtered", P, Q, item_bias, I, d, users, n, draw_ids, seen_indptr, seen_indices,
+                          item_filter, k, temperature, seed, item_slices, workspace, workspace_bytes, items_out,
+                          scores_out, keys_out, log_z_out, hip_stream);
 }

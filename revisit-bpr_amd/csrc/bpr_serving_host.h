@@ -59,15 +59,25 @@ static inline int check_out(const char* who, const void* out, const char* name) 
 
 // The workspace of `<family>_rows`, which `<family>_workspace` sizes: NULL or too small for the `need` bytes.
 // aligned_subject: nullptr, or the subject of "<subject> must be 8-byte aligned" (the two entry points that ask
-// for it word it differently); align_unneeded: ask it of a workspace the shape does not need as well.
+// for it word it differently); align_unneeded: ask it of a workspace the shape does not need as well; rows: what
+// follows the family in the entry point's name ("_rows_filtered").
 static inline int check_workspace(const char* family, const void* workspace, int64_t have, int64_t need,
-                                  const char* aligned_subject = nullptr, bool align_unneeded = false) {
-  const std::string who = std::string(family) + "_rows";
+                                  const char* aligned_subject = nullptr, bool align_unneeded = false,
+                                  const char* rows = "_rows") {
+  const std::string who = std::string(family) + rows;
   if (need > 0 && (workspace == nullptr || have < need))
     return fail(BPR_ERR_INVALID, who + ": workspace of " + std::to_string(have) + " bytes, " + std::to_string(need) +
                                      " needed (" + family + "_workspace)");
   if (aligned_subject != nullptr && (need > 0 || align_unneeded) && reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
     return fail(BPR_ERR_INVALID, who + ": " + aligned_subject + " must be 8-byte aligned");
+  return BPR_OK;
+}
+
+// the item filter of a `_rows_filtered` entry (bpr_item_filter.h): NULL is no filter; a tile's four words are read as
+// one 16-byte run
+static inline int check_item_filter(const char* who, const void* item_filter) {
+  if (reinterpret_cast<uintptr_t>(item_filter) % 16 != 0)
+    return fail(BPR_ERR_INVALID, std::string(who) + ": item_filter must be 16-byte aligned");
   return BPR_OK;
 }
 

@@ -40,6 +40,7 @@
 
 #include <string>
 
+#include "bpr_item_filter.h"
 #include "bpr_serving_host.h"
 #include "bpr_topk_plan.h"
 #include "bpr_topk_shared.h"
@@ -63,8 +64,10 @@ struct TopkArgs {
 };
 
 // VEC: d % 4 == 0 and 16-byte aligned tables (16-byte global loads); else element loads.
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_topk(const TopkArgs a) {
+// FILT: an item filter (bpr_item_filter.h) lies behind the arguments: an item whose bit is clear is not eligible, and
+// the loop walks the slice's non-empty tiles only.  Without it the kernel is what it was before there were filters.
+template <bool VEC, bool FILT>
+__global__ __launch_bounds__(256) void k_topk(const MaybeFiltered<FILT, TopkArgs> a) {
   constexpr int TU = TOPK_TU, TI = TOPK_TI, KC = TOPK_KC, LD = TOPK_LD;
   extern __shared__ __align__(16) unsigned char smem[];
   const int cap = a.k + TI;
@@ -129,8 +132,19 @@ __global__ __launch_bounds__(256) void k_topk(const TopkArgs a) {
   const float* const qa = sQ + (32 * w + r) * LD + 4 * h;
   const float* const pb0 = sP + r * LD + 4 * h;
   const float* const pb1 = sP + (32 + r) * LD + 4 * h;
-  if (t0 < t1) fetch(t0, 0);
-  for (int64_t t = t0; t < t1; ++t) {
+  // The walk.  FILT: the slice's non-empty tiles only — tile_from(t) is the first of them at or after t, or t1, and
+  // tn the one after the current tile, found once a tile for the prefetch and the step.  (Written so that without a
+  // filter the loop is `for (t = t0; t < t1; ++t)` to the compiler: profiles/item_filter_resources.md.)
+  auto tile_from = [&](int64_t t) -> int64_t {
+    if constexpr (FILT) return filter_next_tile(a.filter, a.I, t, t1);
+    else return t;
+  };
+  int64_t tn = 0;
+  auto next = [&](int64_t t) -> int64_t { return FILT ? tn : t + 1; };
+  const int64_t first = tile_from(t0);
+  if (first < t1) fetch(first, 0);
+  for (int64_t t = first; t < t1; t = next(t)) {
+    if constexpr (FILT) tn = tile_from(t + 1);
     f32x16 acc0 = {0.f}, acc1 = {0.f};
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.f;
@@ -139,7 +153,7 @@ __global__ __launch_bounds__(256) void k_topk(const TopkArgs a) {
       stash();
       __syncthreads();
       if (c + 1 < nch) fetch(t, c + 1);
-      else if (t + 1 < t1) fetch(t + 1, 0);
+      else if (next(t) < t1) fetch(next(t), 0);
       mfma_chunk2(qa, pb0, pb1, acc0, acc1);
     }
 
@@ -152,6 +166,9 @@ __global__ __launch_bounds__(256) void k_topk(const TopkArgs a) {
       const int64_t item = ibase + (q & 3) + 8 * (q >> 2);
       bv[q] = has_bias && item < a.I ? a.bias[item] : 0.f;
     }
+    // the wave's word of the filter: bit j is item t * TI + 32 w + j
+    uint32_t fw = 0;
+    if constexpr (FILT) fw = filter_wave_word(a.filter, a.I, t, __builtin_amdgcn_readfirstlane(w));
     // (A) how many scores beat the row's threshold
     unsigned m0 = 0, m1 = 0;
     {
@@ -159,7 +176,7 @@ __global__ __launch_bounds__(256) void k_topk(const TopkArgs a) {
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int64_t item = ibase + (q & 3) + 8 * (q >> 2);
-        const bool ok = item > 0 && item < a.I;
+        const bool ok = item > 0 && item < a.I && (!FILT || ((fw >> (4 * h + (q & 3) + 8 * (q >> 2))) & 1u));
         const float s0 = has_bias ? acc0[q] + bv[q] : acc0[q];
         const float s1 = has_bias ? acc1[q] + bv[q] : acc1[q];
         if (ok && better(s0, (int)item, tau0.s, tau0.i)) m0 |= 1u << q;
@@ -288,16 +305,22 @@ extern "C" int bpr_topk_slices(int64_t n, int64_t I, int32_t d, int32_t k, int32
   return BPR_OK;
 }
 
-extern "C" int bpr_topk_rows(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
-                             const int32_t* users, int64_t n, const int64_t* seen_indptr, const int32_t* seen_indices,
-                             int32_t k, int32_t item_slices, void* workspace, int64_t workspace_bytes,
-                             int32_t* items_out, float* scores_out, void* hip_stream) {
-  using namespace bpr;
-  if (int rc = check_topk_shape("bpr_topk_rows", n, I, d, k, TOPK_MAX, item_slices, "I")) return rc;
+namespace bpr {
+namespace {
+
+// bpr_topk_rows (rows = "_rows", no filter) and bpr_topk_rows_filtered (rows = "_rows_filtered"): one body, the
+// messages under the entry point's own name.  The plan does not look at the filter.
+int topk_rows(const char* rows, const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+              const int32_t* users, int64_t n, const int64_t* seen_indptr, const int32_t* seen_indices,
+              const uint32_t* item_filter, int32_t k, int32_t item_slices, void* workspace, int64_t workspace_bytes,
+              int32_t* items_out, float* scores_out, void* hip_stream) {
+  const std::string who = std::string("bpr_topk") + rows;
+  if (int rc = check_topk_shape(who.c_str(), n, I, d, k, TOPK_MAX, item_slices, "I")) return rc;
   if (n > 0 && (!P || !Q || !users || !items_out || !scores_out))
-    return fail(BPR_ERR_INVALID, "bpr_topk_rows: P, Q, users, items_out or scores_out is NULL");
+    return fail(BPR_ERR_INVALID, who + ": P, Q, users, items_out or scores_out is NULL");
+  if (int rc = check_item_filter(who.c_str(), item_filter)) return rc;
   const TopkPlan p = plan_topk(n, I, k, item_slices);
-  if (int rc = check_workspace("bpr_topk", workspace, workspace_bytes, p.ws_bytes)) return rc;
+  if (int rc = check_workspace("bpr_topk", workspace, workspace_bytes, p.ws_bytes, nullptr, false, rows)) return rc;
   if (n == 0) return BPR_OK;
 
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -306,10 +329,72 @@ extern "C" int bpr_topk_rows(const float* P, const float* Q, const float* item_b
   a.indptr = seen_indptr; a.indices = seen_indices; a.k = k; a.slices = p.slices; a.item_tiles = p.item_tiles;
   slice_outputs(workspace, n, p.slices, k, scores_out, items_out, &a.out_scores, &a.out_items);
   const dim3 grid((unsigned)p.user_tiles, (unsigned)p.slices);
-  if (int rc = launch_kernel(vec_path(d, P, Q) ? k_topk<true> : k_topk<false>, topk_lds_bytes(TOPK_MAX), grid,
-                             dim3(256), p.lds, stream, a))
+  const bool vec = vec_path(d, P, Q);
+  if (item_filter != nullptr) {
+    Filtered<TopkArgs> f = {};
+    static_cast<TopkArgs&>(f) = a;
+    f.filter = item_filter;
+    if (int rc = launch_kernel(vec ? k_topk<true, true> : k_topk<false, true>, topk_lds_bytes(TOPK_MAX), grid,
+                               dim3(256), p.lds, stream, f))
+      return rc;
+  } else if (int rc = launch_kernel(vec ? k_topk<true, false> : k_topk<false, false>, topk_lds_bytes(TOPK_MAX), grid,
+                                    dim3(256), p.lds, stream, a)) {
     return rc;
+  }
   return launch_topk_merge(a.out_scores, a.out_items, n, p.slices, k, p.merge_lds, scores_out, items_out, stream);
+}
+
+}  // namespace
+}  // namespace bpr
+
+extern "C" int bpr_topk_rows(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                             const int32_t* users, int64_t n, const int64_t* seen_indptr, const int32_t* seen_indices,
+                             int32_t k, int32_t item_slices, void* workspace, int64_t workspace_bytes,
+                             int32_t* items_out, float* scores_out, void* hip_stream) {
+  return bpr::topk_rows("_rows", P, Q, item_bias, I, d, users, n, seen_indptr, seen_indices, nullptr, k, item_slices,
+                        workspace, workspace_bytes, items_out, scores_out, hip_stream);
+}
+
+extern "C" int bpr_topk_rows_filtered(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                                      const int32_t* users, int64_t n, const int64_t* seen_indptr,
+                                      const int32_t* seen_indices, const uint32_t* item_filter, int32_t k,
+                                      int32_t item_slices, void* workspace, int64_t workspace_bytes,
+                                      int32_t* items_out, float* scores_out, void* hip_stream) {
+  return bpr::topk_rows("_rows_filtered", P, Q, item_bias, I, d, users, n, seen_indptr, seen_indices, item_filter, k,
+                        item_slices, workspace, workspace_bytes, items_out, scores_out, hip_stream);
+}
+
+// Test hook, not API (tests/test_item_filter_cpu.py sets its signature): bpr_item_filter.h on host words.  The
+// non-empty tiles of each of the `slices` tile ranges [bounds[s], bounds[s + 1]), walked with filter_next_tile:
+// counts[s] of them, one slice after the other in tiles[] (room for ceil(I / 128)); empty[t] = filter_tile_empty for
+// every tile of the catalogue; and for each of the n_probe ids probe[j]: probe_out[3 j ..] = {word, bit, eligible}.
+// Needs no GPU.
+extern "C" int bpr_test_filter_tiles(const uint32_t* words, int64_t I, const int64_t* bounds, int32_t slices,
+                                     int64_t* tiles, int64_t* counts, uint8_t* empty, const int64_t* probe,
+                                     int64_t n_probe, int64_t* probe_out) {
+  using namespace bpr;
+  if (!words || I < 1 || slices < 0 || reinterpret_cast<uintptr_t>(words) % FILTER_ALIGN != 0)
+    return fail(BPR_ERR_INVALID, "bpr_test_filter_tiles: words (16-byte aligned), I >= 1, slices >= 0");
+  const int64_t item_tiles = (I + TOPK_TI - 1) / TOPK_TI;
+  int64_t at = 0;
+  for (int s = 0; s < slices; ++s) {
+    if (bounds[s] < 0 || bounds[s] > bounds[s + 1] || bounds[s + 1] > item_tiles)
+      return fail(BPR_ERR_INVALID, "bpr_test_filter_tiles: bounds must ascend inside [0, ceil(I / 128)]");
+    counts[s] = 0;
+    for (int64_t t = filter_next_tile(words, I, bounds[s], bounds[s + 1]); t < bounds[s + 1];
+         t = filter_next_tile(words, I, t + 1, bounds[s + 1])) {
+      tiles[at++] = t;
+      ++counts[s];
+    }
+  }
+  if (empty != nullptr)
+    for (int64_t t = 0; t < item_tiles; ++t) empty[t] = filter_tile_empty(words, I, t) ? 1 : 0;
+  for (int64_t j = 0; j < n_probe; ++j) {
+    probe_out[3 * j] = filter_word_of(probe[j]);
+    probe_out[3 * j + 1] = filter_bit_of(probe[j]);
+    probe_out[3 * j + 2] = filter_has(words, I, probe[j]) ? 1 : 0;
+  }
+  return BPR_OK;
 }
 
 // Test hook, not API (tests/test_recommend_cpu.py sets its signature): the plan of a shape.  in = {n, I, d, k,

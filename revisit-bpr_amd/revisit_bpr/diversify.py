@@ -104,16 +104,17 @@ def diversify(Q: torch.Tensor, cand_items: torch.Tensor, cand_scores: torch.Tens
 def recommend_diverse(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor], users: torch.Tensor, k: int,
                       *, pool: int = 100, lam: float = 0.7, metric: str = "cosine", scale: str = "minmax",
                       seen_indptr: Optional[torch.Tensor] = None, seen_indices: Optional[torch.Tensor] = None,
-                      check_users: bool = True):
+                      check_users: bool = True, item_filter: Optional[torch.Tensor] = None):
     """`recommend(pool)` followed by `diversify(k)`: the `k` picks of greedy MMR from every user's `pool` best unseen
     items.  (items [n, k] int32, scores [n, k] float32), the scores being `recommend`'s.  lam = 1 returns
-    `recommend(k)` bit for bit."""
+    `recommend(k)` bit for bit.  `item_filter` is `recommend`'s: the pool holds eligible items only."""
     k, pool = int(k), int(pool)
     if pool < k:
         raise ValueError(f"pool = {pool} is shorter than k = {k}")
     if pool > POOL_MAX:
         raise ValueError(f"pool = {pool}: a pool holds at most {POOL_MAX} candidates")
-    cand, rel = recommend(P, Q, item_bias, users, pool, seen_indptr, seen_indices, check_users=check_users)
+    cand, rel = recommend(P, Q, item_bias, users, pool, seen_indptr, seen_indices, check_users=check_users,
+                          item_filter=item_filter)
     return diversify(Q, cand, rel, k, lam=lam, metric=metric, scale=scale)
 
 

@@ -226,23 +226,26 @@ class Engine:
         self._keep["csr"] = (indptr, indices)
         native.check(self._lib.bpr_bind_seen_csr(self._ctx, indptr.data_ptr(), indices.data_ptr()))
 
-    def recommend(self, users: torch.Tensor, k: int, exclude_seen: bool = True, *, item_slices: int = 0):
+    def recommend(self, users: torch.Tensor, k: int, exclude_seen: bool = True, *, item_slices: int = 0,
+                  item_filter: Optional[torch.Tensor] = None):
         """The `k` best items of every user of `users` from the bound tables (`bpr_topk_rows`, see
         revisit_bpr/recommend.py): (items [n, k] int32, scores [n, k] float32), sorted by score descending, ties
         by ascending id, padded with -1 / -inf.  Item 0 is never returned; exclude_seen also leaves out the user's
         row of the CSR given to `bind_seen_csr` (none bound: nothing else to leave out).  Rows an Adam / momentum
         / RMSprop optimizer has not replayed yet are scored as they stand: `flush_lazy()` first
-        (`Model.recommend` does)."""
+        (`Model.recommend` does).  `item_filter`: a packed filter (revisit_bpr/item_filter.py), only its items are
+        eligible; `retrieve`, `sample_items` and `recommend_diverse` take it alike."""
         from revisit_bpr.recommend import recommend
 
         indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
-        return recommend(self.P, self.Q, self.item_bias, users, k, indptr, indices, item_slices=item_slices)
+        return recommend(self.P, self.Q, self.item_bias, users, k, indptr, indices, item_slices=item_slices,
+                         item_filter=item_filter)
 
     def sample_items(self, users: torch.Tensor, k: int, exclude_seen: bool = True, **kw):
         """`k` items per user drawn without replacement from softmax(score / temperature) over the user's
         eligible items, in draw order, from the bound tables (`bpr_sample_rows`, see revisit_bpr/sample.py, which
-        takes the keywords: temperature, seed, draw_ids, return_keys, return_log_z, item_slices, check_users):
-        (items [n, k] int32, scores [n, k] float32[, keys][, log_z]), padded with -1 / -inf.  Eligibility is
+        takes the keywords: temperature, seed, draw_ids, return_keys, return_log_z, item_slices, check_users,
+        item_filter): (items [n, k] int32, scores [n, k] float32[, keys][, log_z]), padded with -1 / -inf.  Eligibility is
         `recommend`'s.  Rows an optimizer has not replayed yet are scored as they stand: `flush_lazy()` first
         (`Model.sample_items` does)."""
         from revisit_bpr.sample import sample_items
@@ -250,15 +253,18 @@ class Engine:
         indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
         return sample_items(self.P, self.Q, self.item_bias, users, k, indptr, indices, **kw)
 
-    def retrieve(self, users: torch.Tensor, k: int, exclude_seen: bool = True, *, item_slices: int = 0):
+    def retrieve(self, users: torch.Tensor, k: int, exclude_seen: bool = True, *, item_slices: int = 0,
+                 item_filter: Optional[torch.Tensor] = None):
         """`recommend` for `k` up to 1,024, the first stage of a two-stage recommender (`bpr_retrieve_rows`, see
         revisit_bpr/retrieve.py): the same scores, exclusions, order and padding, from the kernel that keeps its
-        candidates in device memory.  As `recommend`, rows an optimizer has not replayed yet are scored as they
-        stand: `flush_lazy()` first (`Model.retrieve` does)."""
+        candidates in device memory.  `item_filter`: a packed filter (revisit_bpr/item_filter.py), only its items are
+        eligible.  As `recommend`, rows an optimizer has not replayed yet are scored as they stand: `flush_lazy()`
+        first (`Model.retrieve` does)."""
         from revisit_bpr.retrieve import retrieve
 
         indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
-        return retrieve(self.P, self.Q, self.item_bias, users, k, indptr, indices, item_slices=item_slices)
+        return retrieve(self.P, self.Q, self.item_bias, users, k, indptr, indices, item_slices=item_slices,
+                        item_filter=item_filter)
 
     def rank_items(self, users: torch.Tensor, tgt_indptr: torch.Tensor, tgt_items: torch.Tensor,
                    exclude_seen: bool = True, *, item_slices: int = 0):
@@ -332,14 +338,16 @@ class Engine:
                          return_mmr=return_mmr, layout=layout)
 
     def recommend_diverse(self, users: torch.Tensor, k: int, *, pool: int = 100, lam: float = 0.7,
-                          metric: str = "cosine", scale: str = "minmax", exclude_seen: bool = True):
+                          metric: str = "cosine", scale: str = "minmax", exclude_seen: bool = True,
+                          item_filter: Optional[torch.Tensor] = None):
         """`recommend(pool)` followed by `diversify(k)` on the bound tables (revisit_bpr/diversify.py): the `k`
-        picks of greedy MMR from every user's `pool` best items.  lam = 1 is `recommend(k)` bit for bit."""
+        picks of greedy MMR from every user's `pool` best items.  lam = 1 is `recommend(k)` bit for bit.
+        `item_filter` is `recommend`'s: the pool holds eligible items only."""
         from revisit_bpr.diversify import recommend_diverse
 
         indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
         return recommend_diverse(self.P, self.Q, self.item_bias, users, k, pool=pool, lam=lam, metric=metric,
-                                 scale=scale, seen_indptr=indptr, seen_indices=indices)
+                                 scale=scale, seen_indptr=indptr, seen_indices=indices, item_filter=item_filter)
 
     def fold_in(self, indptr: torch.Tensor, items: torch.Tensor, *, epochs: int, lr: Optional[float] = None,
                 sampler: str = "uniform", refresh: bool = True, **kwargs) -> torch.Tensor:

@@ -482,19 +482,21 @@ class Model(torch.nn.Module):
         self.sync()
         return super().state_dict(*args, **kwargs)
 
-    def recommend(self, users: torch.Tensor, k: int, exclude_seen: bool = True):
+    def recommend(self, users: torch.Tensor, k: int, exclude_seen: bool = True, *,
+                  item_filter: Optional[torch.Tensor] = None):
         """The `k` best items of every user of `users` (device tensor of user ids): (items [n, k] int32,
         scores [n, k] float32) from the engine's fused top-K kernel (revisit_bpr/recommend.py), sorted by score
         descending, ties by ascending id, padded with -1 / -inf; item 0 and — exclude_seen — the items of the
         CSR given to `bind_seen_csr` are never returned.  Rows behind the optimizer step are replayed first
         (`sync()`).  A user bias is added to the returned scores (it does not change a user's order).  Only
-        the MF scorer has a fused form."""
+        the MF scorer has a fused form.  `item_filter`: a packed filter (revisit_bpr/item_filter.py), only its
+        items are eligible; `retrieve`, `sample_items` and `recommend_diverse` take it alike."""
         if not self._fusable():
             raise NotImplementedError("recommend needs the MF logits model in float32: other scorers have no "
                                       "fused top-K kernel")
         eng = self.engine()
         self.sync()
-        items, scores = eng.recommend(users, k, exclude_seen=exclude_seen)
+        items, scores = eng.recommend(users, k, exclude_seen=exclude_seen, item_filter=item_filter)
         ub = self.logits_model._user_bias
         if ub is not None:
             scores += ub.detach()[users.reshape(-1).long()].unsqueeze(1)
@@ -504,7 +506,7 @@ class Model(torch.nn.Module):
         """`k` items per user drawn without replacement from softmax(score / temperature) over the user's
         eligible items (the Plackett-Luce model), in draw order, from the engine's fused sampling kernel
         (revisit_bpr/sample.py, which takes the keywords: temperature, seed, draw_ids, return_keys, return_log_z,
-        item_slices, check_users): (items [n, k] int32, scores [n, k] float32[, keys][, log_z]), padded with
+        item_slices, check_users, item_filter): (items [n, k] int32, scores [n, k] float32[, keys][, log_z]), padded with
         -1 / -inf; eligibility is `recommend`'s.  Rows behind the optimizer step are replayed first (`sync()`).
         A user bias shifts a whole row and so changes no probability: it is added to the returned scores, and
         divided by the temperature to the keys and to log_z, so that `log_propensity` holds as it stands.  Only
@@ -527,9 +529,11 @@ class Model(torch.nn.Module):
                 out[rest] += b / float(kw.get("temperature", 1.0))
         return tuple(out)
 
-    def retrieve(self, users: torch.Tensor, k: int, exclude_seen: bool = True):
+    def retrieve(self, users: torch.Tensor, k: int, exclude_seen: bool = True, *,
+                 item_filter: Optional[torch.Tensor] = None):
         """`recommend` for `k` up to 1,024 (revisit_bpr/retrieve.py): candidates for `rerank`, `diversify` or a
-        ranker of the caller's, with `recommend`'s scores, exclusions, order and padding.  Rows behind the
+        ranker of the caller's, with `recommend`'s scores, exclusions, order and padding; `item_filter` is
+        `recommend`'s (a packed filter, only its items are eligible).  Rows behind the
         optimizer step are replayed first (`sync()`).  A user bias is added to the returned scores (it does not
         change a user's order).  Only the MF scorer has a fused form."""
         if not self._fusable():
@@ -537,7 +541,7 @@ class Model(torch.nn.Module):
                                       "fused top-K kernel")
         eng = self.engine()
         self.sync()
-        items, scores = eng.retrieve(users, k, exclude_seen=exclude_seen)
+        items, scores = eng.retrieve(users, k, exclude_seen=exclude_seen, item_filter=item_filter)
         ub = self.logits_model._user_bias
         if ub is not None:
             scores += ub.detach()[users.reshape(-1).long()].unsqueeze(1)
@@ -646,18 +650,19 @@ class Model(torch.nn.Module):
         return eng.diversify(cand_items, cand_scores, k, lam=lam, metric=metric, scale=scale, return_mmr=return_mmr)
 
     def recommend_diverse(self, users: torch.Tensor, k: int, *, pool: int = 100, lam: float = 0.7,
-                          metric: str = "cosine", scale: str = "minmax", exclude_seen: bool = True):
+                          metric: str = "cosine", scale: str = "minmax", exclude_seen: bool = True,
+                          item_filter: Optional[torch.Tensor] = None):
         """`recommend(pool)` followed by `diversify(k)`: the `k` picks of greedy MMR from every user's `pool` best
         items.  A user bias is added to the returned scores after the picks are made (it shifts a whole row and
-        plays no part in the choice).  Rows behind the optimizer step are replayed first (`sync()`).  Only the MF
-        scorer has a fused form."""
+        plays no part in the choice).  `item_filter` is `recommend`'s: the pool holds eligible items only.  Rows
+        behind the optimizer step are replayed first (`sync()`).  Only the MF scorer has a fused form."""
         if not self._fusable():
             raise NotImplementedError("recommend_diverse needs the MF logits model in float32: other scorers have "
                                       "no fused top-K kernel")
         eng = self.engine()
         self.sync()
         items, scores = eng.recommend_diverse(users, k, pool=pool, lam=lam, metric=metric, scale=scale,
-                                              exclude_seen=exclude_seen)
+                                              exclude_seen=exclude_seen, item_filter=item_filter)
         ub = self.logits_model._user_bias
         if ub is not None:
             scores += ub.detach()[users.reshape(-1).long()].unsqueeze(1)

@@ -129,15 +129,24 @@ SIGNATURES = {
     "bpr_topk_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     "bpr_topk_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
                               c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "bpr_topk_rows_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                       c_void_p]),
     "bpr_retrieve_workspace": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "bpr_retrieve_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     "bpr_retrieve_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
                                   c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "bpr_retrieve_rows_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
+                                           c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p,
+                                           c_void_p, c_void_p]),
     "bpr_sample_workspace": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "bpr_sample_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     "bpr_sample_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                 c_void_p, c_int32, c_float, c_uint64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    "bpr_sample_rows_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_int32, c_float, c_uint64, c_int32, c_void_p,
+                                         c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bpr_neighbors_workspace":(c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "bpr_neighbors_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     "bpr_neighbors_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32,

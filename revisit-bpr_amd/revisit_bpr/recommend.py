@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
+from revisit_bpr.item_filter import check_item_filter, check_item_filter_early
 from revisit_bpr._serving import int32_ids, need_rocm, ptr, query, seen_csr, sliced_workspace, tables
 
 TOPK_MAX = 128  # bpr_topk_rows: largest k
@@ -31,7 +32,8 @@ def slices(n: int, num_items: int, d: int, k: int, item_slices: int = 0) -> int:
 @torch.no_grad()
 def recommend(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor], users: torch.Tensor,
               k: int, seen_indptr: Optional[torch.Tensor] = None,
-              seen_indices: Optional[torch.Tensor] = None, *, item_slices: int = 0, check_users: bool = True):
+              seen_indices: Optional[torch.Tensor] = None, *, item_slices: int = 0, check_users: bool = True,
+              item_filter: Optional[torch.Tensor] = None):
     """The `k` best items of every user of `users` by <P[u], Q[i]> (+ item_bias[i]), item 0 and
     the user's row of the seen CSR (int64 [U+1], int32 sorted per row; None: only item 0) left out.
 
@@ -45,16 +47,22 @@ def recommend(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor
     The kernel reads P[user] and the user's CSR row unchecked, so the ids are range-checked here
     first, which waits for the device; `check_users=False` leaves that out (ids known to be valid:
     a serving loop, a captured graph).
+
+    `item_filter` (None: the whole catalogue): a packed filter of `revisit_bpr.item_filter.pack_item_filter` over
+    the I items, on the tables' device; only items whose bit is set are eligible — the result is the unfiltered
+    ranking restricted to them, bit for bit, cut to k (`bpr_topk_rows_filtered`).
     """
     k = int(k)
     if k > TOPK_MAX:
         raise ValueError(f"k = {k}: recommend returns at most {TOPK_MAX} items per user")
     if k < 1:
         raise ValueError("k must be at least 1")
-    need_rocm("recommend", "the tables and the user list", (P, Q, users, item_bias),
-              (P, Q, item_bias, users, seen_indptr, seen_indices), "P")
+    item_filter = check_item_filter_early(item_filter, Q)
+    need_rocm("recommend", "the tables and the user list", (P, Q, users, item_bias, item_filter),
+              (P, Q, item_bias, users, seen_indptr, seen_indices, item_filter), "P")
     lib = native.load()
     P, Q, item_bias, U, I, d = tables(P, Q, item_bias)
+    item_filter = check_item_filter(item_filter, I)
     dev = P.device
     users = int32_ids(users, strict=False)
     n = users.numel()
@@ -65,6 +73,12 @@ def recommend(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
     item_slices, ws, ws_bytes = sliced_workspace("topk", (n, I, d, k), item_slices, dev)
     with torch.cuda.device(dev):
+        if item_filter is not None:
+            native.check(lib.bpr_topk_rows_filtered(
+                P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(seen_indptr),
+                ptr(seen_indices), item_filter.data_ptr(), k, item_slices, ptr(ws), ws_bytes, items.data_ptr(),
+                scores.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            return items, scores
         native.check(lib.bpr_topk_rows(
             P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(seen_indptr),
             ptr(seen_indices), k, item_slices, ptr(ws), ws_bytes, items.data_ptr(), scores.data_ptr(),

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from revisit_bpr import native
+from revisit_bpr.item_filter import check_item_filter, check_item_filter_early
 from revisit_bpr._serving import int32_ids, need_rocm, ptr, query, seen_csr, sliced_workspace, tables
 
 SAMPLE_MAX = 128  # bpr_sample_rows: largest k
@@ -36,7 +37,7 @@ def sample_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Ten
                  seen_indptr: Optional[torch.Tensor] = None, seen_indices: Optional[torch.Tensor] = None, *,
                  temperature: float = 1.0, seed: int = 0, draw_ids: Optional[torch.Tensor] = None,
                  return_keys: bool = False, return_log_z: bool = False, item_slices: int = 0,
-                 check_users: bool = True):
+                 check_users: bool = True, item_filter: Optional[torch.Tensor] = None):
     """`k` items per user of `users`, drawn without replacement from softmax(s(u, .) / temperature) over the
     user's eligible items, s(u, i) = <P[u], Q[i]> (+ item_bias[i]) with `recommend`'s bits; item 0 and the
     user's row of the seen CSR (int64 [U+1], int32 sorted per row; None: only item 0) are left out.
@@ -52,6 +53,12 @@ def sample_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Ten
     `users` or of `item_slices` (log_z is held to a tolerance, and its last bits may depend on
     `item_slices`).  The same user twice with the same draw id is the same row twice: give rows distinct
     draw ids, a request counter for instance, for independent draws.  `check_users` as in `recommend`.
+
+    `item_filter` (None: the whole catalogue): a packed filter of `revisit_bpr.item_filter.pack_item_filter` over
+    the I items, on the tables' device; the draw is over the items whose bit is set, and `log_z` normalises over
+    them alone, so that `log_propensity` is the propensity of a draw from the restricted catalogue
+    (`bpr_sample_rows_filtered`).  An item's noise does not depend on the filter: an eligible item has the key it
+    has without one.
     """
     k = int(k)
     if k > SAMPLE_MAX:
@@ -67,10 +74,12 @@ def sample_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Ten
     seed = int(seed)
     if not 0 <= seed < 2 ** 64:
         raise ValueError("seed must be in [0, 2^64)")
-    need_rocm("sample_items", "the tables and the user list", (P, Q, users, item_bias),
-              (P, Q, item_bias, users, seen_indptr, seen_indices, draw_ids), "P")
+    item_filter = check_item_filter_early(item_filter, Q)
+    need_rocm("sample_items", "the tables and the user list", (P, Q, users, item_bias, item_filter),
+              (P, Q, item_bias, users, seen_indptr, seen_indices, draw_ids, item_filter), "P")
     lib = native.load()
     P, Q, item_bias, U, I, d = tables(P, Q, item_bias)
+    item_filter = check_item_filter(item_filter, I)
     dev = P.device
     users = int32_ids(users, strict=True)
     n = users.numel()
@@ -90,11 +99,18 @@ def sample_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Ten
     item_slices, ws, ws_bytes = sliced_workspace("sample", (n, I, d, k), item_slices, dev,
                                                  post=(int(bool(return_log_z)),), words=True)
     with torch.cuda.device(dev):
-        native.check(lib.bpr_sample_rows(
-            P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(draw_ids), ptr(seen_indptr),
-            ptr(seen_indices), k, temperature, seed, item_slices, ptr(ws), ws_bytes, items.data_ptr(),
-            scores.data_ptr(), ptr(keys), ptr(log_z),
-            torch.cuda.current_stream(dev).cuda_stream))
+        if item_filter is not None:
+            native.check(lib.bpr_sample_rows_filtered(
+                P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(draw_ids),
+                ptr(seen_indptr), ptr(seen_indices), item_filter.data_ptr(), k, temperature, seed, item_slices,
+                ptr(ws), ws_bytes, items.data_ptr(), scores.data_ptr(), ptr(keys), ptr(log_z),
+                torch.cuda.current_stream(dev).cuda_stream))
+        else:
+            native.check(lib.bpr_sample_rows(
+                P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(draw_ids),
+                ptr(seen_indptr), ptr(seen_indices), k, temperature, seed, item_slices, ptr(ws), ws_bytes,
+                items.data_ptr(), scores.data_ptr(), ptr(keys), ptr(log_z),
+                torch.cuda.current_stream(dev).cuda_stream))
     out = (items, scores)
     if return_keys:
         out += (keys,)
