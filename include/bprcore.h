@@ -700,7 +700,7 @@ int bpr_topk_rows(const float* P, const float* Q, const float* item_bias /* or N
                   void* workspace, int64_t workspace_bytes,
                   int32_t* items_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
 
-/* ---- the item filter of the first-stage calls: "only these items" (in stock, of a category, licensed, not on a
+/* ---- the item filter of the whole-catalogue calls: "only these items" (in stock, of a category, licensed, not on a
  * block list) as one more eligibility rule inside the kernel, beside "not item 0" and "not in the seen row".
  * item_filter is a device bitmap of uint32 words, bit (i & 31) of word (i >> 5) set = item i is eligible;
  * 4 * ceil(I / 128) words long (a whole number of the kernels' item tiles), its start 16-byte aligned (else
@@ -846,6 +846,20 @@ int bpr_rank_rows(const float* P, const float* Q, const float* item_bias /* or N
                   const int64_t* seen_indptr /* or NULL */, const int32_t* seen_indices,
                   int32_t item_slices /* 0 = choose */, void* workspace, int64_t workspace_bytes,
                   int32_t* rank_out, int32_t* not_below_out, float* score_out, void* hip_stream);
+/* bpr_rank_rows over the eligible items of an item filter (the layout, the alignment and the NULL rule: see
+ * bpr_topk_rows_filtered).  Item j is eligible for row r if it is eligible for bpr_rank_rows and its bit is set;
+ * everything else in the definition of rank_out, not_below_out and score_out stands.  A target whose bit is clear is
+ * itself not eligible: -1 / -1 / -inf.  Scores are untouched, so the answer is what bpr_rank_rows gives on the
+ * catalogue compacted to item 0 and the eligible items in ascending order (a monotone renumbering keeps the ties),
+ * whatever n, the rows' order, item_slices, and however many item tiles held no eligible item and were skipped.
+ * bpr_rank_workspace and bpr_rank_slices size and plan the call: the plan does not look at the filter. */
+int bpr_rank_rows_filtered(const float* P, const float* Q, const float* item_bias /* or NULL */, int64_t I, int32_t d,
+                           const int32_t* users, int64_t n,
+                           const int64_t* tgt_indptr /* [n+1] */, const int32_t* tgt_items,
+                           const int64_t* seen_indptr /* or NULL */, const int32_t* seen_indices,
+                           const uint32_t* item_filter /* [4 * ceil(I / 128)] or NULL */,
+                           int32_t item_slices /* 0 = choose */, void* workspace, int64_t workspace_bytes,
+                           int32_t* rank_out, int32_t* not_below_out, float* score_out, void* hip_stream);
 
 /* ---- fold-in: user rows for users who arrive after training, learnt against the FROZEN item table (the reference
  * has no such step: its held-out users' histories are part of the training file, full-train-with-fold-in.jsonl, which
@@ -1079,6 +1093,19 @@ int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int32_t d,
                        int32_t metric, int32_t k, int32_t item_slices /* 0 = choose */,
                        void* workspace, int64_t workspace_bytes,
                        int32_t* ids_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
+/* bpr_neighbors_rows over the rows of T whose bit is set in a filter over T's N rows (the layout of
+ * bpr_topk_rows_filtered: 4 * ceil(N / 128) words, 16-byte aligned, NULL = the unfiltered call itself).  Eligibility
+ * gains "bit j set"; `first` (the filter's lower bound: with first = 0 row 0 is a row like any other and its bit
+ * counts), `exclude` and the cosine rule are unchanged, and so is every score: the result is bpr_neighbors_rows' on
+ * the eligible rows of T alone, ids mapped back, k ids where filtering after the cut returns fewer.  The cosine
+ * pre-pass still writes the norms of all N rows.  bpr_neighbors_workspace and bpr_neighbors_slices are the call's. */
+int bpr_neighbors_rows_filtered(const float* X, const float* T, int64_t N, int32_t d,
+                                const int32_t* rows, int64_t n, const int32_t* exclude /* [n] or NULL */,
+                                int32_t first, int32_t metric,
+                                const uint32_t* item_filter /* [4 * ceil(N / 128)] or NULL */,
+                                int32_t k, int32_t item_slices /* 0 = choose */,
+                                void* workspace, int64_t workspace_bytes,
+                                int32_t* ids_out /* [n,k] */, float* scores_out /* [n,k] */, void* hip_stream);
 
 /* ---- re-ranking: the k best of a GIVEN candidate list per row, and the score of every candidate ("score this user
  * on these items": availability filters, second-stage re-ranking, sampled-negative protocols, explicit pairs).  The

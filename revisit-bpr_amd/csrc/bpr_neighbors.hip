@@ -39,6 +39,7 @@
 
 #include <string>
 
+#include "bpr_item_filter.h"
 #include "bpr_neighbors_plan.h"
 #include "bpr_serving_host.h"
 #include "bpr_topk_shared.h"
@@ -91,8 +92,11 @@ __global__ __launch_bounds__(256) void k_neighbors_norms(const float* __restrict
 }
 
 // VEC: d % 4 == 0 and 16-byte aligned tables (16-byte global loads); else element loads.  COS: cosine metric.
-template <bool VEC, bool COS>
-__global__ __launch_bounds__(256) void k_neighbors(const NeighborsArgs a) {
+// FILT: a filter over the N table rows (bpr_item_filter.h, with `first` as its lower bound) lies behind the
+// arguments: a row whose bit is clear is not eligible, and the loop walks the slice's non-empty tiles only.  Without
+// it the kernel is what it was before there were filters.
+template <bool VEC, bool COS, bool FILT>
+__global__ __launch_bounds__(256) void k_neighbors(const MaybeFiltered<FILT, NeighborsArgs> a) {
   constexpr int TU = TOPK_TU, TI = TOPK_TI, KC = TOPK_KC, LD = TOPK_LD;
   extern __shared__ __align__(16) unsigned char smem[];
   const int cap = a.k + TI;
@@ -159,8 +163,18 @@ __global__ __launch_bounds__(256) void k_neighbors(const NeighborsArgs a) {
   const float* const ta = sT + (32 * w + r) * LD + 4 * h;
   const float* const xb0 = sX + r * LD + 4 * h;
   const float* const xb1 = sX + (32 + r) * LD + 4 * h;
-  if (t0 < t1) fetch(t0, 0);
-  for (int64_t t = t0; t < t1; ++t) {
+  // The walk: k_topk's form (bpr_topk.hip).  FILT: tile_from(t) is the first non-empty tile at or after t, or t1,
+  // and tn the one after the current tile; without a filter the loop is `for (t = t0; t < t1; ++t)` to the compiler.
+  auto tile_from = [&](int64_t t) -> int64_t {
+    if constexpr (FILT) return filter_next_tile_from(a.filter, a.N, t, t1, a.first);
+    else return t;
+  };
+  int64_t tn = 0;
+  auto next = [&](int64_t t) -> int64_t { return FILT ? tn : t + 1; };
+  const int64_t start = tile_from(t0);
+  if (start < t1) fetch(start, 0);
+  for (int64_t t = start; t < t1; t = next(t)) {
+    if constexpr (FILT) tn = tile_from(t + 1);
     f32x16 acc0 = {0.f}, acc1 = {0.f};
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.f;
@@ -169,13 +183,16 @@ __global__ __launch_bounds__(256) void k_neighbors(const NeighborsArgs a) {
       stash(c);
       __syncthreads();
       if (c + 1 < nch) fetch(t, c + 1);
-      else if (t + 1 < t1) fetch(t + 1, 0);
+      else if (next(t) < t1) fetch(next(t), 0);
       mfma_chunk2(ta, xb0, xb1, acc0, acc1);
     }
 
     // ---- epilogue of the tile: register q of the lane is table row jbase + (q & 3) + 8 (q >> 2) of queries r, 32 + r
     const int64_t jbase = t * TI + 32 * w + 4 * h;
     // (A) the eligible scores that beat the query's threshold; under cosine the accumulators become the scores
+    // the wave's word of the filter: bit b is table row t * TI + 32 w + b
+    uint32_t fw = 0;
+    if constexpr (FILT) fw = filter_wave_word_from(a.filter, a.N, t, __builtin_amdgcn_readfirstlane(w), a.first);
     unsigned m0 = 0, m1 = 0;
     {
       const Cand tau0 = sTau[r], tau1 = sTau[32 + r];
@@ -185,7 +202,7 @@ __global__ __launch_bounds__(256) void k_neighbors(const NeighborsArgs a) {
       for (int q = 0; q < 16; ++q) {
         const int jl = 32 * w + 4 * h + (q & 3) + 8 * (q >> 2);
         const int64_t j = t * TI + jl;
-        bool ok = j >= a.first && j < a.N;
+        bool ok = j >= a.first && j < a.N && (!FILT || ((fw >> (jl & 31)) & 1u));
         if (COS) {
           const float rt = sRnT[jl];
           ok = ok && rt >= 0.f;
@@ -266,19 +283,26 @@ extern "C" int bpr_neighbors_slices(int64_t n, int64_t N, int32_t d, int32_t k, 
   return BPR_OK;
 }
 
-extern "C" int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int32_t d, const int32_t* rows, int64_t n,
-                                  const int32_t* exclude, int32_t first, int32_t metric, int32_t k,
-                                  int32_t item_slices, void* workspace, int64_t workspace_bytes, int32_t* ids_out,
-                                  float* scores_out, void* hip_stream) {
-  using namespace bpr;
-  using namespace bpr::nbr;
-  if (int rc = check_topk_shape("bpr_neighbors_rows", n, N, d, k, TOPK_MAX, item_slices, "N")) return rc;
-  if (int rc = check_metric("bpr_neighbors_rows", metric)) return rc;
-  if (first < 0) return fail(BPR_ERR_INVALID, "bpr_neighbors_rows: first must be >= 0");
+namespace bpr {
+namespace nbr {
+namespace {
+
+// bpr_neighbors_rows (rows_suffix = "_rows", no filter) and bpr_neighbors_rows_filtered ("_rows_filtered"): one
+// body, the messages under the entry point's own name.  The plan does not look at the filter.
+int neighbors_rows(const char* rows_suffix, const float* X, const float* T, int64_t N, int32_t d, const int32_t* rows,
+                   int64_t n, const int32_t* exclude, int32_t first, int32_t metric, const uint32_t* item_filter,
+                   int32_t k, int32_t item_slices, void* workspace, int64_t workspace_bytes, int32_t* ids_out,
+                   float* scores_out, void* hip_stream) {
+  const std::string who = std::string("bpr_neighbors") + rows_suffix;
+  if (int rc = check_topk_shape(who.c_str(), n, N, d, k, TOPK_MAX, item_slices, "N")) return rc;
+  if (int rc = check_metric(who.c_str(), metric)) return rc;
+  if (first < 0) return fail(BPR_ERR_INVALID, who + ": first must be >= 0");
   if (n > 0 && (!X || !T || !rows || !ids_out || !scores_out))
-    return fail(BPR_ERR_INVALID, "bpr_neighbors_rows: X, T, rows, ids_out or scores_out is NULL");
+    return fail(BPR_ERR_INVALID, who + ": X, T, rows, ids_out or scores_out is NULL");
+  if (int rc = check_item_filter(who.c_str(), item_filter)) return rc;
   const NeighborsPlan p = plan_neighbors(n, N, k, metric, item_slices);
-  if (int rc = check_workspace("bpr_neighbors", workspace, workspace_bytes, p.ws_bytes)) return rc;
+  if (int rc = check_workspace("bpr_neighbors", workspace, workspace_bytes, p.ws_bytes, nullptr, false, rows_suffix))
+    return rc;
   if (n == 0) return BPR_OK;
 
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -299,11 +323,41 @@ extern "C" int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int
                                dim3(256), 0, stream, T, N, X, rows, n, (int)d, rn_t, rn_x))
       return rc;
   }
-  const auto kernel = cosine ? (vec ? k_neighbors<true, true> : k_neighbors<false, true>)
-                             : (vec ? k_neighbors<true, false> : k_neighbors<false, false>);
   const dim3 grid((unsigned)p.t.user_tiles, (unsigned)S);
-  if (int rc = launch_kernel(kernel, neighbors_lds_bytes(TOPK_MAX), grid, dim3(256), p.lds, stream, a)) return rc;
+  if (item_filter != nullptr) {
+    Filtered<NeighborsArgs> f = {};
+    static_cast<NeighborsArgs&>(f) = a;
+    f.filter = item_filter;
+    const auto kernel = cosine ? (vec ? k_neighbors<true, true, true> : k_neighbors<false, true, true>)
+                               : (vec ? k_neighbors<true, false, true> : k_neighbors<false, false, true>);
+    if (int rc = launch_kernel(kernel, neighbors_lds_bytes(TOPK_MAX), grid, dim3(256), p.lds, stream, f)) return rc;
+  } else {
+    const auto kernel = cosine ? (vec ? k_neighbors<true, true, false> : k_neighbors<false, true, false>)
+                               : (vec ? k_neighbors<true, false, false> : k_neighbors<false, false, false>);
+    if (int rc = launch_kernel(kernel, neighbors_lds_bytes(TOPK_MAX), grid, dim3(256), p.lds, stream, a)) return rc;
+  }
   return launch_topk_merge(a.out_scores, a.out_ids, n, S, k, p.t.merge_lds, scores_out, ids_out, stream);
+}
+
+}  // namespace
+}  // namespace nbr
+}  // namespace bpr
+
+extern "C" int bpr_neighbors_rows(const float* X, const float* T, int64_t N, int32_t d, const int32_t* rows, int64_t n,
+                                  const int32_t* exclude, int32_t first, int32_t metric, int32_t k,
+                                  int32_t item_slices, void* workspace, int64_t workspace_bytes, int32_t* ids_out,
+                                  float* scores_out, void* hip_stream) {
+  return bpr::nbr::neighbors_rows("_rows", X, T, N, d, rows, n, exclude, first, metric, nullptr, k, item_slices,
+                                  workspace, workspace_bytes, ids_out, scores_out, hip_stream);
+}
+
+extern "C" int bpr_neighbors_rows_filtered(const float* X, const float* T, int64_t N, int32_t d, const int32_t* rows,
+                                           int64_t n, const int32_t* exclude, int32_t first, int32_t metric,
+                                           const uint32_t* item_filter, int32_t k, int32_t item_slices,
+                                           void* workspace, int64_t workspace_bytes, int32_t* ids_out,
+                                           float* scores_out, void* hip_stream) {
+  return bpr::nbr::neighbors_rows("_rows_filtered", X, T, N, d, rows, n, exclude, first, metric, item_filter, k,
+                                  item_slices, workspace, workspace_bytes, ids_out, scores_out, hip_stream);
 }
 
 // Test hook, not API (tests/test_neighbors_cpu.py sets its signature): the plan of a shape.  in = {n, N, d, k,

@@ -44,6 +44,7 @@
 #include <atomic>
 #include <string>
 
+#include "bpr_item_filter.h"
 #include "bpr_rank_plan.h"
 #include "bpr_serving_host.h"
 #include "bpr_topk_shared.h"
@@ -51,6 +52,7 @@
 namespace bpr {
 
 static_assert(RANK_KC == TOPK_KC && RANK_LD == TOPK_LD, "k_rank stages k_topk's chunks (bpr_topk_shared.h)");
+static_assert(RANK_TI == TOPK_TI, "an item tile of k_rank is a tile of the item filter (bpr_item_filter.h)");
 
 struct RankArgs {
   const float* P;
@@ -126,8 +128,12 @@ __device__ __forceinline__ void sort_row(const RankArgs& a, int64_t tlo, int T, 
 
 // VEC: d % 4 == 0 and 16-byte aligned tables (16-byte global loads); else element loads.
 // PRE: the target-score pass (step 1 of the header); else the ranking pass (step 2).
-template <bool VEC, bool PRE>
-__global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
+// FILT: an item filter (bpr_item_filter.h) lies behind the arguments: an item whose bit is clear is not eligible.  The
+// target pass tests the target's own bit; the ranking pass joins the tile's four words with the seen mask and walks
+// the slice's non-empty tiles only.  Without it the kernel is what it was before there were filters.
+template <bool VEC, bool PRE, bool FILT>
+__global__ __launch_bounds__(256) void k_rank(const MaybeFiltered<FILT, RankArgs> a) {
+  constexpr bool SKIP = FILT && !PRE;  // the walk leaves out the empty tiles
   constexpr int TR = RANK_TR, TI = RANK_TI, KC = RANK_KC, LD = RANK_LD, TM = RANK_TMAX, HT = RANK_HT;
   extern __shared__ __align__(16) unsigned char smem[];
   float* const sQ = reinterpret_cast<float*>(smem);  // [TI][LD]
@@ -197,6 +203,16 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
   int top = 0;  // ranking: the first step of the binary search (largest power of two <= the longest list)
   const int32_t* seen = nullptr;  // ranking: this thread's quarter of row tid >> 2's seen list
   int se = 0, slen = 0, snext = INT_MAX;
+  // The walk.  SKIP: the slice's non-empty tiles only — tile_from(t) is the first of them at or after t, or t1, and
+  // tn the one after the current tile (k_topk's form, bpr_topk.hip: without a filter the loop is
+  // `for (t = t0; t < t1; ++t)` to the compiler: profiles/rank_neighbors_filter_resources.md).
+  auto tile_from = [&](int64_t t) -> int64_t {
+    if constexpr (SKIP) return filter_next_tile(a.filter, a.I, t, t1);
+    else return t;
+  };
+  int64_t tn = 0;
+  auto next = [&](int64_t t) -> int64_t { return SKIP ? tn : t + 1; };
+  int64_t first = t0;
   if (!PRE) {
     for (int row = w; row < TR; row += 4) {
       sort_row(a, sTgtLo[row], sT[row], lane, sL + row * TM, sPerm + row * TM, sHT + row * HT, &sT[row]);
@@ -208,11 +224,12 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
     top = 1;
     while (top <= maxT) top <<= 1;
     top >>= 1;
+    first = tile_from(t0);  // (after t1 is final)
     const int row = tid >> 2;
     slen = sSeenLen[row];
-    if (slen > 0 && t0 < t1) {
+    if (slen > 0 && first < t1) {
       seen = a.indices + sSeenLo[row];
-      se = lower_bound_i32(seen, slen, t0 * TI) + (tid & 3);
+      se = lower_bound_i32(seen, slen, first * TI) + (tid & 3);
       snext = se < slen ? seen[se] : INT_MAX;
     }
   }
@@ -244,8 +261,9 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
   const float* const pb0 = sP + r * LD + 4 * h;
   const float* const pb1 = sP + (32 + r) * LD + 4 * h;
   const bool has_bias = a.bias != nullptr;
-  if (t0 < t1) fetch(t0, 0);
-  for (int64_t t = t0; t < t1; ++t) {
+  if (first < t1) fetch(first, 0);
+  for (int64_t t = first; t < t1; t = next(t)) {
+    if constexpr (SKIP) tn = tile_from(t + 1);
     f32x16 acc0, acc1;
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.f;
@@ -270,6 +288,16 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
       __syncthreads();
       if (!PRE && c == 0) {  // the seen entries of this thread's quarter that fall into the tile
         const int64_t hi = (t + 1) * TI;
+        if constexpr (SKIP) {
+          // A run of skipped tiles may lie behind: the cursor goes to the first entry of ITS residue class (mod 4)
+          // that is at or past this tile, by one search, not entry by entry.  Every thread keeps its class, so the
+          // four still cover every entry once (tests/test_rank_neighbors_filter_cpu.py models the rule).
+          if (snext < t * TI) {
+            const int at = lower_bound_i32(seen, slen, t * TI);  // > se: seen[se] is below the tile
+            se += (at - se + 3) & ~3;
+            snext = se < slen ? seen[se] : INT_MAX;
+          }
+        }
         while (snext < hi) {
           const int li = snext - (int)(t * TI);  // (negative only for a row that is not sorted: passed over)
           if (li >= 0) atomicOr(&sMask[(tid >> 2) * 4 + (li >> 5)], 1u << (li & 31));
@@ -278,7 +306,7 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
         }
       }
       if (c + 1 < nch) fetch(t, c + 1);
-      else if (t + 1 < t1) fetch(t + 1, 0);
+      else if (next(t) < t1) fetch(next(t), 0);
       mfma_chunk2(qa, pb0, pb1, acc0, acc1);
     }
     __syncthreads();  // the tile's owners / seen masks are complete
@@ -302,13 +330,19 @@ __global__ __launch_bounds__(256) void k_rank(const RankArgs a) {
           const int at = lower_bound_i32(v, sSeenLen[own], id);
           ok = !(at < sSeenLen[own] && v[at] == id);
         }
+        if constexpr (FILT) ok = ok && ((filter_word(a.filter, a.I, filter_word_of(id)) >> filter_bit_of(id)) & 1u);
         a.score[p] = ok ? s : -INFINITY;
         a.rank[p] = ok ? 0 : -1;
         a.not_below[p] = ok ? 0 : -1;
       }
     } else {
       const int64_t ibase = t * TI + lbase;
-      const uint32_t seen0 = sMask[r * 4 + w], seen1 = sMask[(32 + r) * 4 + w];
+      uint32_t seen0 = sMask[r * 4 + w], seen1 = sMask[(32 + r) * 4 + w];
+      if constexpr (FILT) {  // eligible = not seen AND the wave's word of the filter (wave-uniform: a scalar load)
+        const uint32_t fw = filter_wave_word(a.filter, a.I, t, __builtin_amdgcn_readfirstlane(w));
+        seen0 |= ~fw;
+        seen1 |= ~fw;
+      }
       const int T0 = sT[r], T1 = sT[32 + r];
       const Cand* const L0 = sL + r * TM;
       const Cand* const L1 = sL + (32 + r) * TM;
@@ -443,9 +477,19 @@ static int check_shape(const char* who, int64_t n, int64_t I, int32_t d, int32_t
   return BPR_OK;
 }
 
+// item_filter NULL: the instantiation without a filter, with the arguments as they were
 template <bool PRE>
-static int launch_rank(const RankArgs& a, dim3 grid, size_t lds, bool vec, hipStream_t stream) {
-  return launch_kernel(vec ? k_rank<true, PRE> : k_rank<false, PRE>, rank_lds_bytes(), grid, dim3(256), lds, stream, a);
+static int launch_rank(const RankArgs& a, const uint32_t* item_filter, dim3 grid, size_t lds, bool vec,
+                       hipStream_t stream) {
+  if (item_filter != nullptr) {
+    Filtered<RankArgs> f = {};
+    static_cast<RankArgs&>(f) = a;
+    f.filter = item_filter;
+    return launch_kernel(vec ? k_rank<true, PRE, true> : k_rank<false, PRE, true>, rank_lds_bytes(), grid, dim3(256),
+                         lds, stream, f);
+  }
+  return launch_kernel(vec ? k_rank<true, PRE, false> : k_rank<false, PRE, false>, rank_lds_bytes(), grid, dim3(256),
+                       lds, stream, a);
 }
 
 }  // namespace bpr
@@ -466,17 +510,23 @@ extern "C" int bpr_rank_slices(int64_t n, int64_t I, int32_t d, int32_t item_sli
   return BPR_OK;
 }
 
-extern "C" int bpr_rank_rows(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
-                             const int32_t* users, int64_t n, const int64_t* tgt_indptr, const int32_t* tgt_items,
-                             const int64_t* seen_indptr, const int32_t* seen_indices, int32_t item_slices,
-                             void* workspace, int64_t workspace_bytes, int32_t* rank_out, int32_t* not_below_out,
-                             float* score_out, void* hip_stream) {
-  using namespace bpr;
-  if (int rc = check_shape("bpr_rank_rows", n, I, d, item_slices)) return rc;
+namespace bpr {
+namespace {
+
+// bpr_rank_rows (rows = "_rows", no filter) and bpr_rank_rows_filtered (rows = "_rows_filtered"): one body, the
+// messages under the entry point's own name.  The plan does not look at the filter.
+int rank_rows(const char* rows, const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+              const int32_t* users, int64_t n, const int64_t* tgt_indptr, const int32_t* tgt_items,
+              const int64_t* seen_indptr, const int32_t* seen_indices, const uint32_t* item_filter,
+              int32_t item_slices, void* workspace, int64_t workspace_bytes, int32_t* rank_out, int32_t* not_below_out,
+              float* score_out, void* hip_stream) {
+  const std::string who = std::string("bpr_rank") + rows;
+  if (int rc = check_shape(who.c_str(), n, I, d, item_slices)) return rc;
   if (n > 0 && (!P || !Q || !users || !tgt_indptr))
-    return fail(BPR_ERR_INVALID, "bpr_rank_rows: P, Q, users or tgt_indptr is NULL");
+    return fail(BPR_ERR_INVALID, who + ": P, Q, users or tgt_indptr is NULL");
+  if (int rc = check_item_filter(who.c_str(), item_filter)) return rc;
   const RankPlan p = plan_rank(n, I, item_slices);
-  if (int rc = check_workspace("bpr_rank", workspace, workspace_bytes, p.ws_bytes)) return rc;
+  if (int rc = check_workspace("bpr_rank", workspace, workspace_bytes, p.ws_bytes, nullptr, false, rows)) return rc;
   if (n == 0) return BPR_OK;
 
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -494,13 +544,13 @@ extern "C" int bpr_rank_rows(const float* P, const float* Q, const float* item_b
   BPR_HIP_CHECK(hipMemcpyAsync(lens, check, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   BPR_HIP_CHECK(hipStreamSynchronize(stream));
   if (ends[0] < 0 || ends[1] < ends[0] || lens[1] != 0)
-    return fail(BPR_ERR_INVALID, "bpr_rank_rows: tgt_indptr does not ascend");
+    return fail(BPR_ERR_INVALID, who + ": tgt_indptr does not ascend");
   if (lens[0] > RANK_TMAX)
-    return fail(BPR_ERR_INVALID, "bpr_rank_rows: a row holds " + std::to_string(lens[0]) + " targets, at most " +
+    return fail(BPR_ERR_INVALID, who + ": a row holds " + std::to_string(lens[0]) + " targets, at most " +
                                      std::to_string(RANK_TMAX) + " (RANK_TMAX) fit: split the row");
   if (ends[1] == ends[0]) return BPR_OK;
   if (!tgt_items || !rank_out || !not_below_out || !score_out)
-    return fail(BPR_ERR_INVALID, "bpr_rank_rows: tgt_items, rank_out, not_below_out or score_out is NULL");
+    return fail(BPR_ERR_INVALID, who + ": tgt_items, rank_out, not_below_out or score_out is NULL");
 
   RankArgs a = {};
   a.P = P; a.Q = Q; a.bias = item_bias; a.I = I; a.d = d; a.users = users; a.n = n; a.tptr = tgt_indptr;
@@ -508,19 +558,43 @@ extern "C" int bpr_rank_rows(const float* P, const float* Q, const float* item_b
   a.item_tiles = p.item_tiles; a.rank = rank_out; a.not_below = not_below_out; a.score = score_out;
   a.ws = reinterpret_cast<int32_t*>(workspace);
   const bool vec = vec_path(d, P, Q);
-  if (int rc = launch_rank<true>(a, dim3((unsigned)p.row_tiles), p.pre_lds, vec, stream)) return rc;
+  if (int rc = launch_rank<true>(a, item_filter, dim3((unsigned)p.row_tiles), p.pre_lds, vec, stream)) return rc;
   if (p.slices > 1) {  // bins and tied after: 0; place in the list: -1
     const size_t third = (size_t)n * RANK_TMAX * sizeof(int32_t);
     BPR_HIP_CHECK(hipMemsetAsync(a.ws, 0, 2 * third, stream));
     BPR_HIP_CHECK(hipMemsetAsync(a.ws + 2 * n * RANK_TMAX, 0xFF, third, stream));
   }
-  if (int rc = launch_rank<false>(a, dim3((unsigned)p.row_tiles, (unsigned)p.slices), p.lds, vec, stream)) return rc;
+  if (int rc = launch_rank<false>(a, item_filter, dim3((unsigned)p.row_tiles, (unsigned)p.slices), p.lds, vec, stream)) return rc;
   if (p.slices > 1) {
     hipLaunchKernelGGL(k_rank_finish, dim3((unsigned)((n * RANK_TMAX + 255) / 256)), dim3(256), 0, stream, a.ws, n,
                        tgt_indptr, rank_out, not_below_out);
     BPR_HIP_CHECK(hipGetLastError());
   }
   return BPR_OK;
+}
+
+}  // namespace
+}  // namespace bpr
+
+extern "C" int bpr_rank_rows(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                             const int32_t* users, int64_t n, const int64_t* tgt_indptr, const int32_t* tgt_items,
+                             const int64_t* seen_indptr, const int32_t* seen_indices, int32_t item_slices,
+                             void* workspace, int64_t workspace_bytes, int32_t* rank_out, int32_t* not_below_out,
+                             float* score_out, void* hip_stream) {
+  return bpr::rank_rows("_rows", P, Q, item_bias, I, d, users, n, tgt_indptr, tgt_items, seen_indptr, seen_indices,
+                        nullptr, item_slices, workspace, workspace_bytes, rank_out, not_below_out, score_out,
+                        hip_stream);
+}
+
+extern "C" int bpr_rank_rows_filtered(const float* P, const float* Q, const float* item_bias, int64_t I, int32_t d,
+                                      const int32_t* users, int64_t n, const int64_t* tgt_indptr,
+                                      const int32_t* tgt_items, const int64_t* seen_indptr,
+                                      const int32_t* seen_indices, const uint32_t* item_filter, int32_t item_slices,
+                                      void* workspace, int64_t workspace_bytes, int32_t* rank_out,
+                                      int32_t* not_below_out, float* score_out, void* hip_stream) {
+  return bpr::rank_rows("_rows_filtered", P, Q, item_bias, I, d, users, n, tgt_indptr, tgt_items, seen_indptr,
+                        seen_indices, item_filter, item_slices, workspace, workspace_bytes, rank_out, not_below_out,
+                        score_out, hip_stream);
 }
 
 // Test hook, not API (tests/test_rank_cpu.py sets its signature): the plan of a shape.  in = {n, I, d, item_slices,

@@ -397,6 +397,25 @@ extern "C" int bpr_test_filter_tiles(const uint32_t* words, int64_t I, const int
   return BPR_OK;
 }
 
+// Test hook, not API (tests/test_rank_neighbors_filter_cpu.py sets its signature): the `_from` functions of
+// bpr_item_filter.h on host words, for a table of N rows and the lower bound `first`.  out_words[wi] =
+// filter_word_from for every word; has[i] = filter_has_from for every id 0 .. 32 * words - 1; empty[t] =
+// filter_tile_empty_from and next[t] = filter_next_tile_from(t, tiles) for every tile.  Needs no GPU.
+extern "C" int bpr_test_filter_words_from(const uint32_t* words, int64_t N, int64_t first, uint32_t* out_words,
+                                          uint8_t* has, uint8_t* empty, int64_t* next) {
+  using namespace bpr;
+  if (!words || N < 1 || first < 0 || reinterpret_cast<uintptr_t>(words) % FILTER_ALIGN != 0)
+    return fail(BPR_ERR_INVALID, "bpr_test_filter_words_from: words (16-byte aligned), N >= 1, first >= 0");
+  const int64_t nw = filter_words(N), tiles = nw / FILTER_TILE_WORDS;
+  for (int64_t wi = 0; wi < nw; ++wi) out_words[wi] = filter_word_from(words, N, wi, first);
+  for (int64_t i = 0; i < 32 * nw; ++i) has[i] = filter_has_from(words, N, i, first) ? 1 : 0;
+  for (int64_t t = 0; t < tiles; ++t) {
+    empty[t] = filter_tile_empty_from(words, N, t, first) ? 1 : 0;
+    next[t] = filter_next_tile_from(words, N, t, tiles, first);
+  }
+  return BPR_OK;
+}
+
 // Test hook, not API (tests/test_recommend_cpu.py sets its signature): the plan of a shape.  in = {n, I, d, k,
 // item_slices, cus}; out = {slices, user_tiles, item_tiles, tile_users, tile_items, cap, lds, merge_lds, ws_bytes};
 // bounds[0 .. slices] = first item of each slice, then I.  Needs no GPU.

@@ -267,17 +267,19 @@ class Engine:
                         item_filter=item_filter)
 
     def rank_items(self, users: torch.Tensor, tgt_indptr: torch.Tensor, tgt_items: torch.Tensor,
-                   exclude_seen: bool = True, *, item_slices: int = 0):
+                   exclude_seen: bool = True, *, item_slices: int = 0,
+                   item_filter: Optional[torch.Tensor] = None):
         """(rank, not_below, score) of every target of every row (row r: user `users[r]`, targets
         `tgt_items[tgt_indptr[r]:tgt_indptr[r + 1]]`) among the user's eligible items, from the bound tables
         (`bpr_rank_rows`, see revisit_bpr/ranks.py).  Item 0 is never eligible; exclude_seen also leaves out the
         user's row of the CSR given to `bind_seen_csr`.  Rows an Adam / momentum / RMSprop optimizer has not
-        replayed yet are scored as they stand: `flush_lazy()` first (`Model.rank_items` does)."""
+        replayed yet are scored as they stand: `flush_lazy()` first (`Model.rank_items` does).  `item_filter`: a
+        packed filter (revisit_bpr/item_filter.py), only its items are eligible, a target outside it included."""
         from revisit_bpr.ranks import rank_items
 
         indptr, indices = self._keep.get("csr", (None, None)) if exclude_seen else (None, None)
         return rank_items(self.P, self.Q, self.item_bias, users, tgt_indptr, tgt_items, indptr, indices,
-                          item_slices=item_slices)
+                          item_slices=item_slices, item_filter=item_filter)
 
     def rerank(self, users: torch.Tensor, cand_items: torch.Tensor, k: int,
                cand_indptr: Optional[torch.Tensor] = None, exclude_seen: bool = True, *,
@@ -305,25 +307,29 @@ class Engine:
         return score_candidates(self.P, self.Q, self.item_bias, users, cand_items, cand_indptr, indptr, indices,
                                 layout=layout)
 
-    def similar_items(self, items: torch.Tensor, k: int, metric: str = "cosine", *, item_slices: int = 0):
+    def similar_items(self, items: torch.Tensor, k: int, metric: str = "cosine", *, item_slices: int = 0,
+                      item_filter: Optional[torch.Tensor] = None):
         """The `k` items most similar to each item of `items` by the rows of the bound item table
         (`bpr_neighbors_rows`, see revisit_bpr/similar.py): (ids [n, k] int32, scores [n, k] float32), sorted by
         score descending, ties by ascending id, padded with -1 / -inf; never the item itself, never item 0.
         `metric`: "cosine" or "dot".  The item bias plays no part.  Rows an Adam / momentum / RMSprop optimizer
         has not replayed yet are compared as they stand: `flush_lazy()` first (`Model.similar_items` does).  A
         freshly folded-in row is not in the table: `similar.neighbors(Q_new, engine.Q, torch.arange(m), k,
-        first=1)`."""
+        first=1)`.  `item_filter`: a packed filter over the items (revisit_bpr/item_filter.py), only its items
+        are returned."""
         from revisit_bpr.similar import similar_items
 
-        return similar_items(self.Q, items, k, metric, item_slices=item_slices)
+        return similar_items(self.Q, items, k, metric, item_slices=item_slices, item_filter=item_filter)
 
-    def similar_users(self, users: torch.Tensor, k: int, metric: str = "cosine", *, item_slices: int = 0):
+    def similar_users(self, users: torch.Tensor, k: int, metric: str = "cosine", *, item_slices: int = 0,
+                      item_filter: Optional[torch.Tensor] = None):
         """The `k` users most similar to each user of `users` by the rows of the bound user table: as
         `similar_items`, except that user 0 is a user like any other.  A freshly folded-in row:
-        `similar.neighbors(P_new, engine.P, torch.arange(m), k)`."""
+        `similar.neighbors(P_new, engine.P, torch.arange(m), k)`.  `item_filter`: a packed filter over the USERS
+        (`pack_item_filter(U, ...)`; user 0's bit counts), only its users are returned."""
         from revisit_bpr.similar import similar_users
 
-        return similar_users(self.P, users, k, metric, item_slices=item_slices)
+        return similar_users(self.P, users, k, metric, item_slices=item_slices, item_filter=item_filter)
 
     def diversify(self, cand_items: torch.Tensor, cand_scores: torch.Tensor, k: int, *, lam: float = 0.7,
                   metric: str = "cosine", scale: str = "none", return_mmr: bool = False, layout: int = 0):

@@ -203,7 +203,7 @@ def evaluate_fused(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: torc
 def evaluate_ranked(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: torch.Tensor,
                     eval_indptr: torch.Tensor, eval_items: torch.Tensor, seen_indptr, seen_indices,
                     ks=(5, 10, 20, 50, 100), auc: bool = False, extra: bool = False, per_user: bool = False,
-                    masked_negatives: bool = True):
+                    masked_negatives: bool = True, item_filter=None):
     """The keys of `evaluate_topk` from ONE `rank_items` call (revisit_bpr/ranks.py: the exact position of every
     held-out item among its user's unseen items, no [n, I] logits, no target matrix) and segment arithmetic on
     the few numbers per target it returns.  No cutoff limit: any k in `ks` (k > I behaves as k = I, as in
@@ -220,16 +220,77 @@ def evaluate_ranked(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: tor
     reference's metrics/map.py with its default normalisation: sum over the targets retrieved in the top k of
     (targets retrieved up to it) / (its position), over min(n_pos, k).
     per_user=True returns (means, per-user tensors [E] by the same keys), the role of the reference's
-    save_user_metrics."""
+    save_user_metrics.
+
+    `item_filter` (None: the whole catalogue): a packed filter (revisit_bpr/item_filter.py) — quality on a segment:
+    the long tail, one category, the new items.  The call then equals this function on the catalogue compacted to
+    item 0 and the filter's items: a target in 1 .. I-1 whose bit is clear is dropped from its row before n_pos is
+    counted (item 0 and ids out of range stay what they are without a filter: listed, never retrieved), ranks are
+    among the filter's unseen items (`rank_items(item_filter=)`), and the AUC's eligible items of a user are the
+    filter's items the user has not seen.  With masked_negatives=True the filtered-out items are negatives below
+    every positive, exactly like item 0 and the seen ones: n_neg = I - T, as without a filter."""
+    from revisit_bpr.item_filter import check_item_filter
     from revisit_bpr.ranks import rank_items
 
-    dev = P.device
     I = Q.shape[0]
     E = eval_users.numel()
+    item_filter = check_item_filter(item_filter, I)
     first, last = (int(v) for v in eval_indptr[[0, E]].tolist())
     ptr = (eval_indptr[:E + 1] - first).to(torch.int64)
     items = eval_items[first:last].to(torch.int32)
-    rank, not_below, score = rank_items(P, Q, item_bias, eval_users, ptr, items, seen_indptr, seen_indices)
+    if item_filter is not None:
+        ptr, items = drop_filtered_targets(ptr, items, I, item_filter)
+    rank, not_below, score = rank_items(P, Q, item_bias, eval_users, ptr, items, seen_indptr, seen_indices,
+                                        item_filter=item_filter)
+    n_elig = eligible_counts(I, eval_users, seen_indptr, seen_indices, item_filter)
+    return ranked_metrics(rank, not_below, score, ptr, items, I, n_elig, ks=ks, auc=auc, extra=extra,
+                          per_user=per_user, masked_negatives=masked_negatives)
+
+
+def drop_filtered_targets(ptr: torch.Tensor, items: torch.Tensor, I: int, item_filter: torch.Tensor):
+    """The target CSR (ptr int64 [E+1] from 0, items int32) without the targets in 1 .. I-1 whose bit of the packed
+    `item_filter` is clear; item 0 and ids out of range stay.  Returns (ptr, items)."""
+    from revisit_bpr.item_filter import unpack_item_filter
+
+    E = ptr.numel() - 1
+    elig = unpack_item_filter(item_filter, I)
+    judged = (items >= 1) & (items < I)
+    keep = ~judged | elig[items.long().clamp(0, I - 1)]
+    rows = torch.repeat_interleave(torch.arange(E, device=ptr.device), ptr[1:] - ptr[:-1])
+    cnt = torch.zeros(E, dtype=torch.int64, device=ptr.device).index_add_(0, rows, keep.to(torch.int64))
+    new_ptr = torch.zeros(E + 1, dtype=torch.int64, device=ptr.device)
+    new_ptr[1:] = torch.cumsum(cnt, 0)
+    return new_ptr, items[keep].contiguous()
+
+
+def eligible_counts(I: int, eval_users: torch.Tensor, seen_indptr, seen_indices, item_filter=None) -> torch.Tensor:
+    """int64 [E]: how many items are eligible for each eval user — 1 .. I-1 without the user's seen row, and with a
+    packed `item_filter` the filter's items among them, |F minus seen_u| (the filter's bits gathered at the seen
+    indices and summed per row: no kernel output is needed)."""
+    from revisit_bpr.item_filter import unpack_item_filter
+
+    users = eval_users.long()
+    if item_filter is None:
+        n_seen = (seen_indptr[users + 1] - seen_indptr[users]) if seen_indptr is not None else torch.zeros_like(users)
+        return I - 1 - n_seen
+    elig = unpack_item_filter(item_filter, I).clone()
+    elig[0] = False
+    total = elig.sum().to(torch.int64)
+    if seen_indptr is None:
+        return total.expand(users.numel()).clone()
+    run = torch.zeros(seen_indices.numel() + 1, dtype=torch.int64, device=elig.device)
+    run[1:] = torch.cumsum(elig[seen_indices.long()].to(torch.int64), 0)
+    return total - (run[seen_indptr[users + 1]] - run[seen_indptr[users]])
+
+
+def ranked_metrics(rank: torch.Tensor, not_below: torch.Tensor, score: torch.Tensor, ptr: torch.Tensor,
+                   items: torch.Tensor, I: int, n_elig: torch.Tensor, ks=(5, 10, 20, 50, 100), auc: bool = False,
+                   extra: bool = False, per_user: bool = False, masked_negatives: bool = True):
+    """`evaluate_ranked`'s arithmetic behind its `rank_items` call, on any device: (rank, not_below, score) aligned
+    with the targets `items` of the rows `ptr` (int64 [E+1] from 0), the catalogue size I and `n_elig` (int64 [E],
+    `eligible_counts`) -> the means, or (means, per-user tensors)."""
+    dev = rank.device
+    E = ptr.numel() - 1
     t_cnt = ptr[1:] - ptr[:-1]
     rows = torch.repeat_interleave(torch.arange(E, device=dev), t_cnt)
     total = rows.numel()
@@ -278,9 +339,7 @@ def evaluate_ranked(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: tor
             ap = per_row(torch.where(in_k, prec_at, torch.zeros_like(prec_at)))
             per[f"map@{k}"] = torch.nan_to_num(ap / n_pos.clamp(max=kk))
     if auc:
-        users = eval_users.long()
-        n_seen = (seen_indptr[users + 1] - seen_indptr[users]) if seen_indptr is not None else torch.zeros_like(users)
-        n_elig = I - 1 - n_seen  # eligible items of the user
+        n_masked = I - n_elig  # item 0, the seen items and (with a filter) the filtered-out ones
         # a retrievable target's other retrievable targets that score strictly below it: order the row's by
         # (rank), i.e. score descending; those after the last one of its score
         hi_idx = torch.nonzero(hit).reshape(-1)
@@ -299,7 +358,7 @@ def evaluate_ranked(P: torch.Tensor, Q: torch.Tensor, item_bias, eval_users: tor
         below = n_elig[rows] - 1 - not_below.long() - tgt_below  # eligible non-targets strictly below the target
         if masked_negatives:
             out_of_play = per_row(uniq & in_range & (rank < 0)).long()  # positives among the masked entries
-            below = below + torch.where(score > -1e13, (n_seen + 1 - out_of_play)[rows], torch.zeros_like(below))
+            below = below + torch.where(score > -1e13, (n_masked - out_of_play)[rows], torch.zeros_like(below))
             T = per_row(uniq & in_range)
             n_neg = I - T
         else:

@@ -1,4 +1,5 @@
-"""The item filter of `recommend`, `retrieve` and `sample_items` (`item_filter=`): a bitmap over the catalogue that
+"""The item filter of `recommend`, `retrieve`, `sample_items`, `rank_items` / `evaluate_ranked` and `neighbors` /
+`similar_items` / `similar_users` (`item_filter=`): a bitmap over the catalogue that
 says which items a call may return — in stock, of a category, licensed, not on a block list.  The kernels take it as
 one more eligibility rule beside "not item 0" and "not seen" (csrc/bpr_item_filter.h states the layout once), so a
 filtered call returns k items where filtering after the cut returns fewer, and `sample_items`' log_z normalises over
@@ -37,14 +38,19 @@ def _ids(ids, num_items: int, name: str, device) -> torch.Tensor:
     return ids
 
 
-def pack_item_filter(num_items: int, allow=None, deny=None, mask=None, device=None) -> torch.Tensor:
+def pack_item_filter(num_items: int, allow=None, deny=None, mask=None, device=None, first: int = 0) -> torch.Tensor:
     """The packed filter (int32 [4 * ceil(I / 128)]) of exactly one of: `allow`, the eligible ids; `deny`, the ids
     that are not (everything else is); `mask`, bool [I], True = eligible.  Ids are range-checked against
     [0, num_items) and may repeat.  `device`: where the result lives (default: where `mask` / the ids live, else the
-    CPU)."""
+    CPU).  `first`: ids below `first` are cleared.  The default stores every bit as given, item 0's too: the kernels
+    over an item table never read it as an item, and a filter over the USERS (`similar_users`, `neighbors(first=0)`)
+    keeps user 0, who is a user.  `first=1` clears item 0's bit in the stored words as well."""
     num_items = int(num_items)
     if num_items < 1:
         raise ValueError("num_items must be at least 1")
+    first = int(first)
+    if first < 0:
+        raise ValueError("first must be at least 0")
     if sum(x is not None for x in (allow, deny, mask)) != 1:
         raise ValueError("give exactly one of allow, deny and mask")
     given = allow if allow is not None else deny if deny is not None else mask
@@ -65,6 +71,7 @@ def pack_item_filter(num_items: int, allow=None, deny=None, mask=None, device=No
     nw = filter_words(num_items)
     bits = torch.zeros(nw * 32, dtype=torch.int64, device=device)  # (the tail stays zero)
     bits[:num_items] = m
+    bits[:min(first, num_items)] = 0
     weights = torch.ones(32, dtype=torch.int64, device=device) << torch.arange(32, dtype=torch.int64, device=device)
     words = (bits.view(nw, 32) * weights).sum(dim=1)               # in [0, 2^32)
     words = torch.where(words >= 2 ** 31, words - 2 ** 32, words)  # the same 32 bits as int32

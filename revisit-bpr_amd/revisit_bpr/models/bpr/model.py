@@ -548,19 +548,21 @@ class Model(torch.nn.Module):
         return items, scores
 
     def rank_items(self, users: torch.Tensor, tgt_indptr: torch.Tensor, tgt_items: torch.Tensor,
-                   exclude_seen: bool = True):
+                   exclude_seen: bool = True, item_filter: Optional[torch.Tensor] = None):
         """(rank, not_below, score), aligned with `tgt_items`, of every target of every row (row r: user
         `users[r]`, targets `tgt_items[tgt_indptr[r]:tgt_indptr[r + 1]]`) among the user's eligible items, from
         the engine's fused ranking kernel (revisit_bpr/ranks.py): item 0 and — exclude_seen — the items of the
         CSR given to `bind_seen_csr` are not eligible.  Rows behind the optimizer step are replayed first
         (`sync()`).  A user bias is added to the returned scores (it does not change a user's order).  Only the
-        MF scorer has a fused form."""
+        MF scorer has a fused form.  `item_filter`: a packed filter (revisit_bpr/item_filter.py), only its items
+        are eligible, a target outside it included."""
         if not self._fusable():
             raise NotImplementedError("rank_items needs the MF logits model in float32: other scorers have no "
                                       "fused ranking kernel")
         eng = self.engine()
         self.sync()
-        rank, not_below, score = eng.rank_items(users, tgt_indptr, tgt_items, exclude_seen=exclude_seen)
+        rank, not_below, score = eng.rank_items(users, tgt_indptr, tgt_items, exclude_seen=exclude_seen,
+                                                item_filter=item_filter)
         ub = self.logits_model._user_bias
         if ub is not None:
             cnt = tgt_indptr[1:] - tgt_indptr[:-1]
@@ -610,30 +612,34 @@ class Model(torch.nn.Module):
             score.add_(self._cand_user_bias(users, cand_items, cand_indptr))
         return score
 
-    def similar_items(self, items: torch.Tensor, k: int, metric: str = "cosine"):
+    def similar_items(self, items: torch.Tensor, k: int, metric: str = "cosine",
+                      item_filter: Optional[torch.Tensor] = None):
         """The `k` items most similar to each item of `items` (device tensor of item ids) by their embedding rows:
         (ids [n, k] int32, scores [n, k] float32) from the engine's fused neighbour kernel
         (revisit_bpr/similar.py), sorted by score descending, ties by ascending id, padded with -1 / -inf; never
         the item itself, never item 0.  `metric`: "cosine" or "dot"; biases play no part.  Rows behind the
         optimizer step are replayed first (`sync()`).  Only the MF scorer has a fused form.  A freshly folded-in
-        row is not in the table: `similar.neighbors(Q_new, Q, torch.arange(m), k, first=1)`."""
+        row is not in the table: `similar.neighbors(Q_new, Q, torch.arange(m), k, first=1)`.  `item_filter`: a
+        packed filter over the items (revisit_bpr/item_filter.py), only its items are returned."""
         if not self._fusable():
             raise NotImplementedError("similar_items needs the MF logits model in float32: other scorers have no "
                                       "fused neighbour kernel")
         eng = self.engine()
         self.sync()
-        return eng.similar_items(items, k, metric)
+        return eng.similar_items(items, k, metric, item_filter=item_filter)
 
-    def similar_users(self, users: torch.Tensor, k: int, metric: str = "cosine"):
+    def similar_users(self, users: torch.Tensor, k: int, metric: str = "cosine",
+                      item_filter: Optional[torch.Tensor] = None):
         """The `k` users most similar to each user of `users` by their embedding rows: as `similar_items`, except
         that user 0 is a user like any other.  A freshly folded-in row: `similar.neighbors(P_new, P,
-        torch.arange(m), k)`."""
+        torch.arange(m), k)`.  `item_filter`: a packed filter over the USERS (`pack_item_filter(U, ...)`; user 0's bit counts),
+        only its users are returned."""
         if not self._fusable():
             raise NotImplementedError("similar_users needs the MF logits model in float32: other scorers have no "
                                       "fused neighbour kernel")
         eng = self.engine()
         self.sync()
-        return eng.similar_users(users, k, metric)
+        return eng.similar_users(users, k, metric, item_filter=item_filter)
 
     def diversify(self, cand_items: torch.Tensor, cand_scores: torch.Tensor, k: int, *, lam: float = 0.7,
                   metric: str = "cosine", scale: str = "none", return_mmr: bool = False):

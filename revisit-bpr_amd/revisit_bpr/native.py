@@ -151,6 +151,9 @@ SIGNATURES = {
     "bpr_neighbors_slices": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     "bpr_neighbors_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32,
                                    c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "bpr_neighbors_rows_filtered": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int32,
+                                            c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                            c_void_p]),
     "bpr_rerank_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                 c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bpr_rerank_layout": (c_int, [c_int64, c_int32, c_int32, c_int64, c_int32, POINTER(c_int32), POINTER(c_int32)]),
@@ -163,6 +166,9 @@ SIGNATURES = {
     "bpr_rank_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
+    "bpr_rank_rows_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
     "bpr_fold_in_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p,
                                  c_int32, c_float, c_float, c_int32, c_void_p, c_void_p, c_uint64, c_uint64,
                                  c_void_p, c_void_p]),

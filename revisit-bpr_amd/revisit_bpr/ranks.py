@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
+from revisit_bpr.item_filter import check_item_filter, check_item_filter_early
 from revisit_bpr._serving import int32_ids, need_rocm, ptr, query, seen_csr, sliced_workspace, tables
 
 RANK_TMAX = 112  # bpr_rank_rows: targets of one kernel row (csrc/bpr_rank_plan.h); longer rows are split here
@@ -45,7 +46,8 @@ def split_rows(users: torch.Tensor, tgt_indptr: torch.Tensor, tmax: int = RANK_T
 @torch.no_grad()
 def rank_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor], users: torch.Tensor,
                tgt_indptr: torch.Tensor, tgt_items: torch.Tensor, seen_indptr: Optional[torch.Tensor] = None,
-               seen_indices: Optional[torch.Tensor] = None, *, item_slices: int = 0, check_users: bool = True):
+               seen_indices: Optional[torch.Tensor] = None, *, item_slices: int = 0, check_users: bool = True,
+               item_filter: Optional[torch.Tensor] = None):
     """For every target of every row — row r is user `users[r]` with the targets
     `tgt_items[tgt_indptr[r]:tgt_indptr[r + 1]]` (int64 [n+1] starting at 0, int32; a user may appear
     in several rows) — its place among the user's ELIGIBLE items: items 1 .. I-1 that are not in the
@@ -62,8 +64,16 @@ def rank_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tenso
     Runs on the current stream and waits for it (row lengths are read back; `bpr_rank_rows` reads
     them again for its own bound).  The kernel reads P[user] and the user's CSR row unchecked, so the
     ids are range-checked here first; `check_users=False` leaves that out.
+
+    `item_filter` (None: the whole catalogue): a packed filter of `revisit_bpr.item_filter.pack_item_filter` over
+    the I items.  An item is then eligible only if its bit is set as well, and a target whose bit is clear is itself
+    not eligible (-1 / -1 / -inf).  Scores are untouched: the answer is the unfiltered call's on the catalogue
+    compacted to item 0 and the filter's items in ascending order (`bpr_rank_rows_filtered`).  A segment's ranks
+    cannot be had by cutting the unfiltered ranks afterwards.
     """
+    item_filter = check_item_filter_early(item_filter, Q)
     P, Q, item_bias, U, I, d = tables(P, Q, item_bias)
+    item_filter = check_item_filter(item_filter, I)
     users = int32_ids(users, strict=True)
     n = users.numel()
     if tgt_indptr.dtype != torch.int64 or tgt_items.dtype != torch.int32:
@@ -72,8 +82,8 @@ def rank_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tenso
         raise ValueError("tgt_indptr must have n+1 entries")
     seen_indptr, seen_indices = seen_csr(seen_indptr, seen_indices, U)
     # (the shapes are checked on any device; the work is not done on any)
-    need_rocm("rank_items", "the tables, the rows and the targets", (P, Q, users, tgt_indptr, tgt_items),
-              (P, Q, item_bias, users, tgt_indptr, tgt_items, seen_indptr, seen_indices), "P")
+    need_rocm("rank_items", "the tables, the rows and the targets", (P, Q, users, tgt_indptr, tgt_items, item_filter),
+              (P, Q, item_bias, users, tgt_indptr, tgt_items, seen_indptr, seen_indices, item_filter), "P")
     lib = native.load()
     dev = P.device
     tgt_indptr, tgt_items = tgt_indptr.contiguous(), tgt_items.reshape(-1).contiguous()
@@ -98,6 +108,13 @@ def rank_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tenso
         n = users.numel()
     item_slices, ws, ws_bytes = sliced_workspace("rank", (n, I, d), item_slices, dev)
     with torch.cuda.device(dev):
+        if item_filter is not None:
+            native.check(lib.bpr_rank_rows_filtered(
+                P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, tgt_indptr.data_ptr(),
+                tgt_items.data_ptr(), ptr(seen_indptr), ptr(seen_indices), item_filter.data_ptr(), item_slices,
+                ptr(ws), ws_bytes, rank.data_ptr(), not_below.data_ptr(), score.data_ptr(),
+                torch.cuda.current_stream(dev).cuda_stream))
+            return rank, not_below, score
         native.check(lib.bpr_rank_rows(
             P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, tgt_indptr.data_ptr(),
             tgt_items.data_ptr(), ptr(seen_indptr), ptr(seen_indices), item_slices, ptr(ws), ws_bytes,

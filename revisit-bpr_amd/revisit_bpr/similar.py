@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
+from revisit_bpr.item_filter import check_item_filter, check_item_filter_early
 from revisit_bpr._serving import _table, int32_ids, need_rocm, ptr, query, sliced_workspace
 from revisit_bpr.recommend import TOPK_MAX
 
@@ -38,7 +39,7 @@ def slices(n: int, num_rows: int, d: int, k: int, item_slices: int = 0) -> int:
 @torch.no_grad()
 def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, metric: str = "cosine",
               exclude: Optional[torch.Tensor] = None, first: int = 0, item_slices: int = 0,
-              check_rows: bool = True):
+              check_rows: bool = True, item_filter: Optional[torch.Tensor] = None):
     """The `k` rows of `T` [N, d] most similar to each query `X[rows[r]]` (`X` [*, d]: `T` itself or another
     table of the same d), by `metric`: "cosine" (<x, t> / (|x| |t|)) or "dot" (<x, t>, the score of `recommend`
     without a bias).  Left out of row r: ids of `T` below `first`, the id `exclude[r]` (`exclude` None, or an
@@ -56,6 +57,12 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
     unchecked, so `rows` are range-checked against `X` (and `exclude` against `T`) here first, which waits for
     the device; `check_rows=False` leaves that out (ids known to be valid: a serving loop, a captured graph).
 
+    `item_filter` (None: the whole table): a packed filter of `revisit_bpr.item_filter.pack_item_filter` over the N
+    rows of `T`.  Only rows whose bit is set are returned; `first`, `exclude` and the cosine rule apply as before,
+    and so does every score: the result is the unfiltered call's on the eligible rows of `T` alone, ids mapped back,
+    k ids where filtering after the cut returns fewer (`bpr_neighbors_rows_filtered`).  With `first=0` row 0's bit
+    counts like any other.
+
     Rows folded in after training (`fold_in_items`, `fold_in`) are looked at against the catalogue with
     `neighbors(Q_new, Q, torch.arange(m), k, first=1)`: row r of the result is what the new item r resembles."""
     k = int(k)
@@ -67,7 +74,9 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
     first = int(first)
     if first < 0:
         raise ValueError("first must be at least 0")
-    need_rocm("neighbors", "the tables and the row list", (X, T, rows, exclude), (X, T, rows, exclude), "X")
+    item_filter = check_item_filter_early(item_filter, T)
+    need_rocm("neighbors", "the tables and the row list", (X, T, rows, exclude, item_filter),
+              (X, T, rows, exclude, item_filter), "X")
     lib = native.load()
     same = X is T
     T = _table(T, "T")
@@ -75,6 +84,7 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
     if X.dim() != 2 or T.dim() != 2 or X.shape[1] != T.shape[1]:
         raise ValueError("X [*, d] and T [N, d] must share the embedding dim")
     (N, d), dev = T.shape, X.device
+    item_filter = check_item_filter(item_filter, N)
     rows = int32_ids(rows, strict=False)
     n = rows.numel()
     if exclude is not None:
@@ -90,6 +100,12 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
     item_slices, ws, ws_bytes = sliced_workspace("neighbors", (n, N, d, k), item_slices, dev, pre=(code,))
     with torch.cuda.device(dev):
+        if item_filter is not None:
+            native.check(lib.bpr_neighbors_rows_filtered(
+                X.data_ptr(), T.data_ptr(), N, d, rows.data_ptr(), n, ptr(exclude), first, code, item_filter.data_ptr(),
+                k, item_slices, ptr(ws), ws_bytes, ids.data_ptr(), scores.data_ptr(),
+                torch.cuda.current_stream(dev).cuda_stream))
+            return ids, scores
         native.check(lib.bpr_neighbors_rows(
             X.data_ptr(), T.data_ptr(), N, d, rows.data_ptr(), n, ptr(exclude), first, code, k, item_slices,
             ptr(ws), ws_bytes, ids.data_ptr(), scores.data_ptr(),
