@@ -287,3 +287,111 @@ def excused(got_neg, got_tries, res):
     `run` result."""
     diff = (got_neg != res["neg"]) | (got_tries != res["tries"])
     return int(diff.sum()), int((diff & ~(res["gap"] < res["bound"])).sum())
+
+
+# ---- the six row layouts: what tests/test_vstream_widths_cpu.py and tests/test_gpu_vstream_widths.py share ---------------
+# per layout the smallest d, the largest d and a ragged d (not a multiple of G), where PICK_CASES / STEP_CASES of the
+# files above do not already run it; all three for (64, 8) and (64, 16), which they never reach
+WIDTHS = [1, 20, 33, 64, 65, 129, 257, 500, 512, 513, 1000, 1024]
+
+
+def layout(d):
+    """(G, E) of csrc/bpr_group_shape.h, restated: G lanes per row, E elements per lane (opt_replay_model.layout)."""
+    G = 32 if d <= 128 else 64
+    per_lane = -(-d // G)
+    E = next(e for e in ((1, 2, 4) if G == 32 else (4, 8, 16)) if per_lane <= e)
+    return G, E
+
+
+def tail_start(d):
+    """First column of a row's last LIVE element slot: G * (E - 1) where the width fills the layout, the start of the
+    last partly filled slot where it is ragged (G * (E - 1) >= d would name no column at all)."""
+    G, E = layout(d)
+    return G * (min(E, -(-d // G)) - 1)
+
+
+# the step, given the reported picks: (d, bias, optimizer, kind, K, B, vs_direct).  Every width under both kinds; every
+# width >= 257 under all five optimizers; bias on and off, vs_direct -1 / 0 / 1, B 1 / 4 / 32, K 1 / 4 / 32 (dynamic)
+# and 1 / 10 / 32 (WARP) — each value of each, not their product.  d = 65: Adam and RMSprop with item_bias, the E = 4
+# kernels that spill.
+WIDTH_STEP_CASES = [
+    (1, True, "sgd", DYNAMIC, 4, 32, 1), (1, False, "adam_09", WARP, 10, 4, -1),
+    (20, False, "rmsprop", DYNAMIC, 32, 32, 0), (20, True, "adagrad", WARP, 32, 1, -1),
+    (33, True, "nesterov", DYNAMIC, 1, 4, -1), (33, False, "adam_09", WARP, 10, 32, 1),
+    (64, False, "adagrad", DYNAMIC, 4, 32, 1), (64, True, "rmsprop", WARP, 1, 32, 0),
+    (65, True, "adam_09", DYNAMIC, 4, 32, 1), (65, True, "rmsprop", WARP, 10, 32, 0),
+    (129, False, "sgd", DYNAMIC, 32, 32, 0), (129, True, "nesterov", WARP, 32, 4, -1),
+    (257, True, "sgd", DYNAMIC, 4, 32, 1), (257, False, "nesterov", WARP, 10, 32, 0),
+    (257, True, "adam_09", DYNAMIC, 32, 4, -1), (257, False, "rmsprop", WARP, 1, 32, 1),
+    (257, True, "adagrad", WARP, 32, 1, -1),
+    (500, False, "sgd", WARP, 10, 32, 1), (500, True, "nesterov", DYNAMIC, 4, 32, 1),
+    (500, False, "adam_09", WARP, 32, 32, 0), (500, True, "rmsprop", DYNAMIC, 1, 4, -1),
+    (500, False, "adagrad", DYNAMIC, 32, 32, 0),
+    (512, True, "sgd", DYNAMIC, 32, 1, -1), (512, False, "nesterov", WARP, 1, 32, 1),
+    (512, True, "adam_09", WARP, 10, 32, 1), (512, False, "rmsprop", DYNAMIC, 4, 32, 0),
+    (512, True, "adagrad", WARP, 10, 4, -1),
+    (513, False, "sgd", WARP, 32, 4, -1), (513, True, "nesterov", DYNAMIC, 32, 32, 0),
+    (513, False, "adam_09", DYNAMIC, 4, 32, 1), (513, True, "rmsprop", WARP, 10, 32, 0),
+    (513, True, "adagrad", DYNAMIC, 1, 32, 1),
+    (1000, True, "sgd", WARP, 1, 32, 0), (1000, False, "nesterov", DYNAMIC, 4, 4, -1),
+    (1000, True, "adam_09", WARP, 10, 32, 0), (1000, False, "rmsprop", DYNAMIC, 32, 32, 1),
+    (1000, False, "adagrad", WARP, 32, 32, 1),
+    (1024, False, "sgd", DYNAMIC, 4, 32, 0), (1024, True, "nesterov", WARP, 10, 1, -1),
+    (1024, False, "adam_09", DYNAMIC, 1, 32, 0), (1024, True, "rmsprop", WARP, 32, 32, 1),
+    (1024, True, "adagrad", DYNAMIC, 4, 4, -1),
+]
+STEP_SEED = 3  # the problem's seed of every step case (tests/test_gpu_vstream_scored.py's)
+# later batches' picks: (d, bias, optimizer, kind, K, B, seed).  The seeds are those at which at most CAP * N triples
+# have their deciding gap inside the bound (at d >= 1000 many seeds have 5 - 10: tests/test_vstream_widths_cpu.py
+# asserts the count), so the cap cannot bite a kernel that scores on the right views.
+WIDTH_PICK_CASES = [
+    (33, True, "sgd", WARP, 10, 32, 21),
+    (65, False, "rmsprop", DYNAMIC, 4, 4, 21),
+    (129, True, "adagrad", WARP, 32, 32, 21),
+    (257, False, "adam_09", DYNAMIC, 32, 32, 22),
+    (500, True, "nesterov", WARP, 10, 4, 21),
+    (512, False, "adagrad", DYNAMIC, 4, 32, 22),
+    (513, True, "rmsprop", WARP, 32, 32, 22),
+    (1000, False, "adam_09", WARP, 10, 32, 22),
+    (1000, True, "adagrad", DYNAMIC, 32, 4, 31),
+    (1024, True, "sgd", DYNAMIC, 4, 32, 23),
+    (1024, False, "nesterov", WARP, 32, 1, 21),
+]
+# the 256-thread block (max_inflight = 0) with ONE virtual batch (B >= n): (d, bias, optimizer, sampler, K, seed);
+# sampler 1 is the uniform kind on the staged list (K unused).  (64, 8) and (64, 16) under every optimizer and both
+# scored kinds, the other four layouts under both scored kinds.
+UNIFORM = 1  # BPR_NEG_UNIFORM
+WIDTH_FULL_CASES = [
+    (20, False, "sgd", DYNAMIC, 4, 41), (20, True, "nesterov", WARP, 10, 42),
+    (64, True, "adam_09", DYNAMIC, 4, 43), (64, False, "adagrad", WARP, 10, 44),
+    (65, True, "rmsprop", DYNAMIC, 32, 45), (65, True, "adam_09", WARP, 10, 46),
+    (129, False, "adagrad", DYNAMIC, 32, 47), (129, True, "sgd", WARP, 32, 48),
+    (257, True, "rmsprop", DYNAMIC, 32, 49), (257, False, "sgd", WARP, 32, 50), (257, True, "nesterov", UNIFORM, 0, 51),
+    (512, True, "adagrad", DYNAMIC, 4, 52), (512, False, "adam_09", WARP, 10, 53), (512, False, "adagrad", UNIFORM, 0, 54),
+    (513, True, "adam_09", DYNAMIC, 1, 55), (513, False, "nesterov", WARP, 10, 56), (513, True, "rmsprop", UNIFORM, 0, 57),
+    (1024, False, "adagrad", DYNAMIC, 32, 58), (1024, True, "adam_09", WARP, 32, 59), (1024, False, "rmsprop", WARP, 1, 60),
+    (1024, True, "sgd", UNIFORM, 0, 61), (1024, False, "nesterov", DYNAMIC, 4, 62),
+]
+
+
+def given_loop(P, Q, bias, users, pos, neg, B, cfg, alphas):
+    """The mini-batch loop on given negatives, in place: `uniform_loop` without the draw.  Returns (state, touched rows)."""
+    st = new_state(P, Q, bias, cfg)
+    rows = [set(), set(), set()]
+    for b_idx, lo in enumerate(range(0, len(users), B)):
+        sl = slice(lo, lo + B)
+        gP, gQ, gb, ru, ri, rb, _ = batch_grad(P, Q, bias, users[sl], pos[sl], neg[sl], None, alphas)
+        opt_step(P, Q, bias, st, (gP, gQ, gb), (ru, ri, rb), cfg, b_idx + 1)
+        for s, r in zip(rows, (ru, ri, rb)):
+            s.update(int(x) for x in r)
+    return st, rows
+
+
+def want_state(cfg, st):
+    """The state tensors the engine keeps for an optimizer, by the names of Engine.alloc_opt_state."""
+    out = {}
+    if cfg["kind"] in (1, 2) or cfg.get("momentum", 0) > 0:
+        out.update(mP=st["mP"], mQ=st["mQ"], mb=st.get("mb"))
+    if cfg["kind"] in (2, 3, 4):
+        out.update(vP=st["vP"], vQ=st["vQ"], vb=st.get("vb"))
+    return out
