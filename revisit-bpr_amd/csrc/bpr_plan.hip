@@ -261,8 +261,13 @@ int plan_epoch_impl(bpr_ctx* c, const int32_t* users_in, const int32_t* pos_in, 
   }
   const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
   size_t bytes = c->plan_tmp_bytes;  // sized for 64-bit keys: enough for 32-bit ones
-  if (ubits + cbits <= 32) {
-    uint32_t* k32 = reinterpret_cast<uint32_t*>(c->plan_keys);
+  // (a sort on the bits [ubits, 32) of 32-bit keys goes to the 64-bit route: for a few thousand to a million keys
+  // rocprim sorts by merging under the mask ((K)1 << end_bit) - 1 ^ ((K)1 << begin_bit) - 1, and a shift by the whole
+  // width of K leaves the USER bits in that mask — the plan came out sorted by user, not by chunk.  begin_bit = 0
+  // compares whole keys, no mask.)
+  const bool keys32 = ubits + cbits <= 32 && !(c->tune_plan_sorted && ubits + cbits == 32);
+  if (keys32) {
+    uint32_t* k32 =reinterpret_cast<uint32_t*>(c->plan_keys);
     uint32_t* k32s = reinterpret_cast<uint32_t*>(c->plan_keys_sorted);
     hipLaunchKernelGGL(k_plan_keys<uint32_t>, dim3(grid), dim3(256), 0, c->stream, users_in, n,
                        chunk, half_bits, ubits, seed, k32);

@@ -387,7 +387,7 @@ def test_samplers_with_a_64_bit_generator_seed_draw_the_oracles_stream():
 
 
 # ---- 9. seeds that differ only in the high word ----------------------------------------------------------------------
-def test_plan_epoch_and_shuffle_epoch_read_the_high_word_of_the_seed():
+def test_plan_epoch_and_shuffle_epoch_read_the_high_word_of_the_seed():  # (exactly: tests/test_gpu_plan.py)
     from revisit_bpr.datasets import synthetic
 
     data = synthetic.generate(3000, 800, 70_000, median_per_user=15, seed=5)

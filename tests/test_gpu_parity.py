@@ -657,7 +657,7 @@ def test_stream_full_chip_learns_and_never_picks_seen(seen, monkeypatch):
 # ------------------------------------------------------------------------------------------------
 # epoch planner + user-grouped STREAM
 # ------------------------------------------------------------------------------------------------
-def test_plan_epoch_is_a_grouped_random_partition():
+def test_plan_epoch_is_a_grouped_random_partition():  # (bit for bit against a host model: tests/test_gpu_plan.py)
     from revisit_bpr.datasets import synthetic
 
     data = synthetic.generate(3000, 800, 70000, median_per_user=15, seed=5)

@@ -409,7 +409,7 @@ def test_full_concurrency_picks_match_the_oracle(sampler, seen, monkeypatch):
     assert np.array_equal(e.P.cpu().numpy(), P) and np.array_equal(e.Q.cpu().numpy(), Q)
 
 
-def test_shuffle_epoch_is_a_seeded_permutation():
+def test_shuffle_epoch_is_a_seeded_permutation():  # (bit for bit against a host model: tests/test_gpu_plan.py)
     from revisit_bpr.engine import Engine
 
     e = Engine(torch.zeros(10, 4, device="cuda"), torch.zeros(10, 4, device="cuda"))
