@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <new>
 
+#include "bpr_ctx_state.h"
 #include "bpr_host.h"
 
 namespace bpr {
@@ -184,8 +185,8 @@ int comm_item_sync(bpr_ctx* c, bool finish_only) {
     if (m->pending) BPR_HIP_CHECK(hipStreamSynchronize(m->stream));
     if (int rc = comm_rebase(c, m)) return rc;
   }
-  c->keys_cut = false;  // the item table moves
-  c->bias_w_valid = false;  // ... and the item_bias with it
+  items_moved(c);
+  bias_moved(c);  // (the reconciliation carries the item_bias with the table)
   const float scale = 1.0f;
   if (m->pending) {
     // fold the other ranks' contribution of the reconciliation in flight ...

@@ -1,4 +1,5 @@
-// bpr_ctx.h — private state of a bpr_ctx (shared by bprcore.hip, bpr_refresh.hip, bpr_plan.hip, bpr_hot.hip and the other translation units).
+// bpr_ctx.h — private state of a bpr_ctx (shared by every translation unit of libbprcore).  The fields marked "(state)"
+// are the cross-call flags: what each means and who may assign it is in bpr_ctx_state.h, nowhere else.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -91,26 +92,20 @@ struct bpr_ctx {
   const float* snap_keys[2] = {nullptr, nullptr};
   const int32_t* meta_front = nullptr;
   const float* keys_front = nullptr;
-  bool keys_front_stale = false;  // a later cut has overwritten the key buffer the partial FRONT snapshot was sorted from
+  bool keys_front_stale = false;  // (state)
   // split refresh (bpr_adaptive_refresh_begin / _commit): the keys are cut on `stream`, the sort
   // runs on `side` while the caller keeps launching on `stream`, commit orders the swap
   hipStream_t side = nullptr;
   bool side_owned = false;
   hipEvent_t ev_keys = nullptr, ev_sorted = nullptr;
-  bool refresh_pending = false;
+  bool refresh_pending = false;  // (state)
   // what the refresh into either snapshot buffer ran (refresh_impl), and the buffer of the last completed one
   // (bpr_adaptive_refresh_info; -1: none yet)
   struct RefreshInfo { int route = -1, g = 0, items = 0, sub = 0, f_lo = 0, nf = 0; };
   RefreshInfo refresh_info[2];
   int refresh_done = -1;
   bool part_pending = false;  // bpr_adaptive_refresh_part: this rank's columns are sorted, publish pending
-  // bpr_train_stream_cut: the launch's epilogue already cut the next snapshot's keys (keysT); the
-  // next bpr_adaptive_refresh_begin only queues the sort.  Any call that moves the item table
-  // afterwards clears it.
-  bool keys_cut = false;
-  bool keys_event = false;  // ev_keys was recorded by the cut kernel itself (hipExtLaunchKernelGGL)
-  bool keys_on_side = false;  // ... and that cut ran on `side` (bpr_train_stream_acut): a sort on `stream` waits for it
-  bool acut_pending = false;  // an asynchronous cut may still be reading Q, the hot deltas and a launch's partials
+  bool keys_cut = false, keys_event = false, keys_on_side = false, acut_pending = false;  // (state)
   // private scratch — epoch planner
   uint64_t* plan_keys = nullptr;
   uint64_t* plan_keys_sorted = nullptr;
@@ -141,20 +136,10 @@ struct bpr_ctx {
   // hot_tier is on the launches leave their deltas in the block for bpr_hot_exchange
   bool hot_explicit = false;
   bool hot_tier = false;
-  // bpr_train_stream_cut under the hot tier: the launch's epilogue (loss partials) is left to the
-  // bpr_sync_cut that must follow
-  // bpr_train_stream_acut: the cut of the next snapshot runs on the side stream beside the NEXT
-  // launch and folds nothing — the hot deltas stay in the block until somebody needs the table
-  // whole (hot_fold_impl: every other entry point, bpr_hot_fold)
-  bool hot_unfolded = false;
-  // under the hot tier: the global block holds deltas of a launch since the last bpr_hot_exchange with cut = 1 /
-  // bpr_sync_cut.  The LDS-tier kernel reads a hot row of its LDS rows as Q + its own LDS delta, leaving those out:
-  // while this is set the plain kernel runs
-  bool hot_uncut = false;
-  bool acut_call = false;
-  int acut_parity = 0;
+  bool hot_unfolded = false, hot_uncut = false;  // (state)
+  int acut_parity = 0;  // bpr_train_stream_acut (acut_fold = 0): which of the two sets of loss partials the next launch writes
   hipEvent_t ev_launch = nullptr;
-  int defer_blocks = 0;
+  int defer_blocks = 0;  // (state, with the two below)
   float* defer_out = nullptr;
   bool defer_pending = false;
   int32_t* hot_canon = nullptr;  // [hot_H]
@@ -189,7 +174,7 @@ struct bpr_ctx {
   float* bias_w = nullptr;  // [I * BIAS_LINE] the item_bias k_stream works on, one item per 128-B line (bpr_kernels.h)
   int64_t bias_w_rows = 0;
   bool bias_track = false;    // bpr_set_bias_tracking: skip the refill while the wide table is known to be current
-  bool bias_w_valid = false;  // wide table == dense vector (written back by the last launch, untouched since)
+  bool bias_w_valid = false;  // (state, with bias_w_of)
   const float* bias_w_of = nullptr;
   float* dev_scalars = nullptr;
   // timing of the dominant kernel
@@ -203,7 +188,7 @@ struct bpr_ctx {
 };
 
 namespace bpr {
-void set_error(const std::string& msg);
+void set_error(const std::string& msg);                         // bprcore.hip
 int refresh_impl(bpr_ctx* c, bool split, int f_lo, int f_hi);  // bpr_refresh.hip: split = sort on c->side, no swap
 int refresh_publish_impl(bpr_ctx* c);       // bpr_refresh.hip
 int refresh_alloc(bpr_ctx* c);             // bpr_refresh.hip: the snapshot buffers (idempotent)
@@ -216,8 +201,8 @@ int heavy_build_impl(bpr_ctx* c);   // bpr_hot.hip
 void heavy_free(bpr_ctx* c);        // bpr_hot.hip
 int hot_build_impl(bpr_ctx* c, const int32_t* pos, int64_t n);  // bpr_hot.hip
 int hot_set_items_impl(bpr_ctx* c, const int32_t* items, int H, const uint32_t* counts);  // bpr_hot.hip
-int flush_deferred_stats(bpr_ctx* c);  // bprcore.hip: loss partials a hot-tier cut launch left behind
-int hot_fold_impl(bpr_ctx* c);  // bprcore.hip: fold deltas left by bpr_train_stream_acut (no-op otherwise)
+int flush_deferred_stats(bpr_ctx* c);  // bpr_stream_launch.hip: loss partials a hot-tier cut launch left behind
+int hot_fold_impl(bpr_ctx* c);  // bpr_stream_launch.hip: fold deltas left by bpr_train_stream_acut (no-op otherwise)
 void hot_free(bpr_ctx* c);                                       // bpr_hot.hip
 int plan_chunk_impl(bpr_ctx* c, const int32_t* users_in, const int32_t* pos_in, int64_t n, int64_t chunk,  // bpr_plan.hip
                     uint64_t seed, int64_t index, int32_t* users_out, int32_t* pos_out, hipStream_t st);

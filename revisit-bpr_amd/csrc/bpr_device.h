@@ -334,7 +334,7 @@ static_assert(WALK_UNROLL == 4, "the walk fetches one dwordx4 per lane and trip"
 // holds entries base + 4*gl + {0..3}; 512 contiguous bytes per group of 32).  `order` carries
 // ORDER_PAD entries of slack on both ends, so the last vector of the first / last column may
 // overhang; overhanging entries are masked to 0 (the pad item: never a candidate).
-constexpr int ORDER_PAD = WALK_UNROLL;  // == BPR_ORDER_PAD (bpr_ctx.h), checked in bprcore.hip
+constexpr int ORDER_PAD = WALK_UNROLL;  // == BPR_ORDER_PAD (bpr_ctx.h), checked in bpr_stream_launch.hip
 
 // PARTIAL snapshots (bpr_sort.h k_sort_partial): only the two ends of a column are in exact order,
 // [0, kt) and [I - kb, I); the middle is bucketed — bins in order, any order inside a bin, the first

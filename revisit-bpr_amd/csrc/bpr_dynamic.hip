@@ -1,5 +1,5 @@
 // bpr_dynamic.hip — dynamic negative sampling (bpr_scored.h) in a translation unit of its own, so that it compiles
-// beside bprcore.hip and leaves that file's kernels alone: the k_stream<..., NEG_DYNAMIC, ...> instantiations (the
+// beside bpr_stream_launch.hip and leaves that file's kernels alone: the k_stream<..., NEG_DYNAMIC, ...> instantiations (the
 // group widths and "seen?" structures the launcher instantiates for the uniform sampler, plain kernel only) and the
 // two entry points bpr_set_dynamic / bpr_sample_dynamic — and, for both scored kinds, the stand-alone kernel
 // k_sample_scored with its launcher (bpr_warp.hip calls it).
@@ -12,7 +12,7 @@
 
 namespace bpr {
 
-// ---- the fused path: which k_stream a STREAM launch with BPR_NEG_DYNAMIC runs (launch_stream, bprcore.hip) ------
+// ---- the fused path: which k_stream a STREAM launch with BPR_NEG_DYNAMIC runs (launch_stream, bpr_stream_launch.hip)
 int stream_kernel_dynamic(const bpr_ctx* c, int seen, StreamKernelFn* out) {
   return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
     using T = decltype(tag);

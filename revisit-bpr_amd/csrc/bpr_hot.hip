@@ -1,12 +1,16 @@
 // bpr_hot.hip — what is built once per training set or seen CSR: the hot-item list with its delta block
-// (bpr_set_hot_items, the STREAM kernel's replica rows) and the heavy users' seen bitmaps.
+// (bpr_set_hot_items, the STREAM kernel's replica rows) and the heavy users' seen bitmaps; at the end, the entry
+// points of the hot block, the hot tier and the item reconciliation passes (bpr_hot_kernels.h).
 #include <stdlib.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "bpr_ctx.h"
+#include "bpr_ctx_state.h"
+#include "bpr_host.h"
+#include "bpr_hot_kernels.h"
 
 namespace bpr {
 
@@ -33,7 +37,7 @@ void hot_free(bpr_ctx* c) {
   c->hot_canon = c->hot_code = c->hot_by_rank = nullptr;
   c->hot_explicit = false;
   c->hot_tier = false;
-  c->hot_uncut = false;
+  hot_block_cut(c);
   c->hot_delta_alloc = nullptr;
   c->hot_slot = c->hot_items = nullptr;
   c->hot_delta = nullptr;
@@ -292,4 +296,142 @@ int heavy_build_impl(bpr_ctx* c) {
   return BPR_OK;
 }
 
+// one elementwise pass of the item reconciliation over n elements of the four tables, on the caller's stream
+template <typename K, typename... A>
+static int item_pass(const char* who, const void* q, const void* base, const void* own, const void* tot, int64_t n,
+                     void* hip_stream, K kernel, A... args) {
+  if (n < 0 || (n > 0 && (!q || !base || !own || !tot))) return fail(BPR_ERR_INVALID, std::string(who) + ": bad argument");
+  if (n == 0) return BPR_OK;
+  const unsigned grid = (unsigned)std::min<int64_t>((n + 1023) / 1024, 4096);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, args...);
+  BPR_HIP_CHECK(hipGetLastError());
+  return BPR_OK;
+}
+
 }  // namespace bpr
+
+using namespace bpr;
+extern "C" {
+
+int bpr_item_delta(const float* q, const float* base, float* own, float* tot, int64_t n, void* hip_stream) {
+  return item_pass("bpr_item_delta", q, base, own, tot, n, hip_stream, k_item_delta, q, base, own, tot, n);
+}
+
+int bpr_item_fold(float* q, float* base, const float* own, const float* tot, float scale, int32_t rebase, int64_t n,
+                  void* hip_stream) {
+  return item_pass("bpr_item_fold", q, base, own, tot, n, hip_stream, k_item_fold, q, base, own, tot, scale, rebase, n);
+}
+
+int bpr_item_fold_delta(float* q, float* base, float* own, float* tot, float scale, int64_t n, void* hip_stream) {
+  return item_pass("bpr_item_fold_delta", q, base, own, tot, n, hip_stream, k_item_fold_delta, q, base, own, tot, scale, n);
+}
+
+int bpr_set_hot_rows(bpr_ctx* c, int32_t hot_rows, int32_t replicas) {
+  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_set_hot_rows: ctx is NULL");
+  if (hot_rows < 0 || hot_rows > 32768)
+    return fail(BPR_ERR_INVALID, "bpr_set_hot_rows: hot_rows must be in [0, 32768]");
+  if (hot_rows > 0 && replicas != 1 && replicas != 2 && replicas != 4 && replicas != 8)
+    return fail(BPR_ERR_INVALID, "bpr_set_hot_rows: replicas must be 1, 2, 4 or 8");
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  BPR_HIP_CHECK(hipStreamSynchronize(c->stream));
+  hot_free(c);  // rebuilt by the next bpr_plan_epoch
+  c->hot_rows_opt = hot_rows;
+  c->hot_reps_opt = hot_rows > 0 ? replicas : 0;
+  return BPR_OK;
+}
+
+int bpr_set_hot_lds(bpr_ctx* c, int32_t rows, int32_t always) {
+  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_set_hot_lds: ctx is NULL");
+  if (rows < 0 || rows > 32767) return fail(BPR_ERR_INVALID, "bpr_set_hot_lds: rows must be in [0, 32767]");
+  c->tune_hot_lds = rows;
+  c->tune_hot_lds_force = always != 0;
+  return BPR_OK;
+}
+
+int bpr_set_hot_items(bpr_ctx* c, const int32_t* items_host, int32_t H, const uint32_t* counts_host) {
+  if (int rc = check_bound(c, "bpr_set_hot_items")) return rc;
+  if (H < 0 || H > 32768 || H >= c->I || (H > 0 && items_host == nullptr))
+    return fail(BPR_ERR_INVALID, "bpr_set_hot_items: need 0 <= H <= min(32768, I - 1) item ids");
+  if (c->hot_tier) return fail(BPR_ERR_INVALID, "bpr_set_hot_items: the hot tier is on (bpr_hot_tier_end first)");
+  std::vector<char> seen((size_t)c->I, 0);
+  for (int k = 0; k < H; ++k) {
+    const int32_t it = items_host[k];
+    if (it < 0 || it >= c->I || it == c->pad_item || seen[it])
+      return fail(BPR_ERR_INVALID, "bpr_set_hot_items: ids must be distinct item rows, not the pad row");
+    seen[it] = 1;
+  }
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  BPR_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return hot_set_items_impl(c, items_host, H, counts_host);
+}
+
+int bpr_hot_rows(bpr_ctx* c, int32_t* rows_host) {
+  if (c == nullptr || rows_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_hot_rows: NULL argument");
+  *rows_host = c->hot_H;
+  return BPR_OK;
+}
+
+int bpr_hot_tier_begin(bpr_ctx* c, float* hot_base) {
+  if (int rc = check_bound(c, "bpr_hot_tier_begin")) return rc;
+  if (c->hot_H <= 0 || !c->hot_explicit)
+    return fail(BPR_ERR_INVALID, "bpr_hot_tier_begin: no hot set (bpr_set_hot_items first: the ranks "
+                                 "must agree on it)");
+  if (hot_base == nullptr) return fail(BPR_ERR_INVALID, "bpr_hot_tier_begin: hot_base is NULL");
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  const int64_t n = (int64_t)c->hot_H * c->d;
+  hipLaunchKernelGGL(k_hot_gather, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256),
+                     0, c->stream, c->Q, c->hot_items, c->hot_canon, hot_base, c->hot_H, c->d);
+  BPR_HIP_CHECK(hipGetLastError());
+  c->hot_tier = true;
+  return BPR_OK;
+}
+
+int bpr_hot_tier_end(bpr_ctx* c) {
+  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_hot_tier_end: ctx is NULL");
+  if (int rc = flush_deferred_stats(c)) return rc;
+  c->hot_tier = false;  // (the caller has folded everything: bpr_hot_exchange with cut = 1 last)
+  return BPR_OK;
+}
+
+int bpr_hot_exchange(bpr_ctx* c, float* hot_base, float* tot, int32_t fold_prev, int32_t cut,
+                     float* cold_base) {
+  if (int rc = check_bound(c, "bpr_hot_exchange")) return rc;
+  if (!c->hot_tier) return fail(BPR_ERR_INVALID, "bpr_hot_exchange: the hot tier is off (bpr_hot_tier_begin)");
+  if (hot_base == nullptr || tot == nullptr)
+    return fail(BPR_ERR_INVALID, "bpr_hot_exchange: NULL buffer");
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  if (int rc = flush_deferred_stats(c)) return rc;  // a cut launch that was not followed by bpr_sync_cut
+  items_moved(c);  // (moves only hot item rows, no bias)
+  HotStepArgs a;
+  memset(&a, 0, sizeof(a));
+  a.Q = c->Q; a.delta = c->hot_delta; a.hot_items = c->hot_items; a.canon = c->hot_canon;
+  a.hb = hot_base; a.tot = tot; a.cold_base = cold_base;
+  a.H = c->hot_H; a.R = c->hot_R; a.d = c->d; a.fold_prev = fold_prev != 0; a.cut = cut != 0;
+  const int64_t n = (int64_t)c->hot_H * c->d;
+  hipLaunchKernelGGL(k_hot_step, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0,
+                     c->stream, a);
+  BPR_HIP_CHECK(hipGetLastError());
+  if (cut) hot_block_cut(c);  // the block is zero again: the next launch may take the LDS tier
+  return BPR_OK;
+}
+
+int bpr_set_heavy_users(bpr_ctx* c, int32_t threshold, int64_t max_bytes) {
+  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_set_heavy_users: ctx is NULL");
+  if (threshold < -1 || max_bytes < 0)
+    return fail(BPR_ERR_INVALID, "bpr_set_heavy_users: threshold >= -1, max_bytes >= 0");
+  c->heavy_T_opt = threshold;
+  if (max_bytes > 0) c->heavy_max_bytes = max_bytes;
+  c->heavy_for = nullptr;  // rebuilt by the next sampling STREAM launch
+  return BPR_OK;
+}
+
+int bpr_heavy_users(bpr_ctx* c, int64_t* n, int32_t* threshold) {
+  if (c == nullptr || n == nullptr || threshold == nullptr)
+    return fail(BPR_ERR_INVALID, "bpr_heavy_users: NULL argument");
+  const bool built = c->heavy_for != nullptr && c->heavy_for == c->indptr;
+  *n = built ? c->heavy_n : 0;
+  *threshold = built ? c->heavy_T : c->heavy_T_opt;
+  return BPR_OK;
+}
+
+}  // extern "C"

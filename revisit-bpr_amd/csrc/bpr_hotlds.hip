@@ -1,7 +1,7 @@
 // bpr_hotlds.hip — the LDS tier of k_stream's hot block (r6): the instantiations k_stream<..., LDSHOT = true>
 // (bpr_kernels.h: one workgroup of up to 1,024 threads per CU, a private fp32 delta block for the most popular
 // item rows in LDS, flushed into the global delta block at exit) and their launcher, in a translation unit of
-// their own so that they compile beside bprcore.hip.  Reference: the rows concerned are the ones the adaptive
+// their own so that they compile beside bpr_stream_launch.hip.  Reference: the rows concerned are the ones the adaptive
 // sampler of revisit_bpr/modules/neg_samplers.py:84-121 concentrates on once the model has moved.
 #include <hip/hip_runtime.h>
 

@@ -13,7 +13,8 @@
 #include <type_traits>
 #include <vector>
 
-#include "bpr_ctx.h"
+#include "bpr_ctx_state.h"
+#include "bpr_host.h"
 #include "bpr_refresh_plan.h"
 #include "bpr_sort.h"
 
@@ -160,7 +161,7 @@ void refresh_free(bpr_ctx* c) {
   hipFree(c->ids_in);
   hipFree(c->seg_offsets);
   c->sig_acc = nullptr;
-  c->keys_cut = false;
+  items_moved(c);  // (the key buffers are gone)
   hipFree(c->sort_tmp);
   c->order = nullptr;
   c->sigma = nullptr;
@@ -169,7 +170,7 @@ void refresh_free(bpr_ctx* c) {
   c->sort_tmp = nullptr;
   c->sort_tmp_bytes = 0;
   c->have_snapshot = false;
-  c->refresh_pending = false;
+  split_refresh_done(c);
   c->part_pending = false;
 }
 
@@ -240,7 +241,7 @@ static void snapshot_to_front(bpr_ctx* c, int back, bool keep_meta) {
   c->sigma = c->sigma_buf[back];
   c->meta_front = keep_meta && c->snap_partial[back] ? c->snap_meta[back] : nullptr;
   c->keys_front = c->snap_keys[back];
-  c->keys_front_stale = false;
+  front_replaced(c);
   c->have_snapshot = true;
 }
 
@@ -281,11 +282,9 @@ static int refresh_cut(bpr_ctx* c, bool split, RefreshJob* j, bool* event_on_cut
     // the keys were cut on the side stream (bpr_train_stream_acut) and this sort runs on the launch
     // stream: order it behind that cut (the split sort waits for ev_keys on the side stream anyway)
     BPR_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_keys, 0));
-    c->acut_pending = false;
+    acut_waited(c);
   }
-  c->keys_cut = false;
-  c->keys_event = false;
-  c->keys_on_side = false;
+  keys_consumed(c);
   j->keysT = c->keysT + (int64_t)j->f_lo * I;
   j->sig_acc = c->sig_acc + 2 * j->f_lo;
   c->keys_w ^= 1;
@@ -377,7 +376,7 @@ int refresh_impl(bpr_ctx* c, bool split, int f_lo, int f_hi) {
     c->part_pending = true;
   } else if (split) {
     BPR_HIP_CHECK(hipEventRecord(c->ev_sorted, c->side));
-    c->refresh_pending = true;
+    split_refresh_queued(c);
   } else {
     snapshot_to_front(c, j.back, true);
   }
@@ -424,10 +423,9 @@ int refresh_commit_impl(bpr_ctx* c) {
   }
   BPR_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_sorted, 0));
   snapshot_to_front(c, back_snapshot(c), true);
-  c->refresh_pending = false;
+  split_refresh_done(c);
   return BPR_OK;
 }
-
 
 // What the last completed refresh ran (bpr_adaptive_refresh_info): the plan's figures as refresh_impl recorded them,
 // and the columns the split binned sort flagged, read back from its meta — memset to 0 before the launch; a
@@ -453,3 +451,117 @@ int refresh_info_impl(bpr_ctx* c, int32_t* info_host) {
 }
 
 }  // namespace bpr
+
+using namespace bpr;
+extern "C" {
+
+int bpr_adaptive_refresh(bpr_ctx* c) {
+  if (int rc = check_bound(c, "bpr_adaptive_refresh")) return rc;
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  if (c->vs_active)  // batched STREAM: the snapshot must see the item rows as of "now"
+    if (int rc = vs_flush(c, false, true)) return rc;
+  const int world = comm_world(c);
+  if (world > 1 && c->d % world == 0 && !c->refresh_pending) {
+    // several ranks behind one communicator: every rank sorts its share of the factors of its own
+    // replica, an all-gather hands everybody every factor's order, the same snapshot is published
+    const int per = c->d / world, r = comm_rank(c);
+    if (int rc = refresh_impl(c, false, r * per, (r + 1) * per)) return rc;
+    const int back = c->have_snapshot ? (c->snap_front ^ 1) : c->snap_front;
+    if (int rc = comm_gather_snapshot(c, c->order_alloc[back] + BPR_ORDER_PAD, c->sigma_buf[back], per))
+      return rc;
+    return refresh_publish_impl(c);
+  }
+  return refresh_impl(c, false, 0, c->d);
+}
+
+int bpr_adaptive_refresh_begin(bpr_ctx* c) {
+  if (int rc = check_bound(c, "bpr_adaptive_refresh_begin", c == nullptr || !c->keys_cut)) return rc;
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  if (c->vs_active)
+    if (int rc = vs_flush(c, false, true)) return rc;
+  return refresh_impl(c, true, 0, c->d);
+}
+
+int bpr_adaptive_refresh_commit(bpr_ctx* c) {
+  if (int rc = check_bound(c, "bpr_adaptive_refresh_commit", false)) return rc;
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  return refresh_commit_impl(c);
+}
+
+int bpr_adaptive_refresh_part(bpr_ctx* c, int32_t f_lo, int32_t f_hi) {
+  if (int rc = check_bound(c, "bpr_adaptive_refresh_part")) return rc;
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  if (c->vs_active)
+    if (int rc = vs_flush(c, false, true)) return rc;
+  return refresh_impl(c, false, f_lo, f_hi);
+}
+
+int bpr_adaptive_refresh_publish(bpr_ctx* c) {
+  if (int rc = check_bound(c, "bpr_adaptive_refresh_publish")) return rc;
+  return refresh_publish_impl(c);
+}
+
+int bpr_adaptive_snapshot_ptrs(bpr_ctx* c, int32_t back, void** order_host, void** sigma_host) {
+  if (int rc = check_bound(c, "bpr_adaptive_snapshot_ptrs")) return rc;
+  if (order_host == nullptr || sigma_host == nullptr)
+    return fail(BPR_ERR_INVALID, "bpr_adaptive_snapshot_ptrs: NULL argument");
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  if (int rc = refresh_alloc(c)) return rc;
+  if (!back)
+    if (int rc = snapshot_complete_impl(c)) return rc;
+  const int front = c->snap_front;
+  const int which = back ? (c->have_snapshot ? front ^ 1 : front) : front;
+  *order_host = (void*)(c->order_alloc[which] + BPR_ORDER_PAD);
+  *sigma_host = (void*)c->sigma_buf[which];
+  return BPR_OK;
+}
+
+int bpr_adaptive_snapshot_partial(bpr_ctx* c, int32_t* partial_host) {
+  if (c == nullptr || partial_host == nullptr)
+    return fail(BPR_ERR_INVALID, "bpr_adaptive_snapshot_partial: NULL argument");
+  *partial_host = (c->have_snapshot && c->meta_front != nullptr) ? 1 : 0;
+  return BPR_OK;
+}
+
+int bpr_adaptive_refresh_info(bpr_ctx* c, int32_t* info_host) {
+  if (int rc = check_bound(c, "bpr_adaptive_refresh_info")) return rc;
+  if (info_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_adaptive_refresh_info: info_host is NULL");
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  return refresh_info_impl(c, info_host);
+}
+
+int bpr_adaptive_refresh_pending(bpr_ctx* c, int32_t* pending_host) {
+  if (c == nullptr || pending_host == nullptr)
+    return fail(BPR_ERR_INVALID, "bpr_adaptive_refresh_pending: NULL argument");
+  *pending_host = c->refresh_pending ? 1 : 0;
+  return BPR_OK;
+}
+
+int bpr_set_side_stream(bpr_ctx* c, void* hip_stream) {
+  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_set_side_stream: ctx is NULL");
+  if (c->refresh_pending)
+    return fail(BPR_ERR_INVALID, "bpr_set_side_stream: a split refresh is pending");
+  BPR_HIP_CHECK(hipSetDevice(c->device));
+  if (c->side != nullptr) {
+    BPR_HIP_CHECK(hipStreamSynchronize(c->side));
+    if (c->side_owned) hipStreamDestroy(c->side);
+  }
+  c->side = (hipStream_t)hip_stream;
+  c->side_owned = false;
+  return BPR_OK;
+}
+
+int bpr_adaptive_get_snapshot(bpr_ctx* c, int32_t* order_out, float* sigma_out) {
+  if (int rc = check_bound(c, "bpr_adaptive_get_snapshot")) return rc;
+  if (!c->have_snapshot) return fail(BPR_ERR_INVALID, "bpr_adaptive_get_snapshot: no snapshot");
+  if (int rc = snapshot_complete_impl(c)) return rc;
+  if (order_out)
+    BPR_HIP_CHECK(hipMemcpyAsync(order_out, c->order, sizeof(int32_t) * (size_t)c->d * c->I,
+                                 hipMemcpyDeviceToDevice, c->stream));
+  if (sigma_out)
+    BPR_HIP_CHECK(hipMemcpyAsync(sigma_out, c->sigma, sizeof(float) * c->d,
+                                 hipMemcpyDeviceToDevice, c->stream));
+  return BPR_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // bpr_stream.h — k_stream, THE hot kernel of libbprcore (STREAM mode), and what it needs; a header of its own
-// because several translation units instantiate it (bprcore.hip: the plain kernel; bpr_hotlds.hip: the LDS tier of
+// because several translation units instantiate it (bpr_stream_launch.hip: the plain kernel; bpr_hotlds.hip: the LDS tier of
 // the hot block; bpr_dynamic.hip: dynamic negatives; bpr_warp.hip: the WARP objective).  See bpr_kernels.h for the
 // kernels around it and DESIGN.md §4.1 for its roofline.
 #pragma once
@@ -587,7 +587,7 @@ void k_stream(const StreamArgs a) {
 }
 
 // ---- which plain k_stream (the LDSHOT ones: bpr_hotlds.hip) a launch of sampler SMP runs at width d, for a "seen?"
-// structure; the translation unit that calls this holds the instantiations (bprcore.hip, bpr_dynamic.hip, bpr_warp.hip)
+// structure; the translation unit that calls this holds the instantiations (bpr_stream_launch.hip, bpr_dynamic.hip, bpr_warp.hip)
 using StreamKernelFn = void (*)(const StreamArgs);
 template <int G, int E, int SMP, int SN>
 StreamKernelFn stream_kernel_of(bool full, bool part) {

@@ -1,7 +1,7 @@
 // bpr_stream_plan.h — how a STREAM launch (k_stream, bpr_stream.h) is laid out: which kernel, which "seen?"
 // structure, block, grid, dynamic LDS, run length and — for the LDS tier — rows and tail zones.  Integer arithmetic
 // on the shape and the tuning knobs only: no HIP, no bpr_ctx (plain C++17; tests/test_stream_plan_cpu.py pins it
-// on the CPU).  launch_stream (bprcore.hip) fills a StreamShape, supplies the occupancy between the two steps and
+// on the CPU).  launch_stream (bpr_stream_launch.hip) fills a StreamShape, supplies the occupancy between the two steps and
 // launches what the StreamPlan says.
 #pragma once
 #include <stddef.h>

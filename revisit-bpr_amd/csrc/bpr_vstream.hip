@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <string>
 
+#include "bpr_ctx_state.h"
 #include "bpr_host.h"
 #include "bpr_scored_plan.h"
 #include "bpr_vstream.h"
@@ -115,7 +116,7 @@ static int vs_enter(bpr_ctx* c) {
 }
 
 int vs_flush(bpr_ctx* c, bool users, bool items) {
-  c->bias_w_valid = false;  // (the batched path writes the item_bias)
+  bias_moved(c);  // (the batched path writes the item_bias)
   if (!c->vs_active) return BPR_OK;
   const bool stateful = c->opt_kind != BPR_OPT_SGD;
   if (stateful)
@@ -159,7 +160,7 @@ int vs_flush(bpr_ctx* c, bool users, bool items) {
 
 // headers -> lastP / lastQ: everything applied, every row current as of c->step
 int vs_leave(bpr_ctx* c) {
-  if (c->vs_active) c->bias_w_valid = false;
+  if (c->vs_active) bias_moved(c);
   if (!c->vs_active) return BPR_OK;
   if (int rc = vs_flush(c, true, true)) return rc;
   if (c->lastP != nullptr) {
@@ -249,7 +250,7 @@ static int train_stream_batched_impl(bpr_ctx* c, const char* who, const int32_t*
                                      int32_t* neg, int32_t* tries, int64_t n, int64_t B, int32_t sampler,
                                      float adaptive_p, uint64_t seed, uint64_t offset, int64_t max_inflight,
                                      float* out_scalars) {
-  if (c != nullptr) c->keys_cut = false;
+  if (c != nullptr) items_moved(c);  // (the bias: vs_flush says so)
   if (int rc = check_triples(c, who, users, pos, n)) return rc;
   if (int rc = check_sampler(c, who, sampler, adaptive_p, neg, n)) return rc;
   if (B < 1) return fail(BPR_ERR_INVALID, std::string(who) + ": B must be >= 1");

@@ -9,7 +9,7 @@
 
 namespace bpr {
 
-// ---- the fused path: which k_stream a STREAM launch with BPR_NEG_WARP runs (launch_stream, bprcore.hip) ---------
+// ---- the fused path: which k_stream a STREAM launch with BPR_NEG_WARP runs (launch_stream, bpr_stream_launch.hip)----
 int stream_kernel_warp(const bpr_ctx* c, int seen, StreamKernelFn* out) {
   return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
     using T = decltype(tag);

@@ -1,25 +1,23 @@
-// bprcore.hip — C ABI of libbprcore.so (declared in include/bprcore.h) and kernel dispatch.
+// bprcore.hip — what is left of the C ABI of libbprcore.so (include/bprcore.h) once every subsystem has its own file:
+// the error string, the argument checks every entry point shares, the device view of the optimizer, the life of a ctx
+// and what is bound to or set on it, the epoch planner's entry points (bpr_plan.hip does the work), the step counters,
+// timing, stream handles and the two plan test hooks.  It launches no kernel.  The STRICT path: bpr_strict.hip; the
+// STREAM launch, bpr_sync_cut and the stand-alone samplers: bpr_stream_launch.hip; the snapshot: bpr_refresh.hip; the
+// hot tier: bpr_hot.hip.  The flags that make two consecutive calls correct: bpr_ctx_state.h.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
-#include <algorithm>
 #include <string>
-#include <type_traits>
 
-#include "bpr_ctx.h"
-#include "bpr_kernels.h"
+#include "bpr_ctx_state.h"
 #include "bpr_host.h"
 #include "bpr_stream_plan.h"
 #include "bpr_refresh_plan.h"
+#include "bpr_scored_plan.h"
 #include "bpr_group_shape.h"
 #include "bpr_opt_plan.h"
 
 namespace bpr {
-static_assert(ORDER_PAD == BPR_ORDER_PAD, "walk vector width vs snapshot padding");
-static_assert(SEEN_CSR == STREAM_SEEN_CSR && SEEN_BITMAP == STREAM_SEEN_BITMAP && SEEN_LIST == STREAM_SEEN_LIST &&
-                  NEG_GIVEN == BPR_NEG_GIVEN && NEG_DYNAMIC == BPR_NEG_DYNAMIC && NEG_WARP == BPR_NEG_WARP,
-              "the launch plan names the kernels' template arguments");
 
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
@@ -29,146 +27,14 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-static int max_blocks() {
-  static int v = [] {
-    const char* e = getenv("BPR_MAX_BLOCKS");
-    int n = e ? atoi(e) : 0;
-    return n > 0 ? n : 256 * 8;  // 256 CUs x 8 resident 256-thread blocks
-  }();
-  return v;
-}
-// STREAM grids (bpr_stream_plan.h): BPR_MAX_BLOCKS caps them (experiments).
-static int64_t stream_grid_cap() {
-  static const bool forced = getenv("BPR_MAX_BLOCKS") != nullptr;
-  return forced ? (int64_t)max_blocks() : STREAM_MAX_GRID;
-}
-
-// grid for n groups of G lanes, 256-thread blocks, capped (grid-stride inside the kernels)
-static unsigned grid_for(int64_t n_groups, int G, int64_t cap_groups) {
-  if (cap_groups > 0 && n_groups > cap_groups) n_groups = cap_groups;
-  const int64_t per_block = 256 / G;
-  int64_t blocks = (n_groups + per_block - 1) / per_block;
-  if (blocks > max_blocks()) blocks = max_blocks();
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
-}
-
-int check_bound(const bpr_ctx* c, const char* who, bool whole_table) {
+int check_bound(bpr_ctx* c, const char* who, bool whole_table) {
   if (c == nullptr) return fail(BPR_ERR_INVALID, std::string(who) + ": ctx is NULL");
   if (c->P == nullptr || c->Q == nullptr)
     return fail(BPR_ERR_INVALID, std::string(who) + ": tables not bound (bpr_bind_tables)");
   // every entry point sees the item table whole — but bpr_train_stream_acut itself and the calls of
   // its pipeline that never look at the table (commit; begin when the keys are already cut)
-  if (whole_table && c->hot_unfolded && !c->acut_call) return hot_fold_impl(const_cast<bpr_ctx*>(c));
+  if (whole_table && c->hot_unfolded) return hot_fold_impl(c);
   return BPR_OK;
-}
-
-// k_stream_epilogue: the sum of a launch's loss partials (out != NULL), the fold of the hot block into Q and the
-// write-back of the wide item_bias, each if asked for.  `stop`: an event that rides on the kernel's own completion.
-static int stream_epilogue(bpr_ctx* c, const float* partials, int n_blocks, float* out, bool fold, bool with_bias,
-                           hipEvent_t stop) {
-  EpilogueArgs ea;
-  memset(&ea, 0, sizeof(ea));
-  ea.partials = partials; ea.n_blocks = n_blocks; ea.out = out;
-  ea.Q = c->Q; ea.delta = c->hot_delta; ea.hot_items = c->hot_items;
-  ea.H = fold ? c->hot_H : 0; ea.R = c->hot_R; ea.d = c->d;
-  ea.fold_blocks = fold ? (int)std::min<int64_t>(((int64_t)c->hot_H * c->d + 255) / 256, 64) : 0;
-  if (with_bias) {
-    ea.bias_w = c->bias_w; ea.bias = c->bias; ea.I = (int32_t)c->I;
-    ea.bias_blocks = (int)std::min<int64_t>((c->I + 255) / 256, 256);
-  }
-  const dim3 grid(1 + ea.fold_blocks + ea.bias_blocks);
-  if (stop != nullptr)
-    hipExtLaunchKernelGGL(k_stream_epilogue, grid, dim3(256), 0, c->stream, nullptr, stop, 0, ea);
-  else
-    hipLaunchKernelGGL(k_stream_epilogue, grid, dim3(256), 0, c->stream, ea);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
-// Fold the hot deltas an asynchronous cut left in the block (after that cut has read them).
-int hot_fold_impl(bpr_ctx* c) {
-  if (!c->hot_unfolded) return BPR_OK;
-  c->hot_unfolded = false;
-  if (c->hot_H <= 0) return BPR_OK;
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (c->ev_keys != nullptr) BPR_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_keys, 0));
-  c->acut_pending = false;
-  if (int rc = stream_epilogue(c, nullptr, 0, nullptr, true, false, nullptr)) return rc;
-  return BPR_OK;  // (Q + delta is what it was: keys cut from it stay valid)
-}
-
-// bpr_train_stream_cut under the hot tier leaves its loss partials to the bpr_sync_cut that should
-// follow.  Whoever comes first instead — the next launch (it overwrites the partials), a hot exchange
-// of the three-call protocol (bpr_hot_exchange / bpr_hot_sync), the end of the tier — sums them now.
-int flush_deferred_stats(bpr_ctx* c) {
-  if (!c->defer_pending) return BPR_OK;
-  c->defer_pending = false;
-  float* out = c->defer_out;
-  c->defer_out = nullptr;
-  if (out == nullptr || c->defer_blocks <= 0) return BPR_OK;
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->dev_scalars, c->defer_blocks, out);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
-static int ensure_strict_scratch(bpr_ctx* c) {
-  if (c->GP != nullptr) return BPR_OK;
-  const size_t nP = (size_t)c->U * c->d, nQ = (size_t)c->I * c->d;
-  BPR_HIP_CHECK(hipMalloc(&c->GP, sizeof(float) * nP));
-  BPR_HIP_CHECK(hipMalloc(&c->GQ, sizeof(float) * nQ));
-  BPR_HIP_CHECK(hipMalloc(&c->Gb, sizeof(float) * c->I));
-  BPR_HIP_CHECK(hipMalloc(&c->flagP, sizeof(int32_t) * c->U));
-  BPR_HIP_CHECK(hipMalloc(&c->flagQ, sizeof(int32_t) * c->I));
-  BPR_HIP_CHECK(hipMalloc(&c->lastP, sizeof(int32_t) * c->U));
-  BPR_HIP_CHECK(hipMalloc(&c->lastQ, sizeof(int32_t) * c->I));
-  BPR_HIP_CHECK(hipMalloc(&c->touched, sizeof(uint32_t) * (size_t)(c->U + c->I)));
-  BPR_HIP_CHECK(hipMalloc(&c->touched_cnt, 2 * sizeof(uint32_t)));
-  BPR_HIP_CHECK(hipMemsetAsync(c->GP, 0, sizeof(float) * nP, c->stream));
-  BPR_HIP_CHECK(hipMemsetAsync(c->GQ, 0, sizeof(float) * nQ, c->stream));
-  BPR_HIP_CHECK(hipMemsetAsync(c->Gb, 0, sizeof(float) * c->I, c->stream));
-  BPR_HIP_CHECK(hipMemsetAsync(c->flagP, 0, sizeof(int32_t) * c->U, c->stream));
-  BPR_HIP_CHECK(hipMemsetAsync(c->flagQ, 0, sizeof(int32_t) * c->I, c->stream));
-  // rows are current as of the step counter (0, or a resumed checkpoint's: bpr_set_step)
-  BPR_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)c->lastP, (int)c->step, (size_t)c->U, c->stream));
-  BPR_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)c->lastQ, (int)c->step, (size_t)c->I, c->stream));
-  BPR_HIP_CHECK(hipMemsetAsync(c->touched_cnt, 0, 2 * sizeof(uint32_t), c->stream));
-  c->cnt_sel = 0;
-  c->pending = 0;
-  return BPR_OK;
-}
-
-static void free_strict_scratch(bpr_ctx* c) {
-  hipFree(c->GP); hipFree(c->GQ); hipFree(c->Gb);
-  hipFree(c->flagP); hipFree(c->flagQ); hipFree(c->lastP); hipFree(c->lastQ);
-  hipFree(c->touched); hipFree(c->touched_cnt);
-  c->GP = c->GQ = c->Gb = nullptr;
-  c->flagP = c->flagQ = c->lastP = c->lastQ = nullptr;
-  c->touched = c->touched_cnt = nullptr;
-  c->pending = 0;
-}
-
-
-static TripleArgs triple_args(const bpr_ctx* c) {
-  TripleArgs a;
-  memset(&a, 0, sizeof(a));
-  a.P = c->P; a.Q = c->Q; a.bias = c->bias;
-  a.I = c->I; a.d = c->d;
-  a.pad_user = c->pad_user; a.pad_item = c->pad_item;
-  a.au = c->au; a.ai = c->ai; a.an = c->an;
-  a.GP = c->GP; a.GQ = c->GQ; a.Gb = c->Gb;
-  a.flagP = c->flagP; a.flagQ = c->flagQ;
-  a.touched = c->touched; a.touched_cnt = c->touched_cnt + c->cnt_sel;
-  a.partials = c->dev_scalars;
-  a.acc_partials = c->defer_stats ? 1 : 0;
-  a.mP = c->mP; a.vP = c->vP; a.mQ = c->mQ; a.vQ = c->vQ; a.mb = c->mb; a.vb = c->vb;
-  // (Adagrad: no zero-gradient motion to read rows through — the kernel skips the block, as for SGD)
-  if (opt_kind_lazy(c->opt_kind)) {
-    a.lastP = c->lastP; a.lastQ = c->lastQ;
-  }
-  a.o = opt_dev(c, c->step + 1);
-  return a;
 }
 
 OptDev opt_dev(const bpr_ctx* c, int64_t t) {
@@ -217,22 +83,6 @@ OptDev opt_dev(const bpr_ctx* c, int64_t t) {
   return o;
 }
 
-static ApplyArgs apply_args(const bpr_ctx* c, int64_t t) {
-  ApplyArgs a;
-  memset(&a, 0, sizeof(a));
-  a.P = c->P; a.Q = c->Q; a.bias = c->bias;
-  a.GP = c->GP; a.GQ = c->GQ; a.Gb = c->Gb;
-  a.mP = c->mP; a.vP = c->vP; a.mQ = c->mQ; a.vQ = c->vQ; a.mb = c->mb; a.vb = c->vb;
-  a.lastP = c->lastP; a.lastQ = c->lastQ;
-  a.flagP = c->flagP; a.flagQ = c->flagQ;
-  a.touched = c->touched; a.touched_cnt = c->touched_cnt + c->cnt_sel;
-  a.next_cnt = c->touched_cnt + (c->cnt_sel ^ 1);
-  a.U = c->U; a.I = c->I; a.d = c->d;
-  a.pad_user = c->pad_user; a.pad_item = c->pad_item;
-  a.o = opt_dev(c, t);
-  return a;
-}
-
 int check_opt_state(const bpr_ctx* c, const char* who) {
   const bool need_m = c->opt_kind == BPR_OPT_MOMENTUM || c->opt_kind == BPR_OPT_ADAM ||
                       (c->opt_kind == BPR_OPT_RMSPROP && c->opt.momentum > 0.f);
@@ -258,274 +108,12 @@ static int drain_timing(bpr_ctx* c) {
   return BPR_OK;
 }
 
-// ---- launches ---------------------------------------------------------------------------------
-template <int MODE>
-static int launch_triples(bpr_ctx* c, TripleArgs a, bool timed) {
-  if (a.n <= 0) return BPR_OK;
-  return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
-    using T = decltype(tag);
-    constexpr int G = T::G, E = T::E;
-    const unsigned grid = grid_for(a.n, G, 0);
-    Timer tm(c, timed);
-    (void)tm;
-    hipLaunchKernelGGL((k_triples<G, E, MODE>), dim3(grid), dim3(256), 0, c->stream, a);
-    if (a.scalars != nullptr)
-      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, a.partials, (int)grid,
-                         a.scalars);
-    BPR_HIP_CHECK(hipGetLastError());
-    return BPR_OK;
-  });
-}
-
-// CUs the ctx's launch stream may use: the popcount of its CU mask (bpr_stream_create), the whole
-// chip for an unmasked stream.  Queried once per stream handle.
-static int stream_cus(bpr_ctx* c) {
-  if (c->stream_cus_of == (void*)c->stream && c->stream_cus > 0) return c->stream_cus;
-  int n_cu = 0;
-  hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-  int cus = n_cu;
-  if (c->stream != nullptr) {
-    uint32_t mask[16] = {0};
-    if (hipExtStreamGetCUMask(c->stream, 16, mask) == hipSuccess) {
-      int bits = 0;
-      for (int w = 0; w < 16; ++w) bits += __builtin_popcount(mask[w]);
-      if (bits > 0 && bits < n_cu) cus = bits;
-    } else {
-      (void)hipGetLastError();
-    }
-  }
-  c->stream_cus = cus > 0 ? cus : 256;
-  c->stream_cus_of = (void*)c->stream;
-  return c->stream_cus;
-}
-
-// ---- STREAM ------------------------------------------------------------------------------------
-// the plain k_stream instantiation for the ctx's shape (the LDSHOT ones: bpr_hotlds.hip)
-static int stream_kernel(const bpr_ctx* c, int sampler, int seen, bool part, StreamKernelFn* out) {
-  if (sampler == NEG_DYNAMIC) return stream_kernel_dynamic(c, seen, out);  // (bpr_dynamic.hip)
-  if (sampler == NEG_WARP) return stream_kernel_warp(c, seen, out);        // (bpr_warp.hip)
-  return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
-    using T = decltype(tag);
-    constexpr int G = T::G, E = T::E;
-    *out = sampler == NEG_GIVEN     ? stream_kernel_of<G, E, NEG_GIVEN, SEEN_CSR>(c->d == G * E, false)
-           : sampler == NEG_UNIFORM ? stream_kernel_seen<G, E, NEG_UNIFORM>(seen, c->d)
-                                    : stream_kernel_seen<G, E, NEG_ADAPTIVE>(seen, c->d, part);
-    return BPR_OK;
-  });
-}
-
-// blocks of the plan's plain kernel a CU holds at once (asked of the instantiation for a snapshot sorted whole),
-// cached per (d, sampler, seen, block, shmem) until the next bpr_set_tuning
-static int stream_occupancy(bpr_ctx* c, int sampler, const StreamPlan& p, int* occ) {
-  const auto key = std::make_tuple(c->d, sampler, p.seen, (int)p.block, (int64_t)p.shmem);
-  const auto it = c->stream_occ.find(key);
-  if (it != c->stream_occ.end()) {
-    *occ = it->second;
-    return BPR_OK;
-  }
-  StreamKernelFn k = nullptr;
-  if (int rc = stream_kernel(c, sampler, p.seen, false, &k)) return rc;
-  *occ = 0;
-  hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, k, (int)p.block, p.shmem);
-  if (*occ < 1) {
-    (void)hipGetLastError();
-    *occ = 1;
-  }
-  c->stream_occ[key] = *occ;
-  return BPR_OK;
-}
-
-// k_stream_epilogue_cut / k_sync_cut: the cut of the next snapshot's keys (Q + the hot block, transposed into
-// c->keysT) with the sum of the loss partials; fold: the hot block is folded into Q on the way; hot = false: the
-// keys are Q alone
-static EpilogueCutArgs cut_args(const bpr_ctx* c, const float* partials, int n_blocks, float* out, bool hot, bool fold,
-                                bool with_bias) {
-  EpilogueCutArgs ea;
-  memset(&ea, 0, sizeof(ea));
-  ea.partials = partials; ea.n_blocks = n_blocks; ea.out = out;
-  ea.Q = c->Q; ea.T = c->keysT; ea.sig_acc = c->sig_acc; ea.d = c->d; ea.I = (int32_t)c->I;
-  if (hot) { ea.delta = c->hot_delta; ea.hot_slot = c->hot_slot; ea.H = c->hot_H; ea.R = c->hot_R; }
-  ea.fold = fold ? 1 : 0;
-  if (with_bias) { ea.bias_w = c->bias_w; ea.bias = c->bias; }
-  return ea;
-}
-static dim3 cut_grid(const bpr_ctx* c) { return dim3((unsigned)((c->I + 31) / 32), (unsigned)((c->d + 31) / 32) + 1u); }
-
-static int ensure_cut_events(bpr_ctx* c) {
-  if (c->ev_keys != nullptr) return BPR_OK;
-  BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_keys, hipEventDisableTiming));
-  BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_sorted, hipEventDisableTiming));
-  return BPR_OK;
-}
-
-// c->keysT holds the next snapshot's keys: the next bpr_adaptive_refresh_begin only queues the sort.  by_event:
-// ev_keys rides on the cut kernel; on_side: the cut runs on c->side — whoever sorts these keys on the launch stream
-// waits for ev_keys, and so does a launch outside the acut pipeline (the cut reads Q and that launch's partials)
-static void mark_keys_cut(bpr_ctx* c, bool by_event, bool on_side) {
-  c->keys_cut = true;
-  if (c->meta_front != nullptr && c->keysT == c->keys_front) c->keys_front_stale = true;
-  c->keys_event = by_event;
-  if (on_side) c->keys_on_side = c->acut_pending = true;
-}
-
-// One STREAM launch: one group per run of run_len triples; max_inflight (cap_groups) caps the number of groups
-// (= triples in flight).  The layout of the launch is decided in bpr_stream_plan.h.
-static int launch_stream(bpr_ctx* c, StreamArgs a, int sampler, int64_t cap_groups,
-                         float* out_scalars, bool cut, bool acut = false) {
-  if (a.n <= 0) return BPR_OK;
-  if (cut)
-    if (int rc = refresh_alloc(c)) return rc;
-  if (int rc = flush_deferred_stats(c)) return rc;  // (this launch overwrites the partials)
-  if (c->acut_pending && !acut) {
-    // the asynchronous cut of the previous launch still reads that launch's partials (and Q + the hot
-    // deltas) on the side stream: a launch outside the acut pipeline reuses the first set of partials
-    // and folds / moves the rows, so it waits for that cut
-    BPR_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_keys, 0));
-    c->acut_pending = false;
-  }
-  const bool hot = a.hot_slot != nullptr;
-  const bool part = a.snap_meta != nullptr;               // a partial snapshot in front
-  const bool acut_fold = acut && c->tune_acut_fold != 0;  // r6: the asynchronous cut with the fold kept on this stream
-
-  // ---- plan
-  StreamShape s = {};
-  s.n = a.n; s.I = c->I; s.d = c->d; s.G = c->G; s.E = c->E;
-  s.sampler = sampler; s.cap_groups = cap_groups; s.run_len = a.run_len; s.force_seen = c->tune_seen;
-  s.cus = stream_cus(c); s.grid_cap = stream_grid_cap();
-  s.hot = hot; s.hot_H = c->hot_H;
-  s.tune_hot_lds = c->tune_hot_lds; s.tune_hot_lds_force = c->tune_hot_lds_force != 0;
-  s.tune_lds_block = c->tune_lds_block; s.tune_lds_tail = c->tune_lds_tail;
-  // The LDS-tier kernel has FULL instantiations only, reads a snapshot sorted whole, and reads a hot row as Q + its
-  // own LDS delta — which leaves out what the global block holds.  So: not in r4's asynchronous-cut pipeline (the
-  // deltas stay in the block from launch to launch), nor under the hot tier while the block still holds an earlier
-  // launch's deltas that no bpr_hot_exchange with cut = 1 / bpr_sync_cut has taken out yet (c->hot_uncut).
-  s.lds_allowed = c->hot_code != nullptr && c->d == c->G * c->E && !part && (!acut || acut_fold) &&
-                  !c->hot_unfolded && !c->hot_uncut;
-  StreamPlan p = plan_stream_block(s);
-  int occ = 0;
-  if (int rc = stream_occupancy(c, sampler, p, &occ)) return rc;
-  p = plan_stream(s, p, occ);
-  const bool lds = p.kernel == STREAM_LDS;
-  a.run_len = p.run_len; a.bm_words = p.bm_words; a.gpw_active = p.gpw_active;
-  if (lds) {
-    a.lds_L = p.L; a.tail1 = p.tail1; a.tail2 = p.tail2;
-    a.hot_slot = c->hot_code;
-    a.hot_by_rank = c->hot_by_rank;
-    a.lds_only = c->hot_tier ? 0 : 1;
-  }
-  c->last_run_len = p.run_len;
-  c->last_lds_rows = p.L;
-  StreamKernelFn kernel = nullptr;
-  if (!lds)
-    if (int rc = stream_kernel(c, sampler, p.seen, part, &kernel)) return rc;
-
-  // ---- events, the partials' parity, the wide bias
-  if (cut || acut)
-    if (int rc = ensure_cut_events(c)) return rc;
-  if (acut) {
-    if (c->ev_launch == nullptr) BPR_HIP_CHECK(hipEventCreateWithFlags(&c->ev_launch, hipEventDisableTiming));
-    if (c->side == nullptr) {
-      BPR_HIP_CHECK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-      c->side_owned = true;
-    }
-    if (!acut_fold) {
-      // the launch after next reuses this launch's partials: two sets, used alternately
-      if (a.partials != nullptr) a.partials = c->dev_scalars + (size_t)c->acut_parity * 4 * (STREAM_MAX_GRID + 1);
-      c->acut_parity ^= 1;
-    }
-  }
-  if (a.bias != nullptr) {  // the launch works on the bias with one item per line (bpr_kernels.h)
-    if (c->bias_w_rows != c->I) {
-      hipFree(c->bias_w);
-      c->bias_w = nullptr;
-      c->bias_w_rows = 0;
-      BPR_HIP_CHECK(hipMalloc(&c->bias_w, sizeof(float) * (size_t)c->I * BIAS_LINE));
-      c->bias_w_rows = c->I;
-    }
-    // (re)fill the wide table — unless it is known to equal the dense vector still: the epilogue of
-    // the previous launch wrote it back, and nobody has touched the vector since (every entry point
-    // of the library that writes it says so; writes of the caller's own: bpr_bias_written)
-    if (!(c->bias_track && c->bias_w_valid && c->bias_w_of == c->bias))
-      hipLaunchKernelGGL(k_bias_widen, dim3((unsigned)((c->I + 255) / 256)), dim3(256), 0, c->stream, c->bias,
-                         c->bias_w, (int32_t)c->I);
-    c->bias_w_valid = false;
-    c->bias_w_of = c->bias;
-    a.bias = c->bias_w;
-  }
-  // hot tier + cut: fold, reconciliation passes and snapshot cut are ONE pass, bpr_sync_cut, which the
-  // caller issues next; the launch leaves it its loss partials too
-  const bool defer = cut && hot && c->hot_tier;
-  // the write-back rides on the launch's own epilogue where there is one on this stream
-  const bool bias_in_epilogue = a.bias != nullptr && (!acut || acut_fold) && !defer;
-
-  // ---- launch
-  {
-    Timer tm(c, true);
-    (void)tm;
-    hipEvent_t stop = (acut && !acut_fold) ? c->ev_launch : nullptr;
-    if (lds) {
-      if (int rc = launch_stream_lds(c, a, sampler, p, stop)) return rc;
-    } else {
-      hipExtLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.shmem, c->stream, nullptr, stop, 0, a);
-    }
-  }
-  if (hot && c->hot_tier) c->hot_uncut = true;  // this launch's deltas stay in the block for bpr_hot_exchange
-  if (a.bias != nullptr && !bias_in_epilogue)
-    hipLaunchKernelGGL(k_bias_narrow, dim3((unsigned)((c->I + 255) / 256)), dim3(256), 0, c->stream,
-                       c->bias_w, c->bias, (int32_t)c->I);
-  if (a.bias != nullptr) c->bias_w_valid = true;  // dense == wide again once the write-back has run
-
-  // ---- epilogue
-  const bool fold = hot && !c->hot_tier;  // hot tier: the deltas stay for bpr_hot_exchange
-  if (acut) {
-    // the cut of the next snapshot on the SIDE stream, behind this launch and beside the next one.
-    // r6 (acut_fold): the launch stream keeps only what the NEXT launch needs — the fold of the hot block (+ loss
-    // statistics, + the item_bias write-back): k_stream_epilogue, a few microseconds — and the 2 x I x d x 4-byte
-    // transpose that only the sorter reads goes to the side stream, behind this epilogue (it reads Q while the next
-    // launch updates it: a snapshot cut during the launch instead of before it — a little FRESHER than lag 1, inside
-    // the same budget).  The block is folded after every launch, so the LDS-tier kernel stays valid.
-    // r4: read-only (keys = Q + hot deltas, nothing folded); the cut also sums the loss partials.
-    if (acut_fold)
-      if (int rc = stream_epilogue(c, a.partials, (int)p.grid, out_scalars, fold, bias_in_epilogue, c->ev_launch))
-        return rc;
-    const EpilogueCutArgs ec = acut_fold ? cut_args(c, nullptr, 0, nullptr, false, false, false)
-                                         : cut_args(c, a.partials, (int)p.grid, out_scalars, hot, false, false);
-    BPR_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_launch, 0));
-    hipExtLaunchKernelGGL(k_stream_epilogue_cut, cut_grid(c), dim3(256), 0, c->side, nullptr, c->ev_keys, 0, ec);
-    BPR_HIP_CHECK(hipGetLastError());
-    mark_keys_cut(c, true, true);
-    if (!acut_fold) c->hot_unfolded = hot;
-    return BPR_OK;
-  }
-  if (defer) {
-    c->defer_blocks = (int)p.grid;
-    c->defer_out = out_scalars;
-    c->defer_pending = true;
-  } else if (cut) {
-    // the epilogue also cuts the next snapshot's keys (k_stream_epilogue_cut) — into the key
-    // buffer the split refresh that may still be sorting does NOT read (bpr_ctx.h keysT_buf)
-    const EpilogueCutArgs ec = cut_args(c, a.partials, (int)p.grid, out_scalars, hot, true, bias_in_epilogue);
-    // the split refresh's side stream waits for this cut: the event rides on the kernel's own
-    // completion signal (hipExtLaunchKernelGGL stop event) instead of a marker packet behind it
-    static const bool ride = getenv("BPR_CUT_EVENT") == nullptr || atoi(getenv("BPR_CUT_EVENT")) != 0;
-    if (ride)
-      hipExtLaunchKernelGGL(k_stream_epilogue_cut, cut_grid(c), dim3(256), 0, c->stream, nullptr, c->ev_keys, 0, ec);
-    else
-      hipLaunchKernelGGL(k_stream_epilogue_cut, cut_grid(c), dim3(256), 0, c->stream, ec);
-    mark_keys_cut(c, ride, false);
-  } else if (out_scalars != nullptr || fold || bias_in_epilogue) {
-    return stream_epilogue(c, a.partials, (int)p.grid, out_scalars, fold, bias_in_epilogue, nullptr);
-  }
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
 float inv_log1mp(float p) { return (float)(1.0 / log1p(-(double)p)); }
 
 
-int check_triples(const bpr_ctx* c, const char* who, const int32_t* users,
-                         const int32_t* pos, int64_t B) {
-  if (int rc = check_bound(c, who)) return rc;
+int check_triples(bpr_ctx* c, const char* who, const int32_t* users, const int32_t* pos, int64_t B,
+                  bool whole_table) {
+  if (int rc = check_bound(c, who, whole_table)) return rc;
   if (B < 0 || (B > 0 && (users == nullptr || pos == nullptr)))
     return fail(BPR_ERR_INVALID, std::string(who) + ": bad argument");
   return BPR_OK;
@@ -553,26 +141,6 @@ int check_sampler(const bpr_ctx* c, const char* who, int32_t sampler, float adap
       return fail(BPR_ERR_INVALID, std::string(who) + ": adaptive_p not in (0,1)");
   }
   return BPR_OK;
-}
-
-// STRICT lazy replay: bring every row to step c->step (rows tracked by lastP / lastQ)
-int strict_flush_impl(bpr_ctx* c) {
-  // SGD and Adagrad: a dense zero-gradient step moves nothing — no kernel
-  if (!opt_kind_lazy(c->opt_kind) || c->GP == nullptr || c->step == 0) return BPR_OK;
-  c->bias_w_valid = false;
-  if (int rc = check_opt_state(c, "bpr_flush_lazy")) return rc;
-  // (accumulated gradients of a batch in flight are left alone: the flush only advances w / m / v
-  // and the rows' last-step marks, bpr_apply then finds nothing left to replay)
-  ApplyArgs a = apply_args(c, c->step);
-  return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
-    using T = decltype(tag);
-    hipLaunchKernelGGL((k_flush_lazy<T::G, T::E>), dim3(grid_for(c->U, T::G, 0)), dim3(256), 0,
-                       c->stream, a, 0);
-    hipLaunchKernelGGL((k_flush_lazy<T::G, T::E>), dim3(grid_for(c->I, T::G, 0)), dim3(256), 0,
-                       c->stream, a, 1);
-    BPR_HIP_CHECK(hipGetLastError());
-    return BPR_OK;
-  });
 }
 
 }  // namespace bpr
@@ -654,8 +222,8 @@ int bpr_bind_tables(bpr_ctx* c, float* P, int64_t U, float* Q, int64_t I, int32_
     if (int rc = vs_leave(c)) return rc;  // pending steps belong to the tables bound so far
   }
   c->P = P; c->Q = Q; c->bias = item_bias;
-  c->bias_w_valid = false;
-  c->keys_cut = false;
+  bias_moved(c);
+  items_moved(c);
   c->U = U; c->I = I; c->d = d;
   c->pad_user = pad_user; c->pad_item = pad_item;
   const GroupShape g = group_shape(d);  // (bpr_group_shape.h: G = 32 up to d = 128, else 64)
@@ -715,174 +283,6 @@ int bpr_bind_opt_state(bpr_ctx* c, float* m_P, float* v_P, float* m_Q, float* v_
   return BPR_OK;
 }
 
-// ---- sampling -----------------------------------------------------------------------------------
-static int launch_sample(bpr_ctx* c, int what, SampleArgs a) {
-  if (a.n <= 0) return BPR_OK;
-  return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
-    using T = decltype(tag);
-    constexpr int G = T::G, E = T::E;
-    const unsigned grid = grid_for(a.n, G, 0);
-    // adaptive picks walk hundreds of candidates: an LDS seen-bitmap per group when the block's
-    // bitmaps fit 64 KiB; the uniform sampler tests a handful and searches the CSR directly
-    const int words = (int)(((c->I + 31) / 32 + 3) / 4 * 4);
-    const size_t lds = (size_t)(256 / G) * words * sizeof(uint32_t);
-    const bool no_bm = c->tune_seen == 1;
-    // (one block per CU is plenty for a single batch, so the bitmaps may take most of the 160 KB)
-    constexpr size_t SAMPLE_LDS_MAX = 144 * 1024;
-    const bool bm = what != SAMPLE_UNIFORM && lds <= SAMPLE_LDS_MAX && !no_bm;
-    a.bm_words = bm ? words : 0;
-    if (bm && lds > 64 * 1024) {
-      static bool raised = false;  // per (G, E) instantiation of this lambda
-      if (!raised) {
-        BPR_HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&k_sample<G, E, SAMPLE_ADAPTIVE, true>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)SAMPLE_LDS_MAX));
-        BPR_HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&k_sample<G, E, SAMPLE_PICK, true>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)SAMPLE_LDS_MAX));
-        raised = true;
-      }
-    }
-    if (what == SAMPLE_UNIFORM)
-      hipLaunchKernelGGL((k_sample<G, E, SAMPLE_UNIFORM, false>), dim3(grid), dim3(256), 0,
-                         c->stream, a);
-    else if (what == SAMPLE_ADAPTIVE && bm)
-      hipLaunchKernelGGL((k_sample<G, E, SAMPLE_ADAPTIVE, true>), dim3(grid), dim3(256), lds,
-                         c->stream, a);
-    else if (what == SAMPLE_ADAPTIVE)
-      hipLaunchKernelGGL((k_sample<G, E, SAMPLE_ADAPTIVE, false>), dim3(grid), dim3(256), 0,
-                         c->stream, a);
-    else if (bm)
-      hipLaunchKernelGGL((k_sample<G, E, SAMPLE_PICK, true>), dim3(grid), dim3(256), lds, c->stream,
-                         a);
-    else
-      hipLaunchKernelGGL((k_sample<G, E, SAMPLE_PICK, false>), dim3(grid), dim3(256), 0, c->stream,
-                         a);
-    BPR_HIP_CHECK(hipGetLastError());
-    return BPR_OK;
-  });
-}
-
-static SampleArgs sample_args(const bpr_ctx* c) {
-  SampleArgs a;
-  memset(&a, 0, sizeof(a));
-  (void)snapshot_complete_impl(const_cast<bpr_ctx*>(c));  // the sampler kernels read a snapshot sorted whole
-  a.P = c->P; a.I = c->I; a.d = c->d;
-  a.indptr = c->indptr; a.indices = c->indices;
-  a.order = c->order; a.sigma = c->sigma;
-  a.iw = ItemWeights{c->w_accept, c->w_alias};
-  a.mP = c->mP; a.vP = c->vP; a.lastP = opt_kind_lazy(c->opt_kind) ? c->lastP : nullptr;
-  a.o = opt_dev(c, c->step + 1);
-  return a;
-}
-
-int bpr_sample_uniform(bpr_ctx* c, const int32_t* users, int64_t B, uint64_t seed, uint64_t offset,
-                       int32_t* neg_out) {
-  if (int rc = check_bound(c, "bpr_sample_uniform")) return rc;
-  if (c->indptr == nullptr) return fail(BPR_ERR_INVALID, "bpr_sample_uniform: seen CSR not bound");
-  if (users == nullptr || neg_out == nullptr || B < 0)
-    return fail(BPR_ERR_INVALID, "bpr_sample_uniform: bad argument");
-  SampleArgs a = sample_args(c);
-  a.users = users; a.n = B; a.seed = seed; a.offset = offset; a.neg = neg_out;
-  return launch_sample(c, SAMPLE_UNIFORM, a);
-}
-
-int bpr_adaptive_refresh(bpr_ctx* c) {
-  if (int rc = check_bound(c, "bpr_adaptive_refresh")) return rc;
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (c->vs_active)  // batched STREAM: the snapshot must see the item rows as of "now"
-    if (int rc = vs_flush(c, false, true)) return rc;
-  const int world = comm_world(c);
-  if (world > 1 && c->d % world == 0 && !c->refresh_pending) {
-    // several ranks behind one communicator: every rank sorts its share of the factors of its own
-    // replica, an all-gather hands everybody every factor's order, the same snapshot is published
-    const int per = c->d / world, r = comm_rank(c);
-    if (int rc = refresh_impl(c, false, r * per, (r + 1) * per)) return rc;
-    const int back = c->have_snapshot ? (c->snap_front ^ 1) : c->snap_front;
-    if (int rc = comm_gather_snapshot(c, c->order_alloc[back] + BPR_ORDER_PAD, c->sigma_buf[back], per))
-      return rc;
-    return refresh_publish_impl(c);
-  }
-  return refresh_impl(c, false, 0, c->d);
-}
-
-int bpr_adaptive_refresh_begin(bpr_ctx* c) {
-  if (int rc = check_bound(c, "bpr_adaptive_refresh_begin", c == nullptr || !c->keys_cut)) return rc;
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (c->vs_active)
-    if (int rc = vs_flush(c, false, true)) return rc;
-  return refresh_impl(c, true, 0, c->d);
-}
-
-int bpr_adaptive_refresh_commit(bpr_ctx* c) {
-  if (int rc = check_bound(c, "bpr_adaptive_refresh_commit", false)) return rc;
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  return refresh_commit_impl(c);
-}
-
-int bpr_adaptive_refresh_part(bpr_ctx* c, int32_t f_lo, int32_t f_hi) {
-  if (int rc = check_bound(c, "bpr_adaptive_refresh_part")) return rc;
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (c->vs_active)
-    if (int rc = vs_flush(c, false, true)) return rc;
-  return refresh_impl(c, false, f_lo, f_hi);
-}
-
-int bpr_adaptive_refresh_publish(bpr_ctx* c) {
-  if (int rc = check_bound(c, "bpr_adaptive_refresh_publish")) return rc;
-  return refresh_publish_impl(c);
-}
-
-int bpr_adaptive_snapshot_ptrs(bpr_ctx* c, int32_t back, void** order_host, void** sigma_host) {
-  if (int rc = check_bound(c, "bpr_adaptive_snapshot_ptrs")) return rc;
-  if (order_host == nullptr || sigma_host == nullptr)
-    return fail(BPR_ERR_INVALID, "bpr_adaptive_snapshot_ptrs: NULL argument");
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (int rc = refresh_alloc(c)) return rc;
-  if (!back)
-    if (int rc = snapshot_complete_impl(c)) return rc;
-  const int front = c->snap_front;
-  const int which = back ? (c->have_snapshot ? front ^ 1 : front) : front;
-  *order_host = (void*)(c->order_alloc[which] + BPR_ORDER_PAD);
-  *sigma_host = (void*)c->sigma_buf[which];
-  return BPR_OK;
-}
-
-int bpr_adaptive_snapshot_partial(bpr_ctx* c, int32_t* partial_host) {
-  if (c == nullptr || partial_host == nullptr)
-    return fail(BPR_ERR_INVALID, "bpr_adaptive_snapshot_partial: NULL argument");
-  *partial_host = (c->have_snapshot && c->meta_front != nullptr) ? 1 : 0;
-  return BPR_OK;
-}
-
-int bpr_adaptive_refresh_info(bpr_ctx* c, int32_t* info_host) {
-  if (int rc = check_bound(c, "bpr_adaptive_refresh_info")) return rc;
-  if (info_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_adaptive_refresh_info: info_host is NULL");
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  return refresh_info_impl(c, info_host);
-}
-
-int bpr_adaptive_refresh_pending(bpr_ctx* c, int32_t* pending_host) {
-  if (c == nullptr || pending_host == nullptr)
-    return fail(BPR_ERR_INVALID, "bpr_adaptive_refresh_pending: NULL argument");
-  *pending_host = c->refresh_pending ? 1 : 0;
-  return BPR_OK;
-}
-
-int bpr_set_side_stream(bpr_ctx* c, void* hip_stream) {
-  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_set_side_stream: ctx is NULL");
-  if (c->refresh_pending)
-    return fail(BPR_ERR_INVALID, "bpr_set_side_stream: a split refresh is pending");
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (c->side != nullptr) {
-    BPR_HIP_CHECK(hipStreamSynchronize(c->side));
-    if (c->side_owned) hipStreamDestroy(c->side);
-  }
-  c->side = (hipStream_t)hip_stream;
-  c->side_owned = false;
-  return BPR_OK;
-}
-
 int bpr_stream_create(int device_id, const uint32_t* cu_mask, int32_t mask_words, void** stream_out) {
   if (stream_out == nullptr || mask_words < 0 || (mask_words > 0 && cu_mask == nullptr))
     return fail(BPR_ERR_INVALID, "bpr_stream_create: bad argument");
@@ -900,487 +300,6 @@ int bpr_stream_destroy(void* hip_stream) {
   if (hip_stream == nullptr) return BPR_OK;
   BPR_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
   BPR_HIP_CHECK(hipStreamDestroy((hipStream_t)hip_stream));
-  return BPR_OK;
-}
-
-int bpr_sample_adaptive(bpr_ctx* c, const int32_t* users, int64_t B, float p, uint64_t seed,
-                        uint64_t offset, int32_t* neg_out, int32_t* factor_out,
-                        int32_t* rank_out) {
-  if (int rc = check_bound(c, "bpr_sample_adaptive")) return rc;
-  if (c->indptr == nullptr) return fail(BPR_ERR_INVALID, "bpr_sample_adaptive: seen CSR not bound");
-  if (!c->have_snapshot)
-    return fail(BPR_ERR_INVALID, "bpr_sample_adaptive: call bpr_adaptive_refresh first");
-  if (!(p > 0.f && p < 1.f)) return fail(BPR_ERR_INVALID, "bpr_sample_adaptive: p not in (0,1)");
-  if (users == nullptr || neg_out == nullptr || B < 0)
-    return fail(BPR_ERR_INVALID, "bpr_sample_adaptive: bad argument");
-  if (int rc = vs_leave(c)) return rc;  // reads the live user rows
-  if (int rc = snapshot_complete_impl(c)) return rc;  // (sample_args cannot report it)
-  SampleArgs a = sample_args(c);
-  a.users = users; a.n = B; a.seed = seed; a.offset = offset;
-  a.neg = neg_out; a.factor_out = factor_out; a.rank_out = rank_out;
-  a.inv_log1mp = inv_log1mp(p);
-  return launch_sample(c, SAMPLE_ADAPTIVE, a);
-}
-
-int bpr_adaptive_pick(bpr_ctx* c, const int32_t* users, const int32_t* factor, const int32_t* rank,
-                      int64_t B, int32_t* neg_out) {
-  if (int rc = check_bound(c, "bpr_adaptive_pick")) return rc;
-  if (c->indptr == nullptr || !c->have_snapshot)
-    return fail(BPR_ERR_INVALID, "bpr_adaptive_pick: seen CSR / snapshot missing");
-  if (!users || !factor || !rank || !neg_out || B < 0)
-    return fail(BPR_ERR_INVALID, "bpr_adaptive_pick: bad argument");
-  if (int rc = snapshot_complete_impl(c)) return rc;  // (sample_args cannot report it)
-  SampleArgs a = sample_args(c);
-  a.users = users; a.factor_in = factor; a.rank_in = rank; a.n = B; a.neg = neg_out;
-  return launch_sample(c, SAMPLE_PICK, a);
-}
-
-int bpr_adaptive_get_snapshot(bpr_ctx* c, int32_t* order_out, float* sigma_out) {
-  if (int rc = check_bound(c, "bpr_adaptive_get_snapshot")) return rc;
-  if (!c->have_snapshot) return fail(BPR_ERR_INVALID, "bpr_adaptive_get_snapshot: no snapshot");
-  if (int rc = snapshot_complete_impl(c)) return rc;
-  if (order_out)
-    BPR_HIP_CHECK(hipMemcpyAsync(order_out, c->order, sizeof(int32_t) * (size_t)c->d * c->I,
-                                 hipMemcpyDeviceToDevice, c->stream));
-  if (sigma_out)
-    BPR_HIP_CHECK(hipMemcpyAsync(sigma_out, c->sigma, sizeof(float) * c->d,
-                                 hipMemcpyDeviceToDevice, c->stream));
-  return BPR_OK;
-}
-
-// ---- hot path -----------------------------------------------------------------------------------
-int bpr_forward(bpr_ctx* c, const int32_t* users, const int32_t* pos, const int32_t* neg,
-                int64_t B, float* out_logits_pos, float* out_logits_neg, float* out_scalars) {
-  if (int rc = check_triples(c, "bpr_forward", users, pos, B)) return rc;
-  if (neg == nullptr && B > 0) return fail(BPR_ERR_INVALID, "bpr_forward: neg is NULL");
-  if (int rc = vs_leave(c)) return rc;
-  TripleArgs a = triple_args(c);
-  a.users = users; a.pos = pos; a.neg = neg; a.n = B;
-  a.lpos = out_logits_pos; a.lneg = out_logits_neg; a.scalars = out_scalars;
-  return launch_triples<MODE_FORWARD>(c, a, false);
-}
-
-int bpr_forward_grad(bpr_ctx* c, const int32_t* users, const int32_t* pos, const int32_t* neg,
-                     int64_t B, float* out_logits_pos, float* out_logits_neg, float* out_scalars) {
-  if (int rc = check_triples(c, "bpr_forward_grad", users, pos, B)) return rc;
-  if (neg == nullptr && B > 0) return fail(BPR_ERR_INVALID, "bpr_forward_grad: neg is NULL");
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (int rc = vs_leave(c)) return rc;
-  if (int rc = ensure_strict_scratch(c)) return rc;
-  TripleArgs a = triple_args(c);
-  a.users = users; a.pos = pos; a.neg = neg; a.n = B;
-  a.lpos = out_logits_pos; a.lneg = out_logits_neg; a.scalars = out_scalars;
-  c->pending += 3 * B;
-  if (c->pending > c->U + c->I) c->pending = c->U + c->I;
-  return launch_triples<MODE_GRAD>(c, a, true);
-}
-
-int bpr_apply(bpr_ctx* c) {
-  if (int rc = check_bound(c, "bpr_apply")) return rc;
-  c->keys_cut = false;
-  c->bias_w_valid = false;  // writes the item_bias
-  if (int rc = check_opt_state(c, "bpr_apply")) return rc;
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (int rc = ensure_strict_scratch(c)) return rc;
-  c->step += 1;
-  if (c->pending > 0) {
-    ApplyArgs a = apply_args(c, c->step);
-    int rc = dispatch_ge(c->G, c->E, [&](auto tag) -> int {
-      using T = decltype(tag);
-      const unsigned grid = (unsigned)((c->pending * T::G + 255) / 256);
-      hipLaunchKernelGGL((k_apply<T::G, T::E>), dim3(grid), dim3(256), 0, c->stream, a);
-      BPR_HIP_CHECK(hipGetLastError());
-      return BPR_OK;
-    });
-    if (rc) return rc;
-    c->cnt_sel ^= 1;  // the kernel cleared the other counter
-    c->pending = 0;
-  }
-  return BPR_OK;
-}
-
-int bpr_discard_grad(bpr_ctx* c) {
-  if (int rc = check_bound(c, "bpr_discard_grad")) return rc;
-  if (c->GP == nullptr || c->pending == 0) return BPR_OK;
-  ApplyArgs a = apply_args(c, c->step);
-  int rc = dispatch_ge(c->G, c->E, [&](auto tag) -> int {
-    using T = decltype(tag);
-    const unsigned grid = (unsigned)((c->pending * T::G + 255) / 256);
-    hipLaunchKernelGGL((k_discard<T::G, T::E>), dim3(grid), dim3(256), 0, c->stream, a);
-    BPR_HIP_CHECK(hipGetLastError());
-    return BPR_OK;
-  });
-  if (rc) return rc;
-  c->cnt_sel ^= 1;  // the kernel cleared the other counter
-  c->pending = 0;
-  return BPR_OK;
-}
-
-int bpr_get_grad(bpr_ctx* c, float* gP, float* gQ, float* gbias) {
-  if (int rc = check_bound(c, "bpr_get_grad")) return rc;
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (int rc = ensure_strict_scratch(c)) return rc;
-  if (gP)
-    BPR_HIP_CHECK(hipMemcpyAsync(gP, c->GP, sizeof(float) * (size_t)c->U * c->d,
-                                 hipMemcpyDeviceToDevice, c->stream));
-  if (gQ)
-    BPR_HIP_CHECK(hipMemcpyAsync(gQ, c->GQ, sizeof(float) * (size_t)c->I * c->d,
-                                 hipMemcpyDeviceToDevice, c->stream));
-  if (gbias)
-    BPR_HIP_CHECK(hipMemcpyAsync(gbias, c->Gb, sizeof(float) * (size_t)c->I,
-                                 hipMemcpyDeviceToDevice, c->stream));
-  return BPR_OK;
-}
-
-static int train_stream_impl(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg,
-                             int64_t n, int32_t sampler, float adaptive_p, uint64_t seed,
-                             uint64_t offset, int64_t max_inflight, float* out_scalars, bool cut,
-                             bool acut = false) {
-  if (acut)  // (no snapshot to cut)
-    if (int rc = refuse_scored("bpr_train_stream_acut", sampler)) return rc;
-  if (c != nullptr) c->acut_call = acut;  // (check_bound folds pending hot deltas for everybody else)
-  const int rc0 = check_triples(c, "bpr_train_stream", users, pos, n);
-  if (c != nullptr) c->acut_call = false;
-  if (rc0) return rc0;
-  c->keys_cut = false;  // the item table moves
-  if (int rc = check_sampler(c, "bpr_train_stream", sampler, adaptive_p, neg, n)) return rc;
-  if (c->opt_kind != BPR_OPT_SGD)
-    return fail(BPR_ERR_UNSUPPORTED,
-                "bpr_train_stream: this launch implements plain SGD only; momentum / Adam / RMSprop / "
-                "Adagrad run through bpr_train_stream_batched (one launch per refresh period) or STRICT "
-                "(bpr_forward_grad + bpr_apply)");
-  if (c->pending != 0)
-    return fail(BPR_ERR_INVALID, "bpr_train_stream: unapplied STRICT gradients pending");
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (int rc = vs_leave(c)) return rc;
-  if (n >= ((int64_t)1 << 31) || c->U * c->d >= ((int64_t)1 << 31) ||
-      c->I * c->d >= ((int64_t)1 << 31))
-    return fail(BPR_ERR_UNSUPPORTED,
-                "bpr_train_stream: n and rows*d must be < 2^31 (32-bit offsets in the kernel)");
-  StreamArgs a;
-  memset(&a, 0, sizeof(a));
-  a.P = c->P; a.Q = c->Q; a.bias = c->bias;
-  a.indptr = c->indptr; a.indices = c->indices;
-  a.order = c->order; a.sigma = c->sigma;
-  if (c->meta_front != nullptr && c->keys_front_stale)
-    return fail(BPR_ERR_INVALID, "bpr_train_stream: the partial snapshot in front was sorted from keys a later cut has "
-                                 "overwritten; commit the pending refresh first");
-  a.snap_meta = c->meta_front;
-  a.snap_keys = c->meta_front != nullptr ? c->keys_front : nullptr;
-  a.users = users; a.pos = pos; a.neg = neg;
-  a.partials = out_scalars != nullptr ? c->dev_scalars : nullptr;
-  a.seed = seed; a.offset = offset;
-  a.n = (int32_t)n; a.I = (int32_t)c->I; a.d = c->d;
-  a.pad_user = c->pad_user; a.pad_item = c->pad_item;
-  a.run_len = c->run_len;  // 0: launch_stream picks it from the launch size and the chip's occupancy
-  a.grouped = c->grouped;
-  a.au = c->au; a.ai = c->ai; a.an = c->an; a.lr = c->opt.lr;
-  a.iw = ItemWeights{c->w_accept, c->w_alias};
-  a.inv_log1mp = sampler == BPR_NEG_ADAPTIVE ? inv_log1mp(adaptive_p) : 0.f;
-  a.dyn_M = c->dyn_M;
-  a.warp_N = c->warp_N;
-  a.warp_margin = c->warp_margin;
-  if (sampler != BPR_NEG_GIVEN) {
-    if (int rc = heavy_build_impl(c)) return rc;
-    a.heavy_off = c->heavy_off;
-    a.heavy_bits = c->heavy_bits;
-    a.heavy_T = c->heavy_T;
-  }
-  if (c->hot_H > 0) {
-    a.hot_slot = c->hot_slot;
-    a.hot_delta = c->hot_delta;
-    a.hot_H = c->hot_H;
-    a.hot_rmask = c->hot_R - 1;
-  }
-  if (acut && (c->hot_tier || c->vs_active))
-    return fail(BPR_ERR_INVALID, "bpr_train_stream_acut: not under the hot tier / batched STREAM bookkeeping");
-  if (acut)
-    if (int rc = refresh_alloc(c)) return rc;
-  return launch_stream(c, a, sampler, max_inflight, out_scalars, cut && !acut, acut);
-}
-
-int bpr_train_stream(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg, int64_t n,
-                     int32_t sampler, float adaptive_p, uint64_t seed, uint64_t offset,
-                     int64_t max_inflight, float* out_scalars) {
-  return train_stream_impl(c, users, pos, neg, n, sampler, adaptive_p, seed, offset, max_inflight,
-                           out_scalars, false);
-}
-
-int bpr_train_stream_cut(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg,
-                         int64_t n, int32_t sampler, float adaptive_p, uint64_t seed, uint64_t offset,
-                         int64_t max_inflight, float* out_scalars) {
-  if (n <= 0)
-    return fail(BPR_ERR_INVALID, "bpr_train_stream_cut: needs a non-empty launch (the cut rides "
-                                 "on its epilogue)");
-  return train_stream_impl(c, users, pos, neg, n, sampler, adaptive_p, seed, offset, max_inflight,
-                           out_scalars, true);
-}
-
-int bpr_train_stream_acut(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg,
-                          int64_t n, int32_t sampler, float adaptive_p, uint64_t seed, uint64_t offset,
-                          int64_t max_inflight, float* out_scalars) {
-  if (n <= 0)
-    return fail(BPR_ERR_INVALID, "bpr_train_stream_acut: needs a non-empty launch");
-  return train_stream_impl(c, users, pos, neg, n, sampler, adaptive_p, seed, offset, max_inflight,
-                           out_scalars, true, true);
-}
-
-int bpr_hot_fold(bpr_ctx* c) {
-  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_hot_fold: ctx is NULL");
-  return hot_fold_impl(c);
-}
-
-int bpr_step(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg, int64_t B,
-             int32_t mode, int32_t sampler, float adaptive_p, uint64_t seed, uint64_t offset,
-             float* out_logits_pos, float* out_logits_neg, float* out_scalars) {
-  if (mode == BPR_MODE_STRICT)  // (dynamic: draw with bpr_sample_dynamic, pass the picks as BPR_NEG_GIVEN)
-    if (int rc = refuse_scored("bpr_step (STRICT mode)", sampler)) return rc;
-  if (int rc = check_triples(c, "bpr_step", users, pos, B)) return rc;
-  if (int rc = check_sampler(c, "bpr_step", sampler, adaptive_p, neg, B)) return rc;
-  if (mode == BPR_MODE_STREAM) {
-    if (out_logits_pos || out_logits_neg)
-      return fail(BPR_ERR_UNSUPPORTED, "bpr_step: STREAM mode does not return logits");
-    return bpr_train_stream(c, users, pos, neg, B, sampler, adaptive_p, seed, offset, 0,
-                            out_scalars);
-  }
-  if (mode != BPR_MODE_STRICT) return fail(BPR_ERR_INVALID, "bpr_step: unknown mode");
-  if (sampler != BPR_NEG_GIVEN) {
-    if (neg == nullptr && B > 0)
-      return fail(BPR_ERR_INVALID, "bpr_step: STRICT mode needs a neg buffer to sample into");
-    int rc = sampler == BPR_NEG_UNIFORM
-                 ? bpr_sample_uniform(c, users, B, seed, offset, neg)
-                 : bpr_sample_adaptive(c, users, B, adaptive_p, seed, offset, neg, nullptr,
-                                       nullptr);
-    if (rc) return rc;
-  }
-  if (int rc = bpr_forward_grad(c, users, pos, neg, B, out_logits_pos, out_logits_neg,
-                                out_scalars))
-    return rc;
-  return bpr_apply(c);
-}
-
-int bpr_train_strict(bpr_ctx* c, const int32_t* users, const int32_t* pos, int32_t* neg_scratch,
-                     int64_t n, int64_t B, int32_t sampler, float adaptive_p, uint64_t seed,
-                     uint64_t offset, int64_t refresh_every, float* out_scalars) {
-  // (dynamic: draw each batch with bpr_sample_dynamic, step with BPR_NEG_GIVEN)
-  if (int rc = refuse_scored("bpr_train_strict", sampler)) return rc;
-  if (int rc = check_triples(c, "bpr_train_strict", users, pos, n)) return rc;
-  if (B < 1) return fail(BPR_ERR_INVALID, "bpr_train_strict: B must be >= 1");
-  if (int rc = check_sampler(c, "bpr_train_strict", sampler, adaptive_p, neg_scratch, n)) return rc;
-  if (sampler != BPR_NEG_GIVEN && neg_scratch == nullptr && n > 0)
-    return fail(BPR_ERR_INVALID, "bpr_train_strict: neg_scratch is NULL");
-  // loss statistics: k_triples adds each batch's partial sums to the per-block scratch and ONE
-  // k_sum_partials at the end adds them to out_scalars (instead of one extra launch per batch)
-  const bool defer = out_scalars != nullptr && n > 0;
-  const unsigned stat_blocks = grid_for(B < n ? B : n, c->G, 0);
-  if (defer) {
-    BPR_HIP_CHECK(hipSetDevice(c->device));
-    BPR_HIP_CHECK(hipMemsetAsync(c->dev_scalars, 0, sizeof(float) * 4 * stat_blocks, c->stream));
-    c->defer_stats = true;
-  }
-  // AdaptiveSampler.sample (neg_samplers.py:74-124): _iteration_cnt += 1; draw with the CURRENT
-  // snapshot; if _iteration_cnt % every == 0: update_stats() — i.e. the snapshot is retaken after
-  // the draws of that batch and BEFORE its optimizer step, and the counter lives as long as the
-  // sampler (it is not reset at epoch boundaries): c->strict_iter carries it across calls.
-  int rc = BPR_OK;
-  for (int64_t lo = 0; lo < n && rc == BPR_OK; lo += B) {
-    const int64_t b = n - lo < B ? n - lo : B;
-    int32_t* neg = sampler == BPR_NEG_GIVEN ? neg_scratch + lo : neg_scratch;
-    if (sampler == BPR_NEG_UNIFORM)
-      rc = bpr_sample_uniform(c, users + lo, b, seed, offset + (uint64_t)lo, neg);
-    else if (sampler == BPR_NEG_ADAPTIVE)
-      rc = bpr_sample_adaptive(c, users + lo, b, adaptive_p, seed, offset + (uint64_t)lo, neg,
-                               nullptr, nullptr);
-    c->strict_iter += 1;
-    if (rc == BPR_OK && refresh_every > 0 && c->strict_iter % refresh_every == 0) {
-      rc = bpr_flush_lazy(c);
-      if (rc == BPR_OK) rc = bpr_adaptive_refresh(c);
-    }
-    if (rc == BPR_OK)
-      rc = bpr_forward_grad(c, users + lo, pos + lo, neg, b, nullptr, nullptr, nullptr);
-    if (rc == BPR_OK) rc = bpr_apply(c);
-  }
-  c->defer_stats = false;
-  if (rc != BPR_OK) return rc;
-  if (defer) {
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->dev_scalars,
-                       (int)stat_blocks, out_scalars);
-    BPR_HIP_CHECK(hipGetLastError());
-  }
-  return BPR_OK;
-}
-
-int bpr_item_delta(const float* q, const float* base, float* own, float* tot, int64_t n,
-                   void* hip_stream) {
-  if (n < 0 || (n > 0 && (!q || !base || !own || !tot)))
-    return fail(BPR_ERR_INVALID, "bpr_item_delta: bad argument");
-  if (n == 0) return BPR_OK;
-  const unsigned grid = (unsigned)std::min<int64_t>((n + 1023) / 1024, 4096);
-  hipLaunchKernelGGL(k_item_delta, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, q, base, own,
-                     tot, n);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
-int bpr_item_fold(float* q, float* base, const float* own, const float* tot, float scale,
-                  int32_t rebase, int64_t n, void* hip_stream) {
-  if (n < 0 || (n > 0 && (!q || !base || !own || !tot)))
-    return fail(BPR_ERR_INVALID, "bpr_item_fold: bad argument");
-  if (n == 0) return BPR_OK;
-  const unsigned grid = (unsigned)std::min<int64_t>((n + 1023) / 1024, 4096);
-  hipLaunchKernelGGL(k_item_fold, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, q, base, own,
-                     tot, scale, rebase, n);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
-int bpr_item_fold_delta(float* q, float* base, float* own, float* tot, float scale, int64_t n,
-                        void* hip_stream) {
-  if (n < 0 || (n > 0 && (!q || !base || !own || !tot)))
-    return fail(BPR_ERR_INVALID, "bpr_item_fold_delta: bad argument");
-  if (n == 0) return BPR_OK;
-  const unsigned grid = (unsigned)std::min<int64_t>((n + 1023) / 1024, 4096);
-  hipLaunchKernelGGL(k_item_fold_delta, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, q, base,
-                     own, tot, scale, n);
-  BPR_HIP_CHECK(hipGetLastError());
-  return BPR_OK;
-}
-
-int bpr_set_hot_rows(bpr_ctx* c, int32_t hot_rows, int32_t replicas) {
-  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_set_hot_rows: ctx is NULL");
-  if (hot_rows < 0 || hot_rows > 32768)
-    return fail(BPR_ERR_INVALID, "bpr_set_hot_rows: hot_rows must be in [0, 32768]");
-  if (hot_rows > 0 && replicas != 1 && replicas != 2 && replicas != 4 && replicas != 8)
-    return fail(BPR_ERR_INVALID, "bpr_set_hot_rows: replicas must be 1, 2, 4 or 8");
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  BPR_HIP_CHECK(hipStreamSynchronize(c->stream));
-  hot_free(c);  // rebuilt by the next bpr_plan_epoch
-  c->hot_rows_opt = hot_rows;
-  c->hot_reps_opt = hot_rows > 0 ? replicas : 0;
-  return BPR_OK;
-}
-
-int bpr_set_hot_lds(bpr_ctx* c, int32_t rows, int32_t always) {
-  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_set_hot_lds: ctx is NULL");
-  if (rows < 0 || rows > 32767) return fail(BPR_ERR_INVALID, "bpr_set_hot_lds: rows must be in [0, 32767]");
-  c->tune_hot_lds = rows;
-  c->tune_hot_lds_force = always != 0;
-  return BPR_OK;
-}
-
-int bpr_stream_lds_rows(bpr_ctx* c) {
-  return c == nullptr ? 0 : c->last_lds_rows;
-}
-
-int bpr_set_hot_items(bpr_ctx* c, const int32_t* items_host, int32_t H, const uint32_t* counts_host) {
-  if (int rc = check_bound(c, "bpr_set_hot_items")) return rc;
-  if (H < 0 || H > 32768 || H >= c->I || (H > 0 && items_host == nullptr))
-    return fail(BPR_ERR_INVALID, "bpr_set_hot_items: need 0 <= H <= min(32768, I - 1) item ids");
-  if (c->hot_tier) return fail(BPR_ERR_INVALID, "bpr_set_hot_items: the hot tier is on (bpr_hot_tier_end first)");
-  std::vector<char> seen((size_t)c->I, 0);
-  for (int k = 0; k < H; ++k) {
-    const int32_t it = items_host[k];
-    if (it < 0 || it >= c->I || it == c->pad_item || seen[it])
-      return fail(BPR_ERR_INVALID, "bpr_set_hot_items: ids must be distinct item rows, not the pad row");
-    seen[it] = 1;
-  }
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  BPR_HIP_CHECK(hipStreamSynchronize(c->stream));
-  return hot_set_items_impl(c, items_host, H, counts_host);
-}
-
-int bpr_hot_rows(bpr_ctx* c, int32_t* rows_host) {
-  if (c == nullptr || rows_host == nullptr) return fail(BPR_ERR_INVALID, "bpr_hot_rows: NULL argument");
-  *rows_host = c->hot_H;
-  return BPR_OK;
-}
-
-int bpr_hot_tier_begin(bpr_ctx* c, float* hot_base) {
-  if (int rc = check_bound(c, "bpr_hot_tier_begin")) return rc;
-  if (c->hot_H <= 0 || !c->hot_explicit)
-    return fail(BPR_ERR_INVALID, "bpr_hot_tier_begin: no hot set (bpr_set_hot_items first: the ranks "
-                                 "must agree on it)");
-  if (hot_base == nullptr) return fail(BPR_ERR_INVALID, "bpr_hot_tier_begin: hot_base is NULL");
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  const int64_t n = (int64_t)c->hot_H * c->d;
-  hipLaunchKernelGGL(k_hot_gather, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256),
-                     0, c->stream, c->Q, c->hot_items, c->hot_canon, hot_base, c->hot_H, c->d);
-  BPR_HIP_CHECK(hipGetLastError());
-  c->hot_tier = true;
-  return BPR_OK;
-}
-
-int bpr_hot_tier_end(bpr_ctx* c) {
-  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_hot_tier_end: ctx is NULL");
-  if (int rc = flush_deferred_stats(c)) return rc;
-  c->hot_tier = false;  // (the caller has folded everything: bpr_hot_exchange with cut = 1 last)
-  return BPR_OK;
-}
-
-int bpr_hot_exchange(bpr_ctx* c, float* hot_base, float* tot, int32_t fold_prev, int32_t cut,
-                     float* cold_base) {
-  if (int rc = check_bound(c, "bpr_hot_exchange")) return rc;
-  if (!c->hot_tier) return fail(BPR_ERR_INVALID, "bpr_hot_exchange: the hot tier is off (bpr_hot_tier_begin)");
-  if (hot_base == nullptr || tot == nullptr)
-    return fail(BPR_ERR_INVALID, "bpr_hot_exchange: NULL buffer");
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (int rc = flush_deferred_stats(c)) return rc;  // a cut launch that was not followed by bpr_sync_cut
-  c->keys_cut = false;  // the item table moves
-  HotStepArgs a;
-  memset(&a, 0, sizeof(a));
-  a.Q = c->Q; a.delta = c->hot_delta; a.hot_items = c->hot_items; a.canon = c->hot_canon;
-  a.hb = hot_base; a.tot = tot; a.cold_base = cold_base;
-  a.H = c->hot_H; a.R = c->hot_R; a.d = c->d; a.fold_prev = fold_prev != 0; a.cut = cut != 0;
-  const int64_t n = (int64_t)c->hot_H * c->d;
-  hipLaunchKernelGGL(k_hot_step, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0,
-                     c->stream, a);
-  BPR_HIP_CHECK(hipGetLastError());
-  if (cut) c->hot_uncut = false;  // the block is zero again: the next launch may take the LDS tier
-  return BPR_OK;
-}
-
-int bpr_set_heavy_users(bpr_ctx* c, int32_t threshold, int64_t max_bytes) {
-  if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_set_heavy_users: ctx is NULL");
-  if (threshold < -1 || max_bytes < 0)
-    return fail(BPR_ERR_INVALID, "bpr_set_heavy_users: threshold >= -1, max_bytes >= 0");
-  c->heavy_T_opt = threshold;
-  if (max_bytes > 0) c->heavy_max_bytes = max_bytes;
-  c->heavy_for = nullptr;  // rebuilt by the next sampling STREAM launch
-  return BPR_OK;
-}
-
-int bpr_heavy_users(bpr_ctx* c, int64_t* n, int32_t* threshold) {
-  if (c == nullptr || n == nullptr || threshold == nullptr)
-    return fail(BPR_ERR_INVALID, "bpr_heavy_users: NULL argument");
-  const bool built = c->heavy_for != nullptr && c->heavy_for == c->indptr;
-  *n = built ? c->heavy_n : 0;
-  *threshold = built ? c->heavy_T : c->heavy_T_opt;
-  return BPR_OK;
-}
-
-int bpr_sync_cut(bpr_ctx* c, float* hot_base, float* hot_tot, int32_t hot_fold_prev, float* cold_base,
-                 float* cold_own, float* cold_tot, float scale, int32_t cold_mode) {
-  if (int rc = check_bound(c, "bpr_sync_cut")) return rc;
-  if (cold_mode < 0 || cold_mode > 2 || (cold_mode != 0 && (!cold_base || !cold_own || !cold_tot)))
-    return fail(BPR_ERR_INVALID, "bpr_sync_cut: cold_mode 0 | 1 | 2 with base / own / tot");
-  if (c->hot_tier && (hot_base == nullptr || hot_tot == nullptr))
-    return fail(BPR_ERR_INVALID, "bpr_sync_cut: the hot tier is on: hot_base / hot_tot needed");
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (int rc = refresh_alloc(c)) return rc;
-  if (int rc = ensure_cut_events(c)) return rc;
-  SyncCutArgs a;
-  memset(&a, 0, sizeof(a));
-  a.e = cut_args(c, c->dev_scalars, c->defer_pending ? c->defer_blocks : 0, c->defer_pending ? c->defer_out : nullptr,
-                 c->hot_H > 0, false, false);
-  a.canon = c->hot_canon; a.hb = hot_base; a.htot = hot_tot;
-  a.base = cold_base; a.own = cold_own; a.tot = cold_tot; a.scale = scale;
-  a.hot_tier = c->hot_tier ? 1 : 0; a.hot_fold_prev = hot_fold_prev != 0; a.cold_mode = cold_mode;
-  hipExtLaunchKernelGGL(k_sync_cut, cut_grid(c), dim3(256), 0, c->stream, nullptr, c->ev_keys, 0, a);
-  BPR_HIP_CHECK(hipGetLastError());
-  c->defer_pending = false;
-  c->hot_uncut = false;  // (the hot-tier step cut the block)
-  c->keys_cut = true;   // the next bpr_adaptive_refresh_begin only queues the sort
-  c->keys_event = true;
   return BPR_OK;
 }
 
@@ -1407,18 +326,14 @@ int bpr_set_tuning(bpr_ctx* c, const char* key, int32_t value) {
 int bpr_set_bias_tracking(bpr_ctx* c, int32_t on) {
   if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_set_bias_tracking: ctx is NULL");
   c->bias_track = on != 0;
-  c->bias_w_valid = false;
+  bias_moved(c);  // (what the wide table holds was not tracked so far)
   return BPR_OK;
 }
 
 int bpr_bias_written(bpr_ctx* c) {
   if (c == nullptr) return fail(BPR_ERR_INVALID, "bpr_bias_written: ctx is NULL");
-  c->bias_w_valid = false;
+  bias_moved(c);
   return BPR_OK;
-}
-
-int bpr_stream_run_len(bpr_ctx* c) {
-  return c == nullptr ? 0 : c->last_run_len;
 }
 
 // Test hook, not API (tests/test_stream_plan_cpu.py sets its signature): the launch plan of a shape given as plain
@@ -1489,32 +404,6 @@ int bpr_plan_chunk(bpr_ctx* c, const int32_t* users_in, const int32_t* pos_in, i
     return rc;
   BPR_HIP_CHECK(hipEventRecord(c->ev_sorted, c->side));
   return BPR_OK;
-}
-
-int bpr_flush_lazy(bpr_ctx* c) {
-  if (int rc = check_bound(c, "bpr_flush_lazy")) return rc;
-  c->keys_cut = false;
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (c->vs_active) return vs_flush(c, true, true);  // batched STREAM bookkeeping is live
-  return strict_flush_impl(c);
-}
-
-int bpr_flush_items(bpr_ctx* c) {
-  if (int rc = check_bound(c, "bpr_flush_items")) return rc;
-  c->keys_cut = false;
-  c->bias_w_valid = false;
-  BPR_HIP_CHECK(hipSetDevice(c->device));
-  if (c->vs_active) return vs_flush(c, false, true);
-  if (!opt_kind_lazy(c->opt_kind) || c->GP == nullptr || c->step == 0) return BPR_OK;
-  if (int rc = check_opt_state(c, "bpr_flush_items")) return rc;
-  ApplyArgs a = apply_args(c, c->step);
-  return dispatch_ge(c->G, c->E, [&](auto tag) -> int {
-    using T = decltype(tag);
-    hipLaunchKernelGGL((k_flush_lazy<T::G, T::E>), dim3(grid_for(c->I, T::G, 0)), dim3(256), 0,
-                       c->stream, a, 1);
-    BPR_HIP_CHECK(hipGetLastError());
-    return BPR_OK;
-  });
 }
 
 int bpr_get_step_host(bpr_ctx* c, int64_t* step_host) {
