@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_neighbors_norms(const float* __restrict
 // it the kernel is what it was before there were filters.
 template <bool VEC, bool COS, bool FILT>
 __global__ __launch_bounds__(256) void k_neighbors(const MaybeFiltered<FILT, NeighborsArgs> a) {
-  constexpr int TU = TOPK_TU, TI = TOPK_TI, KC = TOPK_KC, LD = TOPK_LD;
+  constexpr int TU = TOPK_TU, TI = TOPK_TI, LD = TOPK_LD;
   extern __shared__ __align__(16) unsigned char smem[];
   const int cap = a.k + TI;
   float* const sT = reinterpret_cast<float*>(smem);          // [TI][LD]
@@ -130,62 +130,26 @@ __global__ __launch_bounds__(256) void k_neighbors(const MaybeFiltered<FILT, Nei
   }
   __syncthreads();
 
-  // the next chunk travels global -> registers while the current one is multiplied, then registers -> LDS
-  float4 treg[4], xreg[2];
+  // the walk (bpr_topk_shared.h).  FILT: the slice's non-empty tiles only.  Cosine: a tile's norms travel with its
+  // first chunk (read in (A) of this tile only, which a barrier separates from the next tile's first stash).
   float rnreg = 0.f;
-  auto fetch = [&](int64_t t, int c) {
-    const int kc = c * KC;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
-      const int64_t j = t * TI + row;
-      treg[m] = j < a.N ? load4<VEC>(a.T + j * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
-      const int u = sRow[row];
-      xreg[m] = u >= 0 ? load4<VEC>(a.X + (int64_t)u * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+  auto fetch_norms = [&](int64_t t, int c) {
     if (COS && c == 0 && tid < TI) {
       const int64_t j = t * TI + tid;
       rnreg = j < a.N ? a.rn_t[j] : -1.0f;
     }
   };
-  auto stash = [&](int c) {
-    BPR_STASH_CHUNK(sT, treg, 4, tid, 256);
-    BPR_STASH_CHUNK(sX, xreg, 2, tid, 256);
-    // (read in (A) of this tile only, which a barrier separates from the next tile's first stash)
+  auto stash_norms = [&](int64_t, int c) {
     if (COS && c == 0 && tid < TI) sRnT[tid] = rnreg;
   };
-
-  const int nch = (a.d + KC - 1) / KC;
-  const float* const ta = sT + (32 * w + r) * LD + 4 * h;
-  const float* const xb0 = sX + r * LD + 4 * h;
-  const float* const xb1 = sX + (32 + r) * LD + 4 * h;
-  // The walk: k_topk's form (bpr_topk.hip).  FILT: tile_from(t) is the first non-empty tile at or after t, or t1,
-  // and tn the one after the current tile; without a filter the loop is `for (t = t0; t < t1; ++t)` to the compiler.
   auto tile_from = [&](int64_t t) -> int64_t {
     if constexpr (FILT) return filter_next_tile_from(a.filter, a.N, t, t1, a.first);
     else return t;
   };
-  int64_t tn = 0;
-  auto next = [&](int64_t t) -> int64_t { return FILT ? tn : t + 1; };
-  const int64_t start = tile_from(t0);
-  if (start < t1) fetch(start, 0);
-  for (int64_t t = start; t < t1; t = next(t)) {
-    if constexpr (FILT) tn = tile_from(t + 1);
-    f32x16 acc0 = {0.f}, acc1 = {0.f};
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.f;
-    for (int c = 0; c < nch; ++c) {
-      __syncthreads();
-      stash(c);
-      __syncthreads();
-      if (c + 1 < nch) fetch(t, c + 1);
-      else if (next(t) < t1) fetch(next(t), 0);
-      mfma_chunk2(ta, xb0, xb1, acc0, acc1);
-    }
+  const table_tiles table = {a.N};
+  BPR_WALK_LANE(a.d, sT, sX);
+  BPR_WALK_TILES_BEGIN(VEC, FILT, tile_from(t0), t1, table, a.T, a.X, a.d, sRow, sT, sX, tile_from, fetch_norms,
+                       stash_norms)
 
     // ---- epilogue of the tile: register q of the lane is table row jbase + (q & 3) + 8 (q >> 2) of queries r, 32 + r
     const int64_t jbase = t * TI + 32 * w + 4 * h;
@@ -236,7 +200,7 @@ __global__ __launch_bounds__(256) void k_neighbors(const MaybeFiltered<FILT, Nei
         }
       }
     }
-  }
+  BPR_WALK_TILES_END
   __syncthreads();
 
   // ---- the slice's result: every query sorted, padded with (-inf, -1)

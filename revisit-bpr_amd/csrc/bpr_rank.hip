@@ -203,9 +203,8 @@ __global__ __launch_bounds__(256) void k_rank(const MaybeFiltered<FILT, RankArgs
   int top = 0;  // ranking: the first step of the binary search (largest power of two <= the longest list)
   const int32_t* seen = nullptr;  // ranking: this thread's quarter of row tid >> 2's seen list
   int se = 0, slen = 0, snext = INT_MAX;
-  // The walk.  SKIP: the slice's non-empty tiles only — tile_from(t) is the first of them at or after t, or t1, and
-  // tn the one after the current tile (k_topk's form, bpr_topk.hip: without a filter the loop is
-  // `for (t = t0; t < t1; ++t)` to the compiler: profiles/rank_neighbors_filter_resources.md).
+  // The walk: the contract is the head of bpr_topk_shared.h; the loop is this kernel's own copy of BPR_WALK_TILES_BEGIN
+  // (why: there).  SKIP: the slice's non-empty tiles only.
   auto tile_from = [&](int64_t t) -> int64_t {
     if constexpr (SKIP) return filter_next_tile(a.filter, a.I, t, t1);
     else return t;

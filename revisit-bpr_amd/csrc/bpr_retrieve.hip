@@ -121,7 +121,7 @@ __device__ __forceinline__ int sort_row(const Cand* buf, int c, int checked, con
 // the loop walks the unit's non-empty tiles only.  Without it the kernel is what it was before there were filters.
 template <bool VEC, bool FILT>
 __global__ __launch_bounds__(256) void k_retrieve(const MaybeFiltered<FILT, RetrieveArgs> a) {
-  constexpr int TU = TOPK_TU, TI = TOPK_TI, KC = TOPK_KC, LD = TOPK_LD;
+  constexpr int TU = TOPK_TU, TI = TOPK_TI, LD = TOPK_LD;
   extern __shared__ __align__(16) unsigned char smem[];
   const int cap = a.cap;
   float* const sQ = reinterpret_cast<float*>(smem);               // [TI][LD]
@@ -138,10 +138,7 @@ __global__ __launch_bounds__(256) void k_retrieve(const MaybeFiltered<FILT, Retr
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
   Cand* const gBuf = a.bufs + (int64_t)blockIdx.x * TU * cap;  // this workgroup's block: [TU][cap]
   Cand* const scratch = sScratch + w * cap;
-  const int nch = (a.d + KC - 1) / KC;
-  const float* const qa = sQ + (32 * w + r) * LD + 4 * h;
-  const float* const pb0 = sP + r * LD + 4 * h;
-  const float* const pb1 = sP + (32 + r) * LD + 4 * h;
+  BPR_WALK_LANE(a.d, sQ, sP);  // (once for all units)
   const bool has_bias = a.bias != nullptr;
 
   for (int64_t unit = blockIdx.x; unit < a.units; unit += gridDim.x) {
@@ -150,78 +147,25 @@ __global__ __launch_bounds__(256) void k_retrieve(const MaybeFiltered<FILT, Retr
     const int64_t t0 = a.item_tiles * slice / a.slices, t1 = a.item_tiles * (slice + 1) / a.slices;
 
     if (tid < TU) {
-      const int64_t row = u0 + tid;
-      const bool live = row < a.n;
-      const int u = live ? a.users[row] : -1;
-      int64_t lo = 0;
-      int len = 0;
-      if (live && a.indptr != nullptr && a.indices != nullptr) {
-        lo = a.indptr[u];
-        len = (int)(a.indptr[u + 1] - lo);
-      }
-      sUser[tid] = u;
-      sSeenLo[tid] = lo;
-      sSeenLen[tid] = len;
-      sCnt[tid] = 0;
-      sNeed[tid] = 0;
-      sChecked[tid] = 0;
-      // nothing kept yet: everything beats tau; a row past n: nothing does
-      sTau[tid] = live ? Cand{-INFINITY, INT_MAX} : Cand{INFINITY, -1};
+      BPR_STAGE_USER_ROW(u0 + tid, a.n, a.users, a.indptr, a.indices, sUser, sSeenLo, sSeenLen);
+      BPR_OPEN_SELECTION_ROW(live, sCnt, sNeed, sTau, sChecked[tid] = 0);
     }
     __syncthreads();
 
-    // the next chunk travels global -> registers while the current one is multiplied, then registers -> LDS
-    float4 qreg[4], preg[2];
-    auto fetch = [&](int64_t t, int c) {
-      const int kc = c * KC;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
-        const int64_t item = t * TI + row;
-        qreg[m] = item < a.I ? load4<VEC>(a.Q + item * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const int f = tid + 256 * m, row = f >> 3, kk = kc + 4 * (f & 7);
-        const int u = sUser[row];
-        preg[m] = u >= 0 ? load4<VEC>(a.P + (int64_t)u * a.d, kk, a.d) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    };
-    auto stash = [&]() {
-      BPR_STASH_CHUNK(sQ, qreg, 4, tid, 256);
-      BPR_STASH_CHUNK(sP, preg, 2, tid, 256);
-    };
     // one wave: row's buffer -> its scratch, unseen and sorted; returns how many
     auto sorted_row = [&](int row) {
       return sort_row(gBuf + (int64_t)row * cap, min(sCnt[row], cap), sChecked[row], a.indices + sSeenLo[row],
                       sSeenLen[row], scratch, lane);
     };
 
-    // The walk.  FILT: the unit's non-empty tiles only — tile_from(t) is the first of them at or after t, or t1,
-    // and tn the one after the current tile, found once a tile for the prefetch and the step.  (Written so that
-    // without a filter the loop is `for (t = t0; t < t1; ++t)` to the compiler: profiles/item_filter_resources.md.)
+    // the walk (bpr_topk_shared.h).  FILT: the unit's non-empty tiles only.
     auto tile_from = [&](int64_t t) -> int64_t {
       if constexpr (FILT) return filter_next_tile(a.filter, a.I, t, t1);
       else return t;
     };
-    int64_t tn = 0;
-    auto next = [&](int64_t t) -> int64_t { return FILT ? tn : t + 1; };
-    const int64_t first = tile_from(t0);
-    if (first < t1) fetch(first, 0);
-    for (int64_t t = first; t < t1; t = next(t)) {
-      if constexpr (FILT) tn = tile_from(t + 1);
-      f32x16 acc0 = {0.f}, acc1 = {0.f};
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.f;
-      for (int c = 0; c < nch; ++c) {
-        __syncthreads();
-        stash();
-        __syncthreads();
-        if (c + 1 < nch) fetch(t, c + 1);
-        else if (next(t) < t1) fetch(next(t), 0);
-        mfma_chunk2(qa, pb0, pb1, acc0, acc1);
-      }
-
+    const table_tiles items = {a.I};
+    BPR_WALK_TILES_BEGIN(VEC, FILT, tile_from(t0), t1, items, a.Q, a.P, a.d, sUser, sQ, sP, tile_from, walk_nop(),
+                         walk_nop())
       // ---- epilogue of the item tile: register q of the lane is item ibase + (q & 3) + 8 (q >> 2) of users r, 32 + r
       const int64_t ibase = t * TI + 32 * w + 4 * h;
       float bv[16];
@@ -292,7 +236,7 @@ __global__ __launch_bounds__(256) void k_retrieve(const MaybeFiltered<FILT, Retr
           }
         }
       }
-    }
+    BPR_WALK_TILES_END
     __syncthreads();
 
     // ---- the unit's result: every row unseen and sorted, straight from the scratch, padded with (-inf, -1)

@@ -1,14 +1,31 @@
-// bpr_topk_shared.h — what the serving kernels have in common (k_topk, bpr_topk.hip; k_rank, bpr_rank.hip;
-// k_neighbors, bpr_neighbors.hip; k_rerank, bpr_rerank.hip; k_diversify, bpr_diversify.hip), each piece defined once.
-// Device side: the guarded load of 4 features (load4), the registers -> LDS copy of a staged chunk (stash_piece,
-// BPR_STASH_CHUNK), the dot product's chain as MFMAs and as fmaf (mfma_chunk2, mfma_block1, fma_chain8), the result order (Cand,
-// better), rank-by-counting compaction of a candidate buffer (compact_row) and the selection step k_topk and
-// k_neighbors run alike (compact_overflowing_rows).  Device code only: what the entry points' host sides share is
-// bpr_serving_host.h.  What differs between the kernels — where a staged row comes from, eligibility, what a score
-// becomes — stays in their files.
+// bpr_topk_shared.h — what the serving kernels have in common (k_topk, bpr_topk.hip; k_retrieve, bpr_retrieve.hip;
+// k_sample, bpr_sample.hip; k_rank, bpr_rank.hip; k_neighbors, bpr_neighbors.hip; k_rerank, bpr_rerank.hip;
+// k_diversify, bpr_diversify.hip), each piece defined once.  Device side: the guarded load of 4 features (load4), the
+// registers -> LDS copy of a staged chunk (stash_piece, BPR_STASH_CHUNK), the dot product's chain as MFMAs and as fmaf
+// (mfma_chunk2, mfma_block1, fma_chain8), the result order (Cand, better), rank-by-counting compaction of a candidate
+// buffer (compact_row), the selection step k_topk and k_neighbors run alike (compact_overflowing_rows), the row
+// prologue (BPR_STAGE_USER_ROW, BPR_OPEN_SELECTION_ROW) and the tile walk of the kernels that stream a whole table
+// past 64 rows (BPR_WALK_TILES_BEGIN / _END: k_topk, k_retrieve, k_sample, k_neighbors).  Device code only: what the
+// entry points' host sides share is bpr_serving_host.h.  What differs between the kernels — where a staged row comes
+// from, eligibility, what a score becomes — stays in their files.
+//
+// The walk's contract.  The 256 threads hold chunk (t, c) — TOPK_KC features of the TOPK_TI table rows of tile t and
+// of the TOPK_TU rows — in registers one step before it is multiplied: the first chunk of the first tile is asked for
+// before the loop, and right after chunk (t, c) has been written to LDS the next one is asked for, (t, c + 1) or,
+// behind a tile's last chunk, chunk 0 of the tile that is walked next (nothing behind the last tile), so that its
+// global loads fly while the MFMAs of (t, c) run and, behind a tile's last chunk, while the tile's epilogue runs.
+// Two barriers a chunk.  The one before the stash: every wave has read the chunk before out of LDS, and is through
+// the epilogue of the tile before, so whatever that epilogue read beside the chunks (k_neighbors' norms) may be
+// written again.  The one after it: the chunk is whole before any wave multiplies it.  With a filter the tile that is
+// walked next is not t + 1 but the next non-empty one, a scan over the filter's words: it is found once a tile (tn),
+// at the tile's head, and serves both the prefetch behind the last chunk and the loop's step; without a filter the
+// loop must stay `for (t = t0; t < t1; ++t)` to the compiler, which is why the step is written as it is.
+// k_rank walks the same way but keeps its own copy of the loop (bpr_rank.hip): on the macros, and on the prologue's,
+// its instantiations came out reordered, two of them with other register counts (profiles/serving_walk_resources.md).
 //
 // Every piece here compiles to the instructions of the same statements written out in each kernel; the pieces that
-// did not in any form tried are still in the kernels' files (profiles/topk_shared_resources.md names them).  No division and no square root: the header means the same under the
+// did not in any form tried are still in the kernels' files (profiles/topk_shared_resources.md and
+// profiles/serving_walk_resources.md name them).  No division and no square root: the header means the same under the
 // Makefile's two flag sets.  Not for the plan headers, which stay plain C++.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -171,5 +188,116 @@ __device__ __forceinline__ void compact_overflowing_rows(Cand* sBuf, int* sCnt, 
     if (c + sNeed[row] > cap) compact_row(sBuf + row * cap, c, k, lane, &sTau[row], &sCnt[row]);
   }
 }
+
+// ---- the row prologue of k_topk, k_retrieve and k_sample (thread tid < TOPK_TU, before the first barrier).  Macros
+// for the walk's reason (below): as functions they reorder the prologue's stores.  They name `tid`.
+
+// Row ROW of the N: its user (-1 past N) and where its sorted seen row lies (nothing without a CSR).  Declares `row`,
+// `live` (the row is there) and `u` for the kernel's own fields.
+#define BPR_STAGE_USER_ROW(ROW, N, USERS, INDPTR, INDICES, SUSER, SSEENLO, SSEENLEN) \
+  const int64_t row = (ROW);                                                         \
+  const bool live = row < (N);                                                       \
+  const int u = live ? (USERS)[row] : -1;                                            \
+  {                                                                                  \
+    int64_t lo_ = 0;                                                                 \
+    int len_ = 0;                                                                    \
+    if (live && (INDPTR) != nullptr && (INDICES) != nullptr) {                       \
+      lo_ = (INDPTR)[u];                                                             \
+      len_ = (int)((INDPTR)[u + 1] - lo_);                                           \
+    }                                                                                \
+    (SUSER)[tid] = u;                                                                \
+    (SSEENLO)[tid] = lo_;                                                            \
+    (SSEENLEN)[tid] = len_;                                                          \
+  }
+
+// Nothing kept yet: everything beats tau; a row that takes nothing (TAKES false: past n): nothing does.  What follows
+// STAU is the kernel's own per-row reset, if it has one (k_retrieve's sChecked), at the place it has always had.
+#define BPR_OPEN_SELECTION_ROW(TAKES, SCNT, SNEED, STAU, ...) \
+  (SCNT)[tid] = 0;                                            \
+  (SNEED)[tid] = 0;                                           \
+  __VA_ARGS__;                                                \
+  (STAU)[tid] = (TAKES) ? bpr::Cand{-INFINITY, INT_MAX} : bpr::Cand{INFINITY, -1}
+
+// ---- the walk: 256 threads, TOPK_TU rows, the table tiles [FIRST, T1) past them (the contract: the head of this
+// file).  A macro pair, for BPR_STASH_CHUNK's reason: as a function that takes the kernel's pieces as lambdas, by
+// value or by reference, forced inline or not, every instantiation of k_topk came out rescheduled, with other register
+// and spill counts (profiles/serving_walk_resources.md); expanded in place, the loop compiles to the parent's
+// instructions.  Being macros they have no scope: they are for the kernels of namespace bpr, they name `tid`, `w`,
+// `r`, `h` as every serving kernel declares them, and they declare `t`, `acc0`, `acc1` for the code between them,
+// which is the tile's epilogue: register q of the lane is staged table row 32 w + 4 h + (q & 3) + 8 (q >> 2) of
+// tile t against rows r (acc0) and 32 + r (acc1).  One walk per scope, BPR_WALK_LANE before it (k_retrieve: once,
+// outside its loop over units).  The kernel passes what differs:
+//   VEC, SKIP        16-byte or element loads; whether TILE_FROM leaves tiles out
+//   FIRST, T1        the tiles; FIRST = TILE_FROM(t0)
+//   TABLE, T         which table row is staged as row `row` of tile t: j = TABLE.row(t, row) of T, [.][D], where
+//                    TABLE.has(j), else zeros (table_tiles: the rows in their order).  The load itself is written
+//                    here: behind a call it is scheduled differently.
+//   X, D, SROW       the rows' table, [.][D], and the rows' ids in it, [TOPK_TU] in LDS, -1 for zeros
+//   ST, SX           the staged chunks, [TOPK_TI][TOPK_LD] and [TOPK_TU][TOPK_LD]
+//   TILE_FROM(t)     the first tile at or after t that is walked, or T1 (without SKIP: t)
+//   FETCHED(t, c), STASHED(t, c)   what else travels with chunk c of tile t (walk_nop for nothing; k_neighbors' norms
+//                    at c == 0): called when the chunk has been asked for, global -> registers, and when it has been
+//                    written to LDS, before the barrier
+
+// the plain table side: tile t is rows TOPK_TI t .. + TOPK_TI - 1 of the N rows of T
+struct table_tiles {
+  int64_t N;
+  __device__ __forceinline__ int64_t row(int64_t t, int row) const { return t * TOPK_TI + row; }
+  __device__ __forceinline__ bool has(int64_t j) const { return j < N; }
+};
+
+struct walk_nop {
+  __device__ __forceinline__ void operator()(int64_t, int) const {}
+};
+
+// the lane's constants of a walk: the chunks of a row and where the lane reads its rows of the staged chunks
+#define BPR_WALK_LANE(D, ST, SX)                                              \
+  const int walk_nch_ = ((D) + bpr::TOPK_KC - 1) / bpr::TOPK_KC;              \
+  const float* const walk_ta_ = (ST) + (32 * w + r) * bpr::TOPK_LD + 4 * h;   \
+  const float* const walk_xb0_ = (SX) + r * bpr::TOPK_LD + 4 * h;             \
+  const float* const walk_xb1_ = (SX) + (32 + r) * bpr::TOPK_LD + 4 * h
+
+#define BPR_WALK_TILES_BEGIN(VEC, SKIP, FIRST, T1, TABLE, T, X, D, SROW, ST, SX, TILE_FROM, FETCHED, STASHED)         \
+  /* the next chunk travels global -> registers while the current one is multiplied, then registers -> LDS */         \
+  float4 walk_treg_[4], walk_xreg_[2];                                                                                \
+  auto walk_fetch_ = [&](int64_t t_, int c_) {                                                                        \
+    const int kc_ = c_ * bpr::TOPK_KC;                                                                                \
+    _Pragma("unroll") for (int m_ = 0; m_ < 4; ++m_) {                                                                \
+      const int f_ = tid + 256 * m_, row_ = f_ >> 3, kk_ = kc_ + 4 * (f_ & 7);                                        \
+      const int64_t j_ = (TABLE).row(t_, row_);                                                                       \
+      walk_treg_[m_] = (TABLE).has(j_) ? bpr::load4<VEC>((T) + j_ * (D), kk_, (D)) : make_float4(0.f, 0.f, 0.f, 0.f); \
+    }                                                                                                                 \
+    _Pragma("unroll") for (int m_ = 0; m_ < 2; ++m_) {                                                                \
+      const int f_ = tid + 256 * m_, row_ = f_ >> 3, kk_ = kc_ + 4 * (f_ & 7);                                        \
+      const int u_ = (SROW)[row_];                                                                                    \
+      walk_xreg_[m_] = u_ >= 0 ? bpr::load4<VEC>((X) + (int64_t)u_ * (D), kk_, (D)) : make_float4(0.f, 0.f, 0.f, 0.f); \
+    }                                                                                                                 \
+    FETCHED(t_, c_);                                                                                                  \
+  };                                                                                                                  \
+  auto walk_stash_ = [&]() {                                                                                          \
+    BPR_STASH_CHUNK((ST), walk_treg_, 4, tid, 256);                                                                   \
+    BPR_STASH_CHUNK((SX), walk_xreg_, 2, tid, 256);                                                                   \
+  };                                                                                                                  \
+  /* SKIP: walk_tn_ is the walked tile after the current one, found once a tile for the prefetch and the step.       \
+     Written so that without SKIP the loop is `for (t = FIRST; t < T1; ++t)` to the compiler                         \
+     (profiles/item_filter_resources.md). */                                                                          \
+  int64_t walk_tn_ = 0;                                                                                               \
+  auto walk_next_ = [&](int64_t t_) -> int64_t { return (SKIP) ? walk_tn_ : t_ + 1; };                                \
+  const int64_t walk_first_ = (FIRST);                                                                                \
+  if (walk_first_ < (T1)) walk_fetch_(walk_first_, 0);                                                                \
+  for (int64_t t = walk_first_; t < (T1); t = walk_next_(t)) {                                                        \
+    if constexpr (SKIP) walk_tn_ = TILE_FROM(t + 1);                                                                  \
+    bpr::f32x16 acc0 = {0.f}, acc1 = {0.f};                                                                           \
+    _Pragma("unroll") for (int q_ = 0; q_ < 16; ++q_) acc0[q_] = acc1[q_] = 0.f;                                      \
+    for (int c_ = 0; c_ < walk_nch_; ++c_) {                                                                          \
+      __syncthreads(); /* every wave is done with the chunk before, and with what the tile before left in LDS */      \
+      walk_stash_();                                                                                                  \
+      STASHED(t, c_);                                                                                                 \
+      __syncthreads(); /* the chunk is whole */                                                                       \
+      if (c_ + 1 < walk_nch_) walk_fetch_(t, c_ + 1);                                                                 \
+      else if (walk_next_(t) < (T1)) walk_fetch_(walk_next_(t), 0);                                                   \
+      bpr::mfma_chunk2(walk_ta_, walk_xb0_, walk_xb1_, acc0, acc1);                                                   \
+    }
+#define BPR_WALK_TILES_END }
 
 }  // namespace bpr

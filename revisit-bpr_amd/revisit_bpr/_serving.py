@@ -1,6 +1,7 @@
 """What the serving wrappers have in common (recommend, retrieve, sample, ranks, rerank, similar, diversify; fold-in
 takes `_table` and `seen_csr`), each block once: the table checks, the seen-CSR check, the id normalisation, the
-device refusals, the `None`-or-address idiom, the sizing calls and the workspace of a sliced call.
+device refusals, the `None`-or-address idiom, the sizing calls, the workspace of a sliced call, the `_rows` /
+`_rows_filtered` call of the families that take an item filter, and the one body of recommend and retrieve.
 
 A helper imposes no order: every wrapper calls them in ITS order, and where two wrappers word or condition a check
 differently the difference is a parameter — which refusal a malformed call meets, and in which words, is the
@@ -14,6 +15,7 @@ from typing import Optional
 import torch
 
 from revisit_bpr import native
+from revisit_bpr.item_filter import check_item_filter, check_item_filter_early
 
 
 def _table(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
@@ -93,3 +95,47 @@ def sliced_workspace(family: str, shape: tuple, item_slices: int, device, *, pre
     if words:
         return item_slices, torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=device), ws_bytes
     return item_slices, torch.empty(ws_bytes, dtype=torch.uint8, device=device), ws_bytes
+
+
+def call_rows(family: str, device, before: tuple, item_filter: Optional[torch.Tensor], after: tuple) -> None:
+    """`bpr_<family>_rows(*before, *after, stream)` on the current stream of `device`; with a filter
+    `bpr_<family>_rows_filtered(*before, filter, *after, stream)` — the filter's place in the argument list is where
+    the wrapper cuts its own.  No filter goes to the unfiltered entry point, whose messages carry its name."""
+    lib = native.load()
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        if item_filter is None:
+            native.check(getattr(lib, f"bpr_{family}_rows")(*before, *after, stream))
+        else:
+            native.check(getattr(lib, f"bpr_{family}_rows_filtered")(*before, item_filter.data_ptr(), *after, stream))
+
+
+def best_items(family: str, name: str, k_max: int, P, Q, item_bias, users, k, seen_indptr, seen_indices, *,
+               item_slices: int, check_users: bool, item_filter):
+    """The body of `recommend` (family "topk") and `retrieve` ("retrieve"): `name` is the caller in the messages,
+    `k_max` its largest k.  Their docstrings say what it returns."""
+    k = int(k)
+    if k > k_max:
+        raise ValueError(f"k = {k}: {name} returns at most {k_max} items per user")
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    item_filter = check_item_filter_early(item_filter, Q)
+    need_rocm(name, "the tables and the user list", (P, Q, users, item_bias, item_filter),
+              (P, Q, item_bias, users, seen_indptr, seen_indices, item_filter), "P")
+    native.load()
+    P, Q, item_bias, U, I, d = tables(P, Q, item_bias)
+    item_filter = check_item_filter(item_filter, I)
+    dev = P.device
+    users = int32_ids(users, strict=False)
+    n = users.numel()
+    seen_indptr, seen_indices = seen_csr(seen_indptr, seen_indices, U)
+    if check_users and n and bool(((users < 0) | (users >= U)).any()):
+        raise ValueError("user id out of range")
+    items = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    item_slices, ws, ws_bytes = sliced_workspace(family, (n, I, d, k), item_slices, dev)
+    call_rows(family, dev,
+              (P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(seen_indptr),
+               ptr(seen_indices)), item_filter,
+              (k, item_slices, ptr(ws), ws_bytes, items.data_ptr(), scores.data_ptr()))
+    return items, scores

@@ -14,7 +14,7 @@ import torch
 
 from revisit_bpr import native
 from revisit_bpr.item_filter import check_item_filter, check_item_filter_early
-from revisit_bpr._serving import int32_ids, need_rocm, ptr, query, seen_csr, sliced_workspace, tables
+from revisit_bpr._serving import call_rows, int32_ids, need_rocm, ptr, query, seen_csr, sliced_workspace, tables
 
 RANK_TMAX = 112  # bpr_rank_rows: targets of one kernel row (csrc/bpr_rank_plan.h); longer rows are split here
 
@@ -84,7 +84,7 @@ def rank_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tenso
     # (the shapes are checked on any device; the work is not done on any)
     need_rocm("rank_items", "the tables, the rows and the targets", (P, Q, users, tgt_indptr, tgt_items, item_filter),
               (P, Q, item_bias, users, tgt_indptr, tgt_items, seen_indptr, seen_indices, item_filter), "P")
-    lib = native.load()
+    native.load()
     dev = P.device
     tgt_indptr, tgt_items = tgt_indptr.contiguous(), tgt_items.reshape(-1).contiguous()
     total = tgt_items.numel()
@@ -107,16 +107,8 @@ def rank_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tenso
         users, tgt_indptr = split_rows(users, tgt_indptr)
         n = users.numel()
     item_slices, ws, ws_bytes = sliced_workspace("rank", (n, I, d), item_slices, dev)
-    with torch.cuda.device(dev):
-        if item_filter is not None:
-            native.check(lib.bpr_rank_rows_filtered(
-                P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, tgt_indptr.data_ptr(),
-                tgt_items.data_ptr(), ptr(seen_indptr), ptr(seen_indices), item_filter.data_ptr(), item_slices,
-                ptr(ws), ws_bytes, rank.data_ptr(), not_below.data_ptr(), score.data_ptr(),
-                torch.cuda.current_stream(dev).cuda_stream))
-            return rank, not_below, score
-        native.check(lib.bpr_rank_rows(
-            P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, tgt_indptr.data_ptr(),
-            tgt_items.data_ptr(), ptr(seen_indptr), ptr(seen_indices), item_slices, ptr(ws), ws_bytes,
-            rank.data_ptr(), not_below.data_ptr(), score.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    call_rows("rank", dev,
+              (P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, tgt_indptr.data_ptr(),
+               tgt_items.data_ptr(), ptr(seen_indptr), ptr(seen_indices)), item_filter,
+              (item_slices, ptr(ws), ws_bytes, rank.data_ptr(), not_below.data_ptr(), score.data_ptr()))
     return rank, not_below, score

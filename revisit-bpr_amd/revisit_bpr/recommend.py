@@ -12,9 +12,7 @@ from typing import Optional
 
 import torch
 
-from revisit_bpr import native
-from revisit_bpr.item_filter import check_item_filter, check_item_filter_early
-from revisit_bpr._serving import int32_ids, need_rocm, ptr, query, seen_csr, sliced_workspace, tables
+from revisit_bpr._serving import best_items, query
 
 TOPK_MAX = 128  # bpr_topk_rows: largest k
 
@@ -52,35 +50,5 @@ def recommend(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Tensor
     the I items, on the tables' device; only items whose bit is set are eligible — the result is the unfiltered
     ranking restricted to them, bit for bit, cut to k (`bpr_topk_rows_filtered`).
     """
-    k = int(k)
-    if k > TOPK_MAX:
-        raise ValueError(f"k = {k}: recommend returns at most {TOPK_MAX} items per user")
-    if k < 1:
-        raise ValueError("k must be at least 1")
-    item_filter = check_item_filter_early(item_filter, Q)
-    need_rocm("recommend", "the tables and the user list", (P, Q, users, item_bias, item_filter),
-              (P, Q, item_bias, users, seen_indptr, seen_indices, item_filter), "P")
-    lib = native.load()
-    P, Q, item_bias, U, I, d = tables(P, Q, item_bias)
-    item_filter = check_item_filter(item_filter, I)
-    dev = P.device
-    users = int32_ids(users, strict=False)
-    n = users.numel()
-    seen_indptr, seen_indices = seen_csr(seen_indptr, seen_indices, U)
-    if check_users and n and bool(((users < 0) | (users >= U)).any()):
-        raise ValueError("user id out of range")
-    items = torch.empty((n, k), dtype=torch.int32, device=dev)
-    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-    item_slices, ws, ws_bytes = sliced_workspace("topk", (n, I, d, k), item_slices, dev)
-    with torch.cuda.device(dev):
-        if item_filter is not None:
-            native.check(lib.bpr_topk_rows_filtered(
-                P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(seen_indptr),
-                ptr(seen_indices), item_filter.data_ptr(), k, item_slices, ptr(ws), ws_bytes, items.data_ptr(),
-                scores.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-            return items, scores
-        native.check(lib.bpr_topk_rows(
-            P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(seen_indptr),
-            ptr(seen_indices), k, item_slices, ptr(ws), ws_bytes, items.data_ptr(), scores.data_ptr(),
-            torch.cuda.current_stream(dev).cuda_stream))
-    return items, scores
+    return best_items("topk", "recommend", TOPK_MAX, P, Q, item_bias, users, k, seen_indptr, seen_indices,
+                      item_slices=item_slices, check_users=check_users, item_filter=item_filter)

@@ -17,7 +17,7 @@ import torch
 
 from revisit_bpr import native
 from revisit_bpr.item_filter import check_item_filter, check_item_filter_early
-from revisit_bpr._serving import int32_ids, need_rocm, ptr, query, seen_csr, sliced_workspace, tables
+from revisit_bpr._serving import call_rows, int32_ids, need_rocm, ptr, query, seen_csr, sliced_workspace, tables
 
 SAMPLE_MAX = 128  # bpr_sample_rows: largest k
 
@@ -77,7 +77,7 @@ def sample_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Ten
     item_filter = check_item_filter_early(item_filter, Q)
     need_rocm("sample_items", "the tables and the user list", (P, Q, users, item_bias, item_filter),
               (P, Q, item_bias, users, seen_indptr, seen_indices, draw_ids, item_filter), "P")
-    lib = native.load()
+    native.load()
     P, Q, item_bias, U, I, d = tables(P, Q, item_bias)
     item_filter = check_item_filter(item_filter, I)
     dev = P.device
@@ -98,19 +98,11 @@ def sample_items(P: torch.Tensor, Q: torch.Tensor, item_bias: Optional[torch.Ten
     log_z = torch.empty(n, dtype=torch.float32, device=dev) if return_log_z else None
     item_slices, ws, ws_bytes = sliced_workspace("sample", (n, I, d, k), item_slices, dev,
                                                  post=(int(bool(return_log_z)),), words=True)
-    with torch.cuda.device(dev):
-        if item_filter is not None:
-            native.check(lib.bpr_sample_rows_filtered(
-                P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(draw_ids),
-                ptr(seen_indptr), ptr(seen_indices), item_filter.data_ptr(), k, temperature, seed, item_slices,
-                ptr(ws), ws_bytes, items.data_ptr(), scores.data_ptr(), ptr(keys), ptr(log_z),
-                torch.cuda.current_stream(dev).cuda_stream))
-        else:
-            native.check(lib.bpr_sample_rows(
-                P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(draw_ids),
-                ptr(seen_indptr), ptr(seen_indices), k, temperature, seed, item_slices, ptr(ws), ws_bytes,
-                items.data_ptr(), scores.data_ptr(), ptr(keys), ptr(log_z),
-                torch.cuda.current_stream(dev).cuda_stream))
+    call_rows("sample", dev,
+              (P.data_ptr(), Q.data_ptr(), ptr(item_bias), I, d, users.data_ptr(), n, ptr(draw_ids), ptr(seen_indptr),
+               ptr(seen_indices)), item_filter,
+              (k, temperature, seed, item_slices, ptr(ws), ws_bytes, items.data_ptr(), scores.data_ptr(), ptr(keys),
+               ptr(log_z)))
     out = (items, scores)
     if return_keys:
         out += (keys,)

@@ -14,7 +14,7 @@ import torch
 
 from revisit_bpr import native
 from revisit_bpr.item_filter import check_item_filter, check_item_filter_early
-from revisit_bpr._serving import _table, int32_ids, need_rocm, ptr, query, sliced_workspace
+from revisit_bpr._serving import _table, call_rows, int32_ids, need_rocm, ptr, query, sliced_workspace
 from revisit_bpr.recommend import TOPK_MAX
 
 METRICS = {"dot": native.SIM_DOT, "cosine": native.SIM_COSINE}
@@ -77,7 +77,7 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
     item_filter = check_item_filter_early(item_filter, T)
     need_rocm("neighbors", "the tables and the row list", (X, T, rows, exclude, item_filter),
               (X, T, rows, exclude, item_filter), "X")
-    lib = native.load()
+    native.load()
     same = X is T
     T = _table(T, "T")
     X = T if same else _table(X, "X")
@@ -99,17 +99,9 @@ def neighbors(X: torch.Tensor, T: torch.Tensor, rows: torch.Tensor, k: int, *, m
     ids = torch.empty((n, k), dtype=torch.int32, device=dev)
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
     item_slices, ws, ws_bytes = sliced_workspace("neighbors", (n, N, d, k), item_slices, dev, pre=(code,))
-    with torch.cuda.device(dev):
-        if item_filter is not None:
-            native.check(lib.bpr_neighbors_rows_filtered(
-                X.data_ptr(), T.data_ptr(), N, d, rows.data_ptr(), n, ptr(exclude), first, code, item_filter.data_ptr(),
-                k, item_slices, ptr(ws), ws_bytes, ids.data_ptr(), scores.data_ptr(),
-                torch.cuda.current_stream(dev).cuda_stream))
-            return ids, scores
-        native.check(lib.bpr_neighbors_rows(
-            X.data_ptr(), T.data_ptr(), N, d, rows.data_ptr(), n, ptr(exclude), first, code, k, item_slices,
-            ptr(ws), ws_bytes, ids.data_ptr(), scores.data_ptr(),
-            torch.cuda.current_stream(dev).cuda_stream))
+    call_rows("neighbors", dev,
+              (X.data_ptr(), T.data_ptr(), N, d, rows.data_ptr(), n, ptr(exclude), first, code), item_filter,
+              (k, item_slices, ptr(ws), ws_bytes, ids.data_ptr(), scores.data_ptr()))
     return ids, scores
 
 
